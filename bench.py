@@ -9,18 +9,25 @@ the rank's 256 frames.  Frames are independent: rank r fits frames [r*256, (r+1)
 (weak scaling), no collective in the data path, one all_gather of the fitted-parameter
 records at the end of every step (RCCL over xGMI when N > 1).
 
-    python bench.py --gpus N --steps K --warmup W [--lbs dense|rows] [--frames 256]
+    python bench.py --gpus N --steps K --warmup W [--lbs dense|rows] [--frames 256] [--full] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 and no launcher environment (WORLD_SIZE unset) starts the N ranks itself
 (torch.distributed.run, one process per GPU, RCCL); under an external launcher it checks that the
 launcher's world size is N.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
+A plain run sets up, warms up, times K steps and prints ONE JSON line on rank 0: metric, value (frames/s),
+unit, higher_is_better, dtype, ms_per_step (one timed step) and the job's configuration.  `--dump-outputs DIR`
+writes what the last timed step returned to DIR/<name>.npy (dump_outputs).  `--full` adds every other
+measurement, and the line then carries extra objects:
   roofline          the dense LBS GEMM (k_lbs_dense16): algorithmic flops / HIP-event duration (MFMA bound)
   roofline_tick     the per-frame loss / adjoint / L-BFGS kernel (k_tick_dense): algorithmic bytes / duration
   cpu_baseline      the oracle (port of the reference path) timed on ALL host cores: latency mode
                     (1 process x all threads) and throughput mode (one single-threaded process per core)
   reference_parity  distribution of the final-loss difference to the REAL reference's fits of the golden frames
+  closure_parity    the HIP closure against fp64 autograd of the oracle at seeded points
+  alt, min3_camera_keypoints, configs3_single_gpu   the same job through the needed-rows path, on the
+                    min-3-camera-keypoints sequence, and configs[3]'s 1 024-frame job on this GPU
+  kernels_ms_avg, host   per-kernel HIP-event times of the timed steps and the host thread's side of the loop
   ranks             (N > 1) per-GPU frames/s, evaluation counts and the time of the RCCL gather
 """
 import argparse
@@ -148,6 +155,37 @@ def write_detail(full, tag):
     except Exception as e:          # a read-only tree must not cost the measurement
         print("[bench] detail file not written: %r" % e, file=sys.stderr)
         return None
+
+
+DUMP_LIMIT = 64 << 20       # bytes: --dump-outputs writes at most this much
+
+
+def dump_outputs(dirname, res, records):
+    """--dump-outputs DIR: what the last timed step returned -- every array of driver.fit_frames' result (this rank's
+    frames: fitted parameters, per-stage losses and evaluation counts) and the gathered records of all frames
+    (`records`) -- as DIR/<name>.npy.  float32 arrays stay float32, everything else (float64, integer and boolean
+    counts and flags: exact) is written as float64.  Above DUMP_LIMIT bytes in all, every array keeps the same seeded
+    sample of its rows (frames), listed in DIR/<name>_rows.npy.  Returns {name: shape} of what was written."""
+    arrays = dict(res)
+    arrays["records"] = records
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: (a if a.dtype == np.float32 else a.astype(np.float64)) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    keep = 1.0
+    if total > DUMP_LIMIT:      # what a sample costs per row kept: the row and its index in <name>_rows.npy (1 % left for headers)
+        keep = 0.99 * DUMP_LIMIT / (total + sum(8 * a.shape[0] for a in arrays.values() if a.ndim > 0))
+    os.makedirs(dirname, exist_ok=True)
+    written = {}
+    for k in sorted(arrays):
+        a = arrays[k]
+        if keep < 1.0 and a.ndim > 0 and a.shape[0] > 1:
+            n = a.shape[0]
+            rows = np.sort(np.random.RandomState(0).choice(n, max(1, int(n * keep)), replace=False))
+            a = a[rows]
+            np.save(os.path.join(dirname, k + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(dirname, k + ".npy"), np.ascontiguousarray(a))
+        written[k] = list(a.shape)
+    return written
 
 
 def item_rows_by_class(joint_map, n_extra, n_lmk, nbj):
@@ -685,7 +723,17 @@ def main():
     ap.add_argument("--slots", type=int, default=-1, help="dense mode: GEMM columns per GPU when --frames is larger (continuous "
                     "batching: retired columns are refilled from the frame queue, longest predicted fits first); 0 = one column per frame; "
                     "-1 (default) = driver.auto_slots: resident up to 512 frames, a 512-column pool beyond")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline as well (the --no-* switches above "
+                    "pick from it): CPU baseline, needed-rows and min-3-camera-keypoints measurements, configs[3]'s 1 024-frame "
+                    "job, reference and closure parity, per-kernel HIP-event times of the timed steps, roofline and host "
+                    "figures, the detail file.  Without it the run sets up, warms up, times --steps fits and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned to DIR/<name>.npy "
+                    "(float32 / float64, at most 64 MB: dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_cpu = args.no_alt = args.no_side = args.no_parity = args.no_configs3 = True
     if args.frames <= 0:
         args.frames = 256 if args.gpus == 1 else 1024
 
@@ -759,8 +807,9 @@ def main():
         return j.cpu().numpy()
     focal = float(cfg.get("focal_length") or 5000.0)
     frames = synthetic.make_frames(B, joints_fn, len(jm), start=rank * B, focal=focal)          # SURVEY 8(d) verbatim: the headline
-    frames_min3 = synthetic.make_frames(B, joints_fn, len(jm), start=rank * B, focal=focal, min_camera_keypoints=MIN_CAMERA_KEYPOINTS,
-                                        camera_keypoints=cfg.get("init_joints_idxs", (9, 12, 2, 5)))
+    frames_min3 = None if args.no_side else synthetic.make_frames(
+        B, joints_fn, len(jm), start=rank * B, focal=focal, min_camera_keypoints=MIN_CAMERA_KEYPOINTS,
+        camera_keypoints=cfg.get("init_joints_idxs", (9, 12, 2, 5)))
 
     from smplifyx_amd import driver, dist as sdist
     if args.slots < 0:
@@ -808,12 +857,14 @@ def main():
         one_fit()
     # (the persistent needed-rows kernel is launched a few dozen times per step: every launch is timed; the dense loop's
     #  thousands of launches are sampled)
+    # (--full only: a plain run times the fits without HIP events between their launches)
     prof_every = 1 if args.lbs == "rows" else args.prof_every
-    engine.prof_enable(True, every=prof_every)
-    engine.prof_reset()
-    engine.loop_host_stats(reset=True)
-    if pen:
-        engine.pen_work_reset()
+    if args.full:
+        engine.prof_enable(True, every=prof_every)
+        engine.prof_reset()
+        engine.loop_host_stats(reset=True)
+        if pen:
+            engine.pen_work_reset()
     sync()
     t0 = time.time()
     for _ in range(args.steps):
@@ -822,12 +873,16 @@ def main():
     dt_rank = time.time() - t0                     # this rank's own time (before waiting for the others)
     sync()
     dt = all_max(time.time() - t0)
-    engine.prof_enable(False)
-    # per-kernel HIP-event figures of the headline region (read before the side runs add their launches)
-    prof = {k: engine.prof_get(k) for k in ("lbs_dense", "tick", "fit_rows", "penetration")}
-    host = engine.loop_host_stats()            # the host thread's side of the timed fits (dense loops)
-    pair_us = event_pair_overhead_us()         # what a HIP-event pair around nothing reads: every timed scope over-reads by it
-    pen_work = engine.pen_work_get() if pen else None      # device counts over the timed region: grid entries, ordered pairs, columns
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, st, table)
+        print("[bench] outputs of the last timed step in %s: %s" % (args.dump_outputs, dumped), file=sys.stderr)
+    if args.full:
+        engine.prof_enable(False)
+        # per-kernel HIP-event figures of the headline region (read before the side runs add their launches)
+        prof = {k: engine.prof_get(k) for k in ("lbs_dense", "tick", "fit_rows", "penetration")}
+        host = engine.loop_host_stats()            # the host thread's side of the timed fits (dense loops)
+        pair_us = event_pair_overhead_us()         # what a HIP-event pair around nothing reads: every timed scope over-reads by it
+        pen_work = engine.pen_work_get() if pen else None      # device counts over the timed region: grid entries, ordered pairs, columns
     # configs[3]'s per-GPU job on THIS GPU (N = 1 only): 1 024 frames of the same generator through the default column pool, so that
     # a 1 -> N curve read off the driver's lines divides equal jobs (the N > 1 lines fit 1 024 frames per GPU and carry
     # `single_gpu_same_job_frames_per_s`; this is the same figure measured in the N = 1 run)
@@ -897,9 +952,6 @@ def main():
                  for r, v in enumerate(x.cpu().numpy() for x in allr)]
 
     if rank == 0:
-        ms_dense, n_dense, u_dense = prof["lbs_dense"]
-        ms_clo, n_clo, u_clo = prof["tick"]
-        ms_lb, n_lb, _ = prof["fit_rows"]
         tag = {"body": "configs[1]" if world == 1 else "configs[3]", "full": "configs[2]", "pen": "configs[4]"}[args.workload]
         what = {"body": "body-only K=25, camera + 5-stage L-BFGS (fit_smplx_smplifyx.yaml, use_vposer=False)",
                 "full": "hands+face K=135, VPoser in the loop, camera + 5-stage L-BFGS (fit_smplx_smplifyx.yaml)",
@@ -933,12 +985,32 @@ def main():
                        "arithmetic": "fp32 parameters, blend shapes, projection, losses, reverse sweep and optimiser (as the reference); "
                                      "fp64 inside the keypoint forward (rotations, kinematic chain, keypoint-vertex skinning), rounded "
                                      "to fp32 before the projection"},
-            "kernels_ms_avg": {"lbs_dense": ms_dense / max(n_dense, 1), "tick_dense": ms_clo / max(n_clo, 1),
-                               "fit_rows": ms_lb / max(n_lb, 1),
-                               "penetration": prof["penetration"][0] / max(prof["penetration"][1], 1),
-                               "timed_launches_per_step": (n_dense + n_clo + n_lb) / max(args.steps, 1)},
         }
         out["config"].update(loss_distribution(st["stage_loss"][:, -1]))
+        if ranks is not None:
+            out["ranks"] = ranks
+            out["config"]["closure_evals_per_s"] = float(sum(r["closure_evals_total"] for r in ranks) * args.steps / dt)
+            # the per-GPU rate of THIS job size: a rank's own B frames over its own time, before it waits for the others.
+            # rank 0's is a single-GPU run of the same job (frames are independent, no data-path collective), so scaling
+            # efficiency on equal jobs is value / (n_gpus x single_gpu_same_job); the driver's N=1 line is configs[1]'s
+            # smaller job (256 frames) and is not the denominator
+            rates = [r["frames_per_s"] for r in ranks]
+            out["config"].update(per_gpu_frames_per_s_min=min(rates), per_gpu_frames_per_s_mean=float(np.mean(rates)),
+                                 single_gpu_same_job_frames_per_s=rates[0],
+                                 per_gpu_closure_evals_max=max(r["closure_evals_per_frame_max"] for r in ranks),
+                                 gather_ms_max=max(r["gather_ms_last_step"] for r in ranks))
+        if not args.full:
+            line = json.dumps(compact_line(out), allow_nan=False)
+            assert len(line) < LINE_LIMIT and "\n" not in line, len(line)
+            print(line, flush=True)
+    if rank == 0 and args.full:
+        ms_dense, n_dense, u_dense = prof["lbs_dense"]
+        ms_clo, n_clo, u_clo = prof["tick"]
+        ms_lb, n_lb, _ = prof["fit_rows"]
+        out["kernels_ms_avg"] = {"lbs_dense": ms_dense / max(n_dense, 1), "tick_dense": ms_clo / max(n_clo, 1),
+                                 "fit_rows": ms_lb / max(n_lb, 1),
+                                 "penetration": prof["penetration"][0] / max(prof["penetration"][1], 1),
+                                 "timed_launches_per_step": (n_dense + n_clo + n_lb) / max(args.steps, 1)}
         if host["rounds"]:
             # where a step's wall time goes on the host: its thread enqueues (hidden behind the GPU on a quick host), waits for the
             # stage flags of a finished batch (= the GPU is the bottleneck: good), or neither (the GPU starved: the loop's wall
@@ -961,18 +1033,6 @@ def main():
         if side_min3 is not None:
             out["value_min3_camera_keypoints"] = side_min3["value"]
             out["min3_camera_keypoints"] = side_min3
-        if ranks is not None:
-            out["ranks"] = ranks
-            out["config"]["closure_evals_per_s"] = float(sum(r["closure_evals_total"] for r in ranks) * args.steps / dt)
-            # the per-GPU rate of THIS job size: a rank's own B frames over its own time, before it waits for the others.
-            # rank 0's is a single-GPU run of the same job (frames are independent, no data-path collective), so scaling
-            # efficiency on equal jobs is value / (n_gpus x single_gpu_same_job); the driver's N=1 line is configs[1]'s
-            # smaller job (256 frames) and is not the denominator
-            rates = [r["frames_per_s"] for r in ranks]
-            out["config"].update(per_gpu_frames_per_s_min=min(rates), per_gpu_frames_per_s_mean=float(np.mean(rates)),
-                                 single_gpu_same_job_frames_per_s=rates[0],
-                                 per_gpu_closure_evals_max=max(r["closure_evals_per_frame_max"] for r in ranks),
-                                 gather_ms_max=max(r["gather_ms_last_step"] for r in ranks))
         # counter-derived figures are REPLAYED from the profile of the same command (one summary per workload: tools/run_prof.sh)
         pmc_name = "pmc_summary_full.json" if full else "pmc_summary_pen.json" if pen else "pmc_summary.json"
         pmc = os.path.join(ROOT, "profiles", pmc_name)

@@ -58,6 +58,42 @@ def test_bench_refuses_a_launcher_world_size_that_differs_from_gpus():
     assert out.returncode != 0 and "must agree" in out.stderr
 
 
+def test_bench_refuses_zero_timed_steps():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], cwd=ROOT,
+                         capture_output=True, text=True, timeout=300)
+    assert out.returncode != 0 and "--steps" in out.stderr
+
+
+def test_dump_outputs_writes_every_array_as_float32_or_float64(tmp_path, monkeypatch):
+    """--dump-outputs: one DIR/<name>.npy per result array and the gathered records; float32 kept, float64 / integer /
+    boolean as float64 (values exact); above the byte limit, the same seeded rows of every array, and the rows listed."""
+    rng = np.random.RandomState(2)
+    B = 40
+    res = dict(body_pose=rng.randn(B, 63).astype(np.float32), stage_loss=rng.rand(B, 6),
+               stage_evals=rng.randint(0, 3000, (B, 6)).astype(np.int64), n_orient=np.ones(B, np.int32),
+               pen_order_dependent=np.zeros(B, bool))
+    rec = rng.randn(B, 90)
+    d = str(tmp_path / "out")
+    written = BB.dump_outputs(d, res, rec)
+    assert sorted(written) == sorted(list(res) + ["records"])
+    for k, v in list(res.items()) + [("records", rec)]:
+        a = np.load(os.path.join(d, k + ".npy"))
+        assert a.dtype == (np.float32 if v.dtype == np.float32 else np.float64), k
+        assert np.array_equal(a, v), k
+    # a limit below the total: every array keeps the same rows, deterministically, and the files fit under it
+    monkeypatch.setattr(BB, "DUMP_LIMIT", 16000)
+    d2, d3 = str(tmp_path / "s2"), str(tmp_path / "s3")
+    BB.dump_outputs(d2, res, rec)
+    BB.dump_outputs(d3, res, rec)
+    rows = np.load(os.path.join(d2, "records_rows.npy")).astype(np.int64)
+    assert 0 < len(rows) < B and np.array_equal(rows, np.load(os.path.join(d2, "body_pose_rows.npy")))
+    assert np.array_equal(np.load(os.path.join(d2, "records.npy")), rec[rows])
+    assert np.array_equal(np.load(os.path.join(d2, "stage_evals.npy")), res["stage_evals"][rows].astype(np.float64))
+    assert sum(os.path.getsize(os.path.join(d2, f)) for f in os.listdir(d2)) <= 16000 + 128 * len(os.listdir(d2))
+    for f in os.listdir(d2):
+        assert np.array_equal(np.load(os.path.join(d2, f)), np.load(os.path.join(d3, f))), f
+
+
 def test_record_widths_follow_the_configuration():
     """dist.pack_records / unpack_records with num_betas 16, 6 hand components, 20 expression coefficients (the cmd_parser
     default of num_pca_comps is 6): widths come from the result dict, frame index and evaluation count stay exact."""

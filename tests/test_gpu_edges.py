@@ -239,7 +239,7 @@ def test_bench_two_rank_control_flow_rehearsal(n, extra):
         env.pop(k, None)
     # exactly what the driver types, no launcher: bench.py starts its ranks itself
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n), "--steps", "1", "--warmup", "0",
-           "--frames", "32", "--no-cpu", "--no-alt"] + extra
+           "--frames", "32", "--no-cpu", "--no-alt", "--full"] + extra
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -292,7 +292,7 @@ def test_bench_line_contract(workload):
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "0", "--frames", "32", "--no-cpu",
-           "--no-alt", "--workload", workload]
+           "--no-alt", "--workload", workload, "--full"]
     out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -335,6 +335,35 @@ def test_bench_line_contract(workload):
         rp = d["roofline_pen"]
         assert rp["grid_entries_per_column"] > 0 and rp["pairs_per_column"] >= 0 and rp["columns_per_launch"] > 0
         assert rp["frac"] == pytest.approx(rp["achieved"] / rp["peak"], rel=1e-4)
+
+
+def test_bench_plain_run_times_the_headline_and_dumps_its_outputs(tmp_path):
+    """bench.py without --full: the contract line and nothing measured beside it (no CPU baseline, side fits, parity,
+    per-kernel or roofline figures, detail file), `--steps` timed steps, and --dump-outputs writes what the last timed step
+    returned -- the arrays agree with the figures of the line."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dump = str(tmp_path / "dump")
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "0", "--frames", "32",
+           "--dump-outputs", dump]
+    out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0], parse_constant=lambda c: (_ for _ in ()).throw(ValueError("non-strict JSON: " + c)))
+    assert d["metric"] == "fitted frames/sec" and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 2 and d["warmup"] == 0 and d["config"]["frames_per_gpu"] == 32
+    assert abs(d["value"] - 32 / (d["ms_per_step"] * 1e-3)) < 1e-4 * d["value"]       # (both figures are printed to 6 digits)
+    for k in ("roofline", "roofline_tick", "cpu_baseline", "reference_parity", "closure_parity", "alt", "kernels_ms_avg", "host",
+              "value_min3_camera_keypoints", "detail"):
+        assert k not in d, k
+    assert d["config"]["configs3_single_gpu_frames_per_s"] is None
+    fl, ev = np.load(os.path.join(dump, "final_loss.npy")), np.load(os.path.join(dump, "stage_evals.npy"))
+    assert fl.shape == (32,) and fl.dtype == np.float32 and ev.dtype == np.float64
+    assert fl[np.isfinite(fl)].mean() == pytest.approx(d["config"]["final_loss_mean"], rel=1e-5)
+    assert ev.sum(1).mean() == pytest.approx(d["config"]["closure_evals_per_frame_mean"], rel=1e-5)
+    bp, rec = np.load(os.path.join(dump, "body_pose.npy")), np.load(os.path.join(dump, "records.npy"))
+    assert bp.shape == (32, 63) and bp.dtype == np.float32 and rec.shape[0] == 32 and rec.dtype == np.float64
 
 
 @pytest.mark.parametrize("mode", ["rows", "dense"])

@@ -12,7 +12,7 @@ for tag in base "$@"; do
     env:*) EV="${tag#env:}" ;;
     *) export SFX_LIB=$GRAFT_REPO_ROOT/smplify-x-partial_amd/libsfx_$tag.so ;;
   esac
-  env $EV timeout 240 python bench.py --steps 4 --warmup 1 --no-cpu --no-parity --no-alt $ABFLAGS > /tmp/ab.json 2> /tmp/ab.err
+  env $EV timeout 240 python bench.py --steps 4 --warmup 1 --no-cpu --no-parity --no-alt --full $ABFLAGS > /tmp/ab.json 2> /tmp/ab.err
   python - <<P
 import json; d=json.load(open("/tmp/ab.json")); print("$tag", d["value"], d["config"]["final_loss_mean"], d["config"]["closure_evals_per_frame_mean"], "gemm", d["roofline"]["avg_launch_us"], "tick", d["roofline_tick"]["avg_launch_us"])
 P

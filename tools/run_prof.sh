@@ -11,7 +11,7 @@ set -x
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
 TAG=$1; shift
 O=$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG; mkdir -p $O
-CMD="python bench.py --steps 2 --warmup 1 --no-cpu --no-parity --no-alt --no-configs3 $*"
+CMD="python bench.py --steps 2 --warmup 1 --no-cpu --no-parity --no-alt --no-configs3 --full $*"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o p -- $CMD > $O/bench_under_rocprof.json 2> $O/kt.log
 PM="python bench.py --steps 1 --warmup 0 --no-cpu --no-alt --no-parity --no-configs3 $*"
 rm -rf /tmp/pmc_f /tmp/pmc_w /tmp/pmc_s /tmp/pmc_c

@@ -14,13 +14,13 @@ for w in body full pen rows; do
   cp gpurun_out/prof_${R}_$w/kt/p_kernel_stats.csv profiles/kernel_stats$s.csv
 done
 line() { tag=$1; shift; timeout 900 python bench.py "$@" > gpurun_out/${R}_bench_$tag.json 2> gpurun_out/${R}_bench_$tag.err; tail -c 300 gpurun_out/${R}_bench_$tag.err; head -c 400 gpurun_out/${R}_bench_$tag.json; echo; }
-line default
+line default --full
 cp gpurun_out/bench_detail_body.json gpurun_out/${R}_detail_body.json
-line full --workload full --steps 3
+line full --workload full --steps 3 --full
 cp gpurun_out/bench_detail_full.json gpurun_out/${R}_detail_full.json
-line pen --workload pen --steps 3
+line pen --workload pen --steps 3 --full
 cp gpurun_out/bench_detail_pen.json gpurun_out/${R}_detail_pen.json
-line rows --lbs rows --steps 3
+line rows --lbs rows --steps 3 --full
 cp gpurun_out/bench_detail_body_rows.json gpurun_out/${R}_detail_rows.json
-line 1024 --frames 1024 --steps 2 --no-cpu
+line 1024 --frames 1024 --steps 2 --no-cpu --full
 cp profiles/pmc_summary*.json profiles/kernel_stats*.csv gpurun_out/ 2>/dev/null
