@@ -99,6 +99,16 @@ typedef struct sfx_stage_weights {      /* one entry of opt_weights (fit_single_
     float bending_prior_weight;                   /* < 0: derive 3.17 * body_pose_weight (:567-568) */
 } sfx_stage_weights;
 
+typedef struct sfx_stage_weights_f64 {  /* the same fields in double: float64 batches (high_precision = 2), whose reference
+                                           run carries weights like 57.4 unrounded and forms 3.17 * body_pose_weight in double */
+    double body_pose_weight, shape_weight;
+    double hand_prior_weight, expr_prior_weight;
+    double jaw_prior_weight[3];
+    double hand_joint_weight, face_joint_weight;
+    double coll_loss_weight;                      /* (no interpenetration term in float64 mode: ignored) */
+    double bending_prior_weight;                  /* < 0: derive 3.17 * body_pose_weight in double */
+} sfx_stage_weights_f64;
+
 typedef struct sfx_batch_cfg {
     int32_t B;
     int32_t n_stages;               /* body stages (3 or 5)                              */
@@ -145,7 +155,16 @@ typedef struct sfx_batch_cfg {
     int32_t high_precision;         /* cfg float_dtype: float64 (main.py:99-105): besides the keypoint forward (always fp64) the
                                        projection up to the pixel residual is carried in fp64 in every stage -- gradient noise
                                        0.13 x torch fp32's, the fits behave like the reference's float64 run (LAB_NOTES.md §3.1);
-                                       parameters, reverse sweep and optimiser stay fp32                          */
+                                       parameters, reverse sweep and optimiser stay fp32.
+                                       Any nonzero value other than 2 selects this mode.
+                                       2: the closure in float64 (the arithmetic of the reference's float_dtype: float64 run):
+                                       parameters, rotations, blend-shape sums, projection, losses and the whole reverse
+                                       sweep in double (model tables stay fp32: widening them is exact).  Body-only needed-rows
+                                       batches: lbs_mode 0 without use_vposer, use_hands, use_face, interpenetration or the GMM
+                                       prior (refused by sfx_batch_create / sfx_batch_set_gmm).  The batch is driven through the
+                                       _f64 entry points below; float inputs (set_frames, set_params) are widened, float
+                                       outputs are refused, and the device optimiser (fit, step, guess_init, stats, trace) and
+                                       sfx_batch_forward are not available in this mode                             */
     int32_t point2plane;            /* DistanceFieldPenetrationLoss(point2plane=True) (cmd_parser.py:239): see
                                        sfx_pen_set_point2plane                                                     */
 } sfx_batch_cfg;
@@ -253,6 +272,29 @@ int  sfx_batch_set_gmm(sfx_batch* b, int32_t M, int32_t D, const float* means, c
  * comp_const [M] = 0.5 (log(det cov_m + epsilon) + D log 2 pi) (HOST); comp_const NULL = the merged form above.   */
 int  sfx_batch_set_gmm_form(sfx_batch* b, int32_t M, int32_t D, const float* means, const float* precisions,
                             const float* nll_weights, const float* comp_const);
+
+/* ---- float64 mode (sfx_batch_cfg.high_precision = 2); each of these refuses a batch of mode 0 or 1.
+ * sfx_batch_set_stage_weights_f64: the batch's stage weights [n_stages] in double (sfx_batch_create widens the float ones).
+ * sfx_batch_set_frames_f64: as sfx_batch_set_frames; camera (focal, center, data_weight = 1000 / H, est_tz) in double,
+ *   keypoints, weights, masks and rotation must hold fp32 values (kept in fp32 tables, as the reference reads them).
+ * sfx_batch_set_params_f64 / sfx_batch_get_params_f64: as sfx_batch_set_params / get_params in double; the regression
+ *   pose must hold fp32 values.  body_pose = the embedding (no VPoser in this mode).
+ * sfx_batch_closure_f64: as sfx_batch_closure, loss [B] and gradient [B][N] in double.
+ * sfx_batch_get_grad_f64: as sfx_batch_get_grad in double.                                                    */
+int  sfx_batch_set_stage_weights_f64(sfx_batch* b, const sfx_stage_weights_f64* stages /* [n_stages] */);
+int  sfx_batch_set_frames_f64(sfx_batch* b, const double* keypoints, const double* joint_weights,
+                              const double* cam_init_mask, const double* camera, const double* cam_rot);
+int  sfx_batch_set_params_f64(sfx_batch* b, const double* cam_translation, const double* global_orient,
+                              const double* betas, const double* lhand, const double* rhand,
+                              const double* expression, const double* jaw, const double* leye,
+                              const double* reye, const double* pose_embedding,
+                              const double* regression_pose);
+int  sfx_batch_get_params_f64(sfx_batch* b, double* cam_translation, double* global_orient,
+                              double* betas, double* lhand, double* rhand, double* expression,
+                              double* jaw, double* leye, double* reye, double* pose_embedding,
+                              double* body_pose);
+int  sfx_batch_closure_f64(sfx_batch* b, int32_t stage, double* loss_out, double* grad_out, void* stream);
+int  sfx_batch_get_grad_f64(sfx_batch* b, int32_t stage, double* grad_out);
 
 /* Final meshes / joints at the current parameters (dense LBS; DEVICE pointers, may be NULL). */
 int  sfx_batch_forward(sfx_batch* b, float* vertices_out_dev /* [B][V][3] */,

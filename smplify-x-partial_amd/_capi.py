@@ -15,6 +15,7 @@ _lib = None
 
 f32p = C.POINTER(C.c_float)
 i32p = C.POINTER(C.c_int32)
+f64p = C.POINTER(C.c_double)
 
 
 class ModelDesc(C.Structure):
@@ -38,6 +39,17 @@ class StageWeights(C.Structure):
         ("jaw_prior_weight", C.c_float * 3),
         ("hand_joint_weight", C.c_float), ("face_joint_weight", C.c_float),
         ("coll_loss_weight", C.c_float), ("bending_prior_weight", C.c_float),
+    ]
+
+
+class StageWeights64(C.Structure):
+    """sfx_stage_weights_f64: the stage weights of a float64 batch (high_precision = 2)."""
+    _fields_ = [
+        ("body_pose_weight", C.c_double), ("shape_weight", C.c_double),
+        ("hand_prior_weight", C.c_double), ("expr_prior_weight", C.c_double),
+        ("jaw_prior_weight", C.c_double * 3),
+        ("hand_joint_weight", C.c_double), ("face_joint_weight", C.c_double),
+        ("coll_loss_weight", C.c_double), ("bending_prior_weight", C.c_double),
     ]
 
 
@@ -78,6 +90,12 @@ SYMBOLS = {
     "sfx_batch_step": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, f32p, C.c_void_p]),
     "sfx_batch_pen_stats": (C.c_int, [C.c_void_p, i32p, i32p]),
     "sfx_batch_get_grad": (C.c_int, [C.c_void_p, C.c_int32, f32p]),
+    "sfx_batch_set_stage_weights_f64": (C.c_int, [C.c_void_p, C.POINTER(StageWeights64)]),
+    "sfx_batch_set_frames_f64": (C.c_int, [C.c_void_p] + [f64p] * 5),
+    "sfx_batch_set_params_f64": (C.c_int, [C.c_void_p] + [f64p] * 11),
+    "sfx_batch_get_params_f64": (C.c_int, [C.c_void_p] + [f64p] * 11),
+    "sfx_batch_closure_f64": (C.c_int, [C.c_void_p, C.c_int32, f64p, f64p, C.c_void_p]),
+    "sfx_batch_get_grad_f64": (C.c_int, [C.c_void_p, C.c_int32, f64p]),
     "sfx_batch_get_stats": (C.c_int, [C.c_void_p, f32p, i32p, i32p]),
     "sfx_lbfgs_two_loop": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "sfx_batch_trace": (C.c_int, [C.c_void_p, C.c_int32]),
@@ -186,6 +204,18 @@ def iptr(a):
 
 def f32(a):
     return np.ascontiguousarray(np.asarray(a), dtype=np.float32)
+
+
+def dptr(a):
+    """numpy float64 C-contiguous array -> double* (None -> NULL).  Keeps no reference."""
+    if a is None:
+        return None
+    assert a.dtype == np.float64 and a.flags["C_CONTIGUOUS"], (a.dtype, a.flags)
+    return a.ctypes.data_as(f64p)
+
+
+def f64(a):
+    return np.ascontiguousarray(np.asarray(a), dtype=np.float64)
 
 
 def i32(a):

@@ -191,7 +191,27 @@ struct sfx_batch {
     hipStream_t cap_stream = nullptr;   // capture happens on a stream of its own (the caller's may be the legacy NULL stream, which cannot capture)
     int* pen_stats_all = nullptr; // [B][stride] diagnostics of a CHUNKED evaluation (stand-alone call on a pooled batch), else unused
     bool pen_chunked = false;     // the most recent evaluation was chunked: sfx_batch_pen_stats reads pen_stats_all
+    bool f64 = false;             // float64 mode (high_precision = 2): X, Xt, f, g hold doubles, closures run k_closure64
+    StageW64* sw64_dev = nullptr; // [n_stages] its stage weights
 };
+
+// The float64 mode's guards.  Float inputs to a float64 batch are widened; float OUTPUTS are refused, so that no result is
+// silently rounded, and so is everything the mode does not have (the device optimiser, the dense path, the GMM prior).
+static int refuse_f64(const sfx_batch* b, const char* fn) {
+    if (b && b->f64) {
+        sfx_set_error("%s: not available on a float64 batch (high_precision = 2): use the _f64 entry points", fn); return -1; }
+    return 0;
+}
+static int need_f64(const sfx_batch* b, const char* fn) {
+    if (!b) { sfx_set_error("null batch"); return -1; }
+    if (!b->f64) { sfx_set_error("%s: the batch is not in float64 mode (high_precision = 2)", fn); return -1; }
+    return 0;
+}
+// values the float64 mode keeps in fp32 tables (keypoints, weights, masks, camera rotation, regression pose): exact or refused
+static bool fp32_exact(const double* v, size_t n) {
+    for (size_t i = 0; i < n; ++i) if (!((double)(float)v[i] == v[i]) && !std::isnan(v[i])) return false;
+    return true;
+}
 
 extern "C" int sfx_model_create(const sfx_model_desc* d, sfx_model** out) {
     if (!d || !out) { sfx_set_error("null argument"); return -1; }
@@ -285,6 +305,7 @@ extern "C" int sfx_model_create(const sfx_model_desc* d, sfx_model** out) {
     // folded joint regressor: J = J_template + J_dirs . coeff   (J_regressor . v_shaped)
     {
         std::vector<float> Jt((size_t)SFX_J * 3), Jd((size_t)SFX_J * 3 * S);
+        std::vector<double> Jt64(Jt.size()), Jd64(Jd.size());
         for (int j = 0; j < SFX_J; ++j) {
             std::vector<double> acc(3 + 3 * S, 0.0);
             const float* jr = d->J_regressor + (size_t)j * V;
@@ -298,12 +319,15 @@ extern "C" int sfx_model_create(const sfx_model_desc* d, sfx_model** out) {
                 }
             }
             for (int c = 0; c < 3; ++c) {
-                Jt[j * 3 + c] = (float)acc[c];
-                for (int l = 0; l < S; ++l) Jd[((size_t)j * 3 + c) * S + l] = (float)acc[3 + c * S + l];
+                Jt[j * 3 + c] = (float)acc[c]; Jt64[j * 3 + c] = acc[c];
+                for (int l = 0; l < S; ++l) {
+                    Jd[((size_t)j * 3 + c) * S + l] = (float)acc[3 + c * S + l]; Jd64[((size_t)j * 3 + c) * S + l] = acc[3 + c * S + l]; }
             }
         }
         M.J_template = m->mem.up(Jt);
         M.J_dirs = m->mem.up(Jd);
+        M.J_template64 = m->mem.up(Jt64);
+        M.J_dirs64 = m->mem.up(Jd64);
     }
     // kinematic tree: depth levels and child lists
     {
@@ -604,6 +628,12 @@ extern "C" int sfx_batch_create(sfx_model* m, const sfx_batch_cfg* c, const sfx_
     if (!m || !c || !out) { sfx_set_error("null argument"); return -1; }
     if (c->n_stages < 0 || c->n_stages > SFX_MAX_STAGES) { sfx_set_error("n_stages=%d unsupported", c->n_stages); return -1; }
     if (c->use_vposer && m->M.vp_latent == 0) { sfx_set_error("use_vposer without sfx_model_set_vposer"); return -1; }
+    if (c->high_precision == 2) {       // float64 end to end: the body-only needed-rows closure (FrameLDSSmall64) only
+        const char* why = c->lbs_mode != 0 ? "lbs_mode must be 0 (needed rows)" : c->use_vposer ? "use_vposer" : c->use_hands ? "use_hands" :
+                          c->use_face ? "use_face" : c->interpenetration ? "interpenetration" :
+                          m->M.n_items > SFX_SMALL_ITEMS ? "a model whose keypoints need more than 32 vertex rows" : nullptr;
+        if (why) { sfx_set_error("high_precision = 2 (float64) does not support %s", why); return -1; }
+    }
     sfx_batch* b = new sfx_batch();
     b->m = m; b->K = m->M.K;
     BatchDev& D = b->D;
@@ -618,6 +648,7 @@ extern "C" int sfx_batch_create(sfx_model* m, const sfx_batch_cfg* c, const sfx_
     D.cfg.side_thsh = c->side_view_thsh; D.cfg.lsh = c->left_shoulder_idx; D.cfg.rsh = c->right_shoulder_idx;
     D.cfg.pen = c->interpenetration ? 1 : 0;
     D.cfg.proj64 = c->high_precision ? 1 : 0;
+    b->f64 = c->high_precision == 2;
     // negative = the reference's default; 0 is a legal value of lbfgs_ls.LBFGS (it disables the test) and reaches the device as 0
     D.cfg.tol_grad = c->lbfgs_tolerance_grad >= 0 ? c->lbfgs_tolerance_grad : 1e-5;
     D.cfg.tol_change = c->lbfgs_tolerance_change >= 0 ? c->lbfgs_tolerance_change : 1e-9;
@@ -675,9 +706,28 @@ extern "C" int sfx_batch_create(sfx_model* m, const sfx_batch_cfg* c, const sfx_
         w.coll = D.cfg.pen ? st[i].coll_loss_weight : 0.f;
     }
     b->sw_dev = b->mem.up(sws);
+    if (b->f64) {       // the float weights widened; the reference's float64 run forms 3.17 * body_pose_weight in double
+        std::vector<StageW64> w64(std::max(1, c->n_stages));
+        for (int i = 0; i < c->n_stages; ++i) {
+            StageW64& w = w64[i];
+            w.bpw = st[i].body_pose_weight; w.sw = st[i].shape_weight;
+            w.bend = (st[i].bending_prior_weight >= 0.f) ? (double)st[i].bending_prior_weight : 3.17 * (double)st[i].body_pose_weight;
+            w.hpw = st[i].hand_prior_weight; w.epw = st[i].expr_prior_weight;
+            for (int q = 0; q < 3; ++q) w.jaw[q] = st[i].jaw_prior_weight[q];
+            w.hand_jw = st[i].hand_joint_weight; w.face_jw = st[i].face_joint_weight; w.coll = 0.0;
+        }
+        b->sw64_dev = b->mem.up(w64);
+    }
     D.Bpad = ((B + 127) / 128) * 128;
     D.X = b->mem.zeros<float>((size_t)B * SFX_NPAR_MAX);
     D.Xt = b->mem.zeros<float>((size_t)B * SFX_NPAR_MAX);
+    if (b->f64) {       // the float64 mode's own buffers (typed twins; the fp32 ones stay, unused)
+        D.X64 = b->mem.zeros<double>((size_t)B * SFX_NPAR_MAX);
+        D.Xt64 = b->mem.zeros<double>((size_t)B * SFX_NPAR_MAX);
+        D.f64 = b->mem.zeros<double>(B);
+        D.g64 = b->mem.zeros<double>((size_t)B * SFX_NVAR_MAX);
+        D.cam64 = b->mem.zeros<double>((size_t)B * 8);
+    }
     D.gt = b->mem.zeros<float>((size_t)B * K * 2);
     D.conf = b->mem.zeros<float>((size_t)B * K);
     D.jw = b->mem.zeros<float>((size_t)B * K);
@@ -822,6 +872,10 @@ extern "C" int sfx_batch_set_frames(sfx_batch* b, const float* kp, const float* 
         std::vector<float> c8((size_t)B * 8, 0.f);
         for (int i = 0; i < B; ++i) for (int q = 0; q < 6; ++q) c8[(size_t)i * 8 + q] = cam[(size_t)i * 6 + q];
         SFX_CHECK(hipMemcpy(b->D.cam, c8.data(), c8.size() * 4, hipMemcpyHostToDevice));
+        if (b->f64) {       // (float64 batch: the float camera widened)
+            std::vector<double> d8(c8.begin(), c8.end());
+            SFX_CHECK(hipMemcpy(b->D.cam64, d8.data(), d8.size() * 8, hipMemcpyHostToDevice));
+        }
     }
     if (camR) SFX_CHECK(hipMemcpy(b->D.camR, camR, (size_t)B * 9 * 4, hipMemcpyHostToDevice));
     pack_fd(b, 0);
@@ -829,7 +883,8 @@ extern "C" int sfx_batch_set_frames(sfx_batch* b, const float* kp, const float* 
     return 0;
 }
 
-static void put(std::vector<float>& X, int B, int off, int n, const float* src) {
+template <class T, class S>
+static void put(std::vector<T>& X, int B, int off, int n, const S* src) {
     if (!src) return;
     for (int i = 0; i < B; ++i) for (int q = 0; q < n; ++q) X[(size_t)i * SFX_NPAR_MAX + off + q] = src[(size_t)i * n + q];
 }
@@ -838,11 +893,31 @@ static void take(const std::vector<float>& X, int B, int off, int n, float* dst)
     for (int i = 0; i < B; ++i) for (int q = 0; q < n; ++q) dst[(size_t)i * n + q] = X[(size_t)i * SFX_NPAR_MAX + off + q];
 }
 
+// the parameter block of a float64 batch (doubles): sfx_batch_set_params widens float inputs into it
+template <class S>
+static int set_params64(sfx_batch* b, const S* cam_t, const S* go, const S* betas, const S* lh, const S* rh, const S* expr,
+                        const S* jaw, const S* leye, const S* reye, const S* emb) {
+    const int B = b->D.cfg.B; const ParLayout& L = b->D.L;
+    std::vector<double> X((size_t)B * SFX_NPAR_MAX);
+    SFX_CHECK(hipMemcpy(X.data(), b->D.X64, X.size() * 8, hipMemcpyDeviceToHost));
+    put(X, B, L.cam_t, 3, cam_t); put(X, B, L.go, 3, go); put(X, B, L.betas, L.NB, betas);
+    put(X, B, L.lh, L.NPCA, lh); put(X, B, L.rh, L.NPCA, rh); put(X, B, L.expr, L.NE, expr);
+    put(X, B, L.jaw, 3, jaw); put(X, B, L.leye, 3, leye); put(X, B, L.reye, 3, reye);
+    put(X, B, L.emb, L.NEMB, emb);
+    if (L.has_bodyp && emb) put(X, B, L.bodyp, 63, emb);
+    SFX_CHECK(hipMemcpy(b->D.X64, X.data(), X.size() * 8, hipMemcpyHostToDevice));
+    SFX_CHECK(hipMemcpy(b->D.Xt64, X.data(), X.size() * 8, hipMemcpyHostToDevice));
+    return 0;
+}
+
 extern "C" int sfx_batch_set_params(sfx_batch* b, const float* cam_t, const float* go, const float* betas,
                                     const float* lh, const float* rh, const float* expr, const float* jaw,
                                     const float* leye, const float* reye, const float* emb, const float* reg) {
     if (!b) { sfx_set_error("null batch"); return -1; }
     const int B = b->D.cfg.B; const ParLayout& L = b->D.L;
+    if (b->f64) {       // float inputs to a float64 batch: widened
+        if (int rc = set_params64(b, cam_t, go, betas, lh, rh, expr, jaw, leye, reye, emb)) return rc;
+    } else {
     std::vector<float> X((size_t)B * SFX_NPAR_MAX);
     SFX_CHECK(hipMemcpy(X.data(), b->D.X, X.size() * 4, hipMemcpyDeviceToHost));
     put(X, B, L.cam_t, 3, cam_t); put(X, B, L.go, 3, go); put(X, B, L.betas, L.NB, betas);
@@ -853,6 +928,7 @@ extern "C" int sfx_batch_set_params(sfx_batch* b, const float* cam_t, const floa
     if (L.has_bodyp && emb) put(X, B, L.bodyp, 63, emb);
     SFX_CHECK(hipMemcpy(b->D.X, X.data(), X.size() * 4, hipMemcpyHostToDevice));
     SFX_CHECK(hipMemcpy(b->D.Xt, X.data(), X.size() * 4, hipMemcpyHostToDevice));
+    }
     if (reg) {
         std::vector<float> r((size_t)B * 63, 0.f);
         for (int i = 0; i < B; ++i) for (int q = 0; q < L.NEMB; ++q) r[(size_t)i * 63 + q] = reg[(size_t)i * L.NEMB + q];
@@ -866,6 +942,7 @@ extern "C" int sfx_batch_set_params(sfx_batch* b, const float* cam_t, const floa
 extern "C" int sfx_batch_get_params(sfx_batch* b, float* cam_t, float* go, float* betas, float* lh, float* rh,
                                     float* expr, float* jaw, float* leye, float* reye, float* emb, float* body_pose) {
     if (!b) { sfx_set_error("null batch"); return -1; }
+    if (refuse_f64(b, "sfx_batch_get_params")) return -1;
     const int B = b->D.cfg.B; const ParLayout& L = b->D.L;
     std::vector<float> X((size_t)B * SFX_NPAR_MAX);
     SFX_CHECK(hipMemcpy(X.data(), b->D.X, X.size() * 4, hipMemcpyDeviceToHost));
@@ -885,9 +962,83 @@ extern "C" int sfx_batch_get_params(sfx_batch* b, float* cam_t, float* go, float
     return 0;
 }
 
+// ---- float64 mode (high_precision = 2)
+extern "C" int sfx_batch_set_stage_weights_f64(sfx_batch* b, const sfx_stage_weights_f64* st) {
+    if (need_f64(b, "sfx_batch_set_stage_weights_f64")) return -1;
+    if (!st) { sfx_set_error("null argument"); return -1; }
+    const int n = b->D.cfg.n_stages;
+    std::vector<StageW64> w64(std::max(1, n));
+    for (int i = 0; i < n; ++i) {
+        StageW64& w = w64[i];
+        w.bpw = st[i].body_pose_weight; w.sw = st[i].shape_weight;
+        w.bend = (st[i].bending_prior_weight >= 0.0) ? st[i].bending_prior_weight : 3.17 * st[i].body_pose_weight;
+        w.hpw = st[i].hand_prior_weight; w.epw = st[i].expr_prior_weight;
+        for (int q = 0; q < 3; ++q) w.jaw[q] = st[i].jaw_prior_weight[q];
+        w.hand_jw = st[i].hand_joint_weight; w.face_jw = st[i].face_joint_weight; w.coll = 0.0;
+    }
+    SFX_CHECK(hipMemcpy(b->sw64_dev, w64.data(), (size_t)n * sizeof(StageW64), hipMemcpyHostToDevice));
+    return 0;
+}
+
+extern "C" int sfx_batch_set_frames_f64(sfx_batch* b, const double* kp, const double* jw, const double* cmask,
+                                        const double* cam, const double* camR) {
+    if (need_f64(b, "sfx_batch_set_frames_f64")) return -1;
+    const int B = b->D.cfg.B, K = b->K;
+    // the keypoint tables stay fp32 (the reference reads fp32 keypoints too): their values must be fp32 numbers
+    if ((kp && !fp32_exact(kp, (size_t)B * K * 3)) || (jw && !fp32_exact(jw, (size_t)B * K)) ||
+        (cmask && !fp32_exact(cmask, (size_t)B * K)) || (camR && !fp32_exact(camR, (size_t)B * 9))) {
+        sfx_set_error("sfx_batch_set_frames_f64: keypoints, joint weights, masks and camera rotation must be fp32 values"); return -1; }
+    auto narrow = [](const double* v, size_t n) { return std::vector<float>(v, v + n); };
+    std::vector<float> k32, j32, m32, r32;
+    if (kp) k32 = narrow(kp, (size_t)B * K * 3);
+    if (jw) j32 = narrow(jw, (size_t)B * K);
+    if (cmask) m32 = narrow(cmask, (size_t)B * K);
+    if (camR) r32 = narrow(camR, (size_t)B * 9);
+    std::vector<float> c32;
+    if (cam) c32 = narrow(cam, (size_t)B * 6);      // (the fp32 record is only read by kernels the mode does not run)
+    if (int rc = sfx_batch_set_frames(b, kp ? k32.data() : nullptr, jw ? j32.data() : nullptr, cmask ? m32.data() : nullptr,
+                                      cam ? c32.data() : nullptr, camR ? r32.data() : nullptr)) return rc;
+    if (cam) {
+        std::vector<double> d8((size_t)B * 8, 0.0);
+        for (int i = 0; i < B; ++i) for (int q = 0; q < 6; ++q) d8[(size_t)i * 8 + q] = cam[(size_t)i * 6 + q];
+        SFX_CHECK(hipMemcpy(b->D.cam64, d8.data(), d8.size() * 8, hipMemcpyHostToDevice));
+    }
+    return 0;
+}
+
+extern "C" int sfx_batch_set_params_f64(sfx_batch* b, const double* cam_t, const double* go, const double* betas,
+                                        const double* lh, const double* rh, const double* expr, const double* jaw,
+                                        const double* leye, const double* reye, const double* emb, const double* reg) {
+    if (need_f64(b, "sfx_batch_set_params_f64")) return -1;
+    const int B = b->D.cfg.B, nemb = b->D.L.NEMB;
+    if (reg && !fp32_exact(reg, (size_t)B * nemb)) {
+        sfx_set_error("sfx_batch_set_params_f64: the regression pose is kept in fp32 and must hold fp32 values"); return -1; }
+    if (int rc = set_params64(b, cam_t, go, betas, lh, rh, expr, jaw, leye, reye, emb)) return rc;
+    if (reg) {
+        std::vector<float> r(reg, reg + (size_t)B * nemb);
+        return sfx_batch_set_params(b, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, r.data());
+    }
+    return 0;
+}
+
+extern "C" int sfx_batch_get_params_f64(sfx_batch* b, double* cam_t, double* go, double* betas, double* lh, double* rh,
+                                        double* expr, double* jaw, double* leye, double* reye, double* emb, double* body_pose) {
+    if (need_f64(b, "sfx_batch_get_params_f64")) return -1;
+    const int B = b->D.cfg.B; const ParLayout& L = b->D.L;
+    std::vector<double> X((size_t)B * SFX_NPAR_MAX);
+    SFX_CHECK(hipMemcpy(X.data(), b->D.X64, X.size() * 8, hipMemcpyDeviceToHost));
+    auto tk = [&](int off, int n, double* dst) {
+        if (dst) for (int i = 0; i < B; ++i) for (int q = 0; q < n; ++q) dst[(size_t)i * n + q] = X[(size_t)i * SFX_NPAR_MAX + off + q]; };
+    tk(L.cam_t, 3, cam_t); tk(L.go, 3, go); tk(L.betas, L.NB, betas); tk(L.lh, L.NPCA, lh); tk(L.rh, L.NPCA, rh);
+    tk(L.expr, L.NE, expr); tk(L.jaw, 3, jaw); tk(L.leye, 3, leye); tk(L.reye, 3, reye); tk(L.emb, L.NEMB, emb);
+    tk(L.emb, 63, body_pose);        // (no VPoser in this mode: body_pose is the embedding)
+    return 0;
+}
+
 #ifdef SFX_LAB       // include/sfx_lab.h
 extern "C" int sfx_debug_phase_clocks(sfx_batch* b, int32_t stage, int64_t* out /* [32] */) {
     if (!b) { sfx_set_error("null batch"); return -1; }
+    if (refuse_f64(b, "sfx_debug_phase_clocks")) return -1;
     long long* d = nullptr;
     SFX_CHECK(hipMalloc((void**)&d, 64 * sizeof(long long)));
     SFX_CHECK(hipMemset(d, 0, 64 * sizeof(long long)));
@@ -1102,6 +1253,7 @@ static int eval_closure(sfx_batch* b, int stage_override, int from_X, hipStream_
 
 extern "C" int sfx_batch_closure(sfx_batch* b, int32_t stage, float* loss_out, float* grad_out, void* stream) {
     if (!b) { sfx_set_error("null batch"); return -1; }
+    if (refuse_f64(b, "sfx_batch_closure")) return -1;
     if (stage >= b->D.cfg.n_stages) { sfx_set_error("stage %d out of range", stage); return -1; }
     hipStream_t s = (hipStream_t)stream;
     if (int rc = eval_closure(b, stage < 0 ? -1 : stage, 1, s)) return rc;
@@ -1113,6 +1265,25 @@ extern "C" int sfx_batch_closure(sfx_batch* b, int32_t stage, float* loss_out, f
         std::vector<float> g((size_t)B * SFX_NVAR_MAX);
         SFX_CHECK(hipMemcpy(g.data(), b->D.g, g.size() * 4, hipMemcpyDeviceToHost));
         for (int i = 0; i < B; ++i) memcpy(grad_out + (size_t)i * N, &g[(size_t)i * SFX_NVAR_MAX], (size_t)N * 4);
+    }
+    return 0;
+}
+
+extern "C" int sfx_batch_closure_f64(sfx_batch* b, int32_t stage, double* loss_out, double* grad_out, void* stream) {
+    if (need_f64(b, "sfx_batch_closure_f64")) return -1;
+    if (stage >= b->D.cfg.n_stages) { sfx_set_error("stage %d out of range", stage); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    ClosureArgs a{};
+    a.stage_override = stage < 0 ? -1 : stage; a.from_X = 1;
+    { ProfScope p("closure", s); launch_closure64(b->m->M, b->D, b->vl_dev, b->sw64_dev, a, s); }
+    SFX_CHECK(hipStreamSynchronize(s));
+    SFX_CHECK(hipGetLastError());
+    const int B = b->D.cfg.B, N = b->vl_host[stage < 0 ? 0 : 1].n;
+    if (loss_out) SFX_CHECK(hipMemcpy(loss_out, b->D.f64, (size_t)B * 8, hipMemcpyDeviceToHost));
+    if (grad_out) {
+        std::vector<double> g((size_t)B * SFX_NVAR_MAX);
+        SFX_CHECK(hipMemcpy(g.data(), b->D.g64, g.size() * 8, hipMemcpyDeviceToHost));
+        for (int i = 0; i < B; ++i) memcpy(grad_out + (size_t)i * N, &g[(size_t)i * SFX_NVAR_MAX], (size_t)N * 8);
     }
     return 0;
 }
@@ -1140,6 +1311,7 @@ __global__ void k_guess_init(BatchDev D, int K, const int* pairs, int n_pairs) {
 
 extern "C" int sfx_batch_guess_init(sfx_batch* b, const int32_t* pairs, int32_t n_pairs, void* stream) {
     if (!b) { sfx_set_error("null batch"); return -1; }
+    if (refuse_f64(b, "sfx_batch_guess_init")) return -1;
     hipStream_t s = (hipStream_t)stream;
     std::vector<int> pv(pairs, pairs + 2 * n_pairs);
     int* pd = nullptr;
@@ -1359,6 +1531,7 @@ static int run_ticks(sfx_batch* b, int first_stage, int last_stage, int init, in
 
 extern "C" int sfx_batch_fit(sfx_batch* b, int32_t first_stage, int32_t last_stage, void* stream) {
     if (!b) { sfx_set_error("null batch"); return -1; }
+    if (refuse_f64(b, "sfx_batch_fit")) return -1;
     if (first_stage < -1 || last_stage >= b->D.cfg.n_stages || last_stage < first_stage) {
         sfx_set_error("bad stage range [%d,%d]", first_stage, last_stage); return -1;
     }
@@ -1367,6 +1540,7 @@ extern "C" int sfx_batch_fit(sfx_batch* b, int32_t first_stage, int32_t last_sta
 
 extern "C" int sfx_batch_step(sfx_batch* b, int32_t stage, int32_t resume, float* loss_out, void* stream) {
     if (!b) { sfx_set_error("null batch"); return -1; }
+    if (refuse_f64(b, "sfx_batch_step")) return -1;
     if (stage < -1 || stage >= b->D.cfg.n_stages) { sfx_set_error("stage %d out of range", stage); return -1; }
     int rc = run_ticks(b, stage, stage, resume ? 2 : 1, 1, (hipStream_t)stream);
     if (rc) return rc;
@@ -1390,6 +1564,7 @@ extern "C" int sfx_batch_set_gmm(sfx_batch* b, int32_t M, int32_t Dm, const floa
 extern "C" int sfx_batch_set_gmm_form(sfx_batch* b, int32_t M, int32_t Dm, const float* means, const float* precisions,
                                       const float* nll_weights, const float* comp_const) {
     if (!b || !means || !precisions || !nll_weights) { sfx_set_error("null argument"); return -1; }
+    if (b->f64) { sfx_set_error("the mixture prior is fp32: not available on a float64 batch (high_precision = 2)"); return -1; }
     if (M < 1 || M > 2 * (256 / 64)) { sfx_set_error("1..8 mixture components supported, got %d", M); return -1; }
     if (b->D.cfg.use_vposer) { sfx_set_error("the mixture prior acts on body_pose: use_vposer must be off"); return -1; }
     if (Dm != b->D.L.NEMB) { sfx_set_error("mixture dimension %d != body pose dimension %d", Dm, b->D.L.NEMB); return -1; }
@@ -1465,6 +1640,7 @@ extern "C" int sfx_batch_pen_flags(sfx_batch* b, int32_t* flags_host /* [B] */) 
 
 extern "C" int sfx_batch_get_grad(sfx_batch* b, int32_t stage, float* grad_out) {
     if (!b || !grad_out) { sfx_set_error("null argument"); return -1; }
+    if (refuse_f64(b, "sfx_batch_get_grad")) return -1;
     if (stage < -1 || stage >= b->D.cfg.n_stages) { sfx_set_error("stage %d out of range", stage); return -1; }
     const int B = b->D.cfg.B, n = b->vl_host[stage < 0 ? 0 : 1].n;
     std::vector<float> g((size_t)B * SFX_NVAR_MAX);
@@ -1473,8 +1649,20 @@ extern "C" int sfx_batch_get_grad(sfx_batch* b, int32_t stage, float* grad_out) 
     return 0;
 }
 
+extern "C" int sfx_batch_get_grad_f64(sfx_batch* b, int32_t stage, double* grad_out) {
+    if (need_f64(b, "sfx_batch_get_grad_f64")) return -1;
+    if (!grad_out) { sfx_set_error("null argument"); return -1; }
+    if (stage < -1 || stage >= b->D.cfg.n_stages) { sfx_set_error("stage %d out of range", stage); return -1; }
+    const int B = b->D.cfg.B, n = b->vl_host[stage < 0 ? 0 : 1].n;
+    std::vector<double> g((size_t)B * SFX_NVAR_MAX);
+    SFX_CHECK(hipMemcpy(g.data(), b->D.g64, g.size() * 8, hipMemcpyDeviceToHost));
+    for (int i = 0; i < B; ++i) memcpy(grad_out + (size_t)i * n, g.data() + (size_t)i * SFX_NVAR_MAX, (size_t)n * 8);
+    return 0;
+}
+
 extern "C" int sfx_batch_trace(sfx_batch* b, int32_t capacity) {
     if (!b) { sfx_set_error("bad argument"); return -1; }
+    if (refuse_f64(b, "sfx_batch_trace")) return -1;
     BatchDev& D = b->D;
     D.trace_evals = capacity < 0 ? 1 : 0;          // negative capacity: also one record per closure evaluation (debug)
     if (capacity < 0) capacity = -capacity;
@@ -1499,6 +1687,7 @@ extern "C" int sfx_batch_trace(sfx_batch* b, int32_t capacity) {
 }
 
 extern "C" int sfx_batch_get_trace(sfx_batch* b, float* records, int32_t* counts) {
+    if (refuse_f64(b, "sfx_batch_get_trace")) return -1;
     if (!b || !b->D.trace) { sfx_set_error("no trace buffer attached (sfx_batch_trace)"); return -1; }
     const BatchDev& D = b->D;
     SFX_CHECK(hipDeviceSynchronize());
@@ -1509,6 +1698,7 @@ extern "C" int sfx_batch_get_trace(sfx_batch* b, float* records, int32_t* counts
 
 extern "C" int sfx_batch_get_stats(sfx_batch* b, float* stage_loss, int32_t* stage_evals, int32_t* stage_ref_evals) {
     if (!b) { sfx_set_error("null batch"); return -1; }
+    if (refuse_f64(b, "sfx_batch_get_stats")) return -1;
     const int B = b->D.cfg.B, NS = b->D.cfg.n_stages + 1;
     std::vector<float> l((size_t)B * (1 + SFX_MAX_STAGES));
     std::vector<int> e(l.size()), r(l.size());
@@ -1526,6 +1716,7 @@ extern "C" int sfx_batch_get_stats(sfx_batch* b, float* stage_loss, int32_t* sta
 
 extern "C" int sfx_batch_forward(sfx_batch* b, float* verts_dev, float* joints_dev, void* stream) {
     if (!b) { sfx_set_error("null batch"); return -1; }
+    if (refuse_f64(b, "sfx_batch_forward")) return -1;
     hipStream_t s = (hipStream_t)stream;
     const DevModel& M = b->m->M; const BatchDev& D = b->D;
     if (D.cfg.lbs_mode == 0 && !verts_dev) {       // needed-rows batch, joints only: the forward the rows closure runs

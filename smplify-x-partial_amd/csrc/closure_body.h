@@ -43,20 +43,38 @@ typedef float proj_t;
 #endif
 
 // camera.py:93-117: p_cam = R p + t, pixel = f p_cam.xy / p_cam.z + c; residual gt - pixel, all in T.
-template <class T>
-__device__ __forceinline__ void project_residual(const fwd_t* pj, const float* Rc, const float* ct, float fx, float fy, float cx,
-                                                 float cy, float gtx, float gty, float& pcx, float& pcy, float& pcz, float& rx,
-                                                 float& ry) {
+// O: the closure's working precision (float; double in the float64 mode)
+template <class T, class O>
+__device__ __forceinline__ void project_residual(const fwd_t* pj, const float* Rc, const O* ct, O fx, O fy, O cx,
+                                                 O cy, float gtx, float gty, O& pcx, O& pcy, O& pcz, O& rx,
+                                                 O& ry) {
     const T p[3] = {(T)pj[0], (T)pj[1], (T)pj[2]};
     const T pxd = (T)Rc[0] * p[0] + (T)Rc[1] * p[1] + (T)Rc[2] * p[2] + (T)ct[0];
     const T pyd = (T)Rc[3] * p[0] + (T)Rc[4] * p[1] + (T)Rc[5] * p[2] + (T)ct[1];
     const T pzd = (T)Rc[6] * p[0] + (T)Rc[7] * p[1] + (T)Rc[8] * p[2] + (T)ct[2];
-    pcx = (float)pxd; pcy = (float)pyd; pcz = (float)pzd;
-    rx = (float)((T)gtx - ((T)fx * (pxd / pzd) + (T)cx));
-    ry = (float)((T)gty - ((T)fy * (pyd / pzd) + (T)cy));
+    pcx = (O)pxd; pcy = (O)pyd; pcz = (O)pzd;
+    rx = (O)((T)gtx - ((T)fx * (pxd / pzd) + (T)cx));
+    ry = (O)((T)gty - ((T)fy * (pyd / pzd) + (T)cy));
 }
 __device__ __forceinline__ void sincos_t(double a, double* s, double* c) { sincos(a, s, c); }
 __device__ __forceinline__ void sincos_t(float a, float* s, float* c) { *s = sinf(a); *c = cosf(a); }
+// the closure's math at its working precision (float: the fp32 library calls of the fp32 closure, unchanged)
+__device__ __forceinline__ float r_sqrt(float a) { return sqrtf(a); }
+__device__ __forceinline__ double r_sqrt(double a) { return sqrt(a); }
+__device__ __forceinline__ float r_sin(float a) { return sinf(a); }
+__device__ __forceinline__ double r_sin(double a) { return sin(a); }
+__device__ __forceinline__ float r_cos(float a) { return cosf(a); }
+__device__ __forceinline__ double r_cos(double a) { return cos(a); }
+__device__ __forceinline__ float r_exp(float a) { return expf(a); }
+__device__ __forceinline__ double r_exp(double a) { return exp(a); }
+// batch_rodrigues' 1e-8 (a Python float: rounded to the tensor's dtype)
+template <class Real> __device__ __forceinline__ Real rodrigues_eps() { return (Real)1e-8; }
+template <> __device__ __forceinline__ float rodrigues_eps<float>() { return 1e-8f; }
+// an integer parked in a slot of the reduction scratch
+__device__ __forceinline__ void red_put_int(float& r, int n) { r = __int_as_float(n); }
+__device__ __forceinline__ void red_put_int(double& r, int n) { r = (double)n; }
+__device__ __forceinline__ int red_get_int(float r) { return __float_as_int(r); }
+__device__ __forceinline__ int red_get_int(double r) { return (int)r; }
 
 // threads per closure workgroup: a property of the LDS variant (FrameLDSx::kThreads) -- 256 for the body-only working set
 // (two or three workgroups share a CU), 512 for the full one (142 KB: the workgroup owns its CU, and what it does there is
@@ -122,37 +140,41 @@ __device__ __forceinline__ void lds_fill_async16(void* lds_dst, const void* gsrc
 // both (threads >= 256 hold no keypoint, parameter or item of this variant: they add zeros) or is dealt to kRowWaves = 4
 // wavefronts whatever the thread count (the adjoint's row streams), and the layout -- the forward-state blob two launches
 // hand each other -- does not depend on TH.
-template <int MAXI, bool VP, int TH = 0>
-struct __align__(16) FrameLDSx {
+// Real (the float64 mode, sfx_batch_cfg.high_precision = 2: double): the closure's working precision -- parameters,
+// rotations, blend-shape sums, item vertices and transforms, losses and the whole reverse sweep.  The copies of model
+// tables (vt, iw, ww, sjw, djw) stay fp32: the model is fp32 and widening it is exact.
+template <int MAXI, bool VP, int TH, class Real>
+struct __align__(16) FrameLDSBase {
+    using real_t = Real;
     static constexpr int kMaxItems = MAXI;
     static constexpr int kBlocksPerCU = (MAXI <= SFX_SMALL_ITEMS && !VP) ? SFX_SMALL_OCC : 1;    // register budget of the fused kernels
     static constexpr int kThreads = TH ? TH : ((MAXI <= SFX_SMALL_ITEMS && !VP) ? 256 : SFX_BIG_THREADS);
     static constexpr int kRowWaves = (MAXI <= SFX_SMALL_ITEMS && !VP) ? 4 : kThreads / 64;        // wavefronts that stream adjoint rows
     // scratch T: the item transforms, and (reverse sweep) one 512-float partial per row-streaming wavefront
     static constexpr int kScratch = (MAXI * 12 > kRowWaves * 512) ? MAXI * 12 : kRowWaves * 512;
-    float feat[SFX_KD_PAD];        // first: read as float4
-    float x[SFX_NPAR_MAX];
-    float full_pose[168];
-    float R[SFX_J * 9];
-    float Jr[SFX_J * 3];
-    float G[SFX_J * 12];
-    float A[SFX_J * 12];
+    Real  feat[SFX_KD_PAD];        // first: read as float4
+    Real  x[SFX_NPAR_MAX];
+    Real  full_pose[168];
+    Real  R[SFX_J * 9];
+    Real  Jr[SFX_J * 3];
+    Real  G[SFX_J * 12];
+    Real  A[SFX_J * 12];
     // the part of the forward whose ROUNDING NOISE decides when the line search stalls is carried in fp64 (see
     // "forward precision" below): skinning transforms and posed kinematic joints; saved with the prefix above
     fwd_t Ad[SFX_J * 12];
     fwd_t Gt[SFX_J * 3 + 3];      // (+3: keeps the saved prefix a multiple of 16 bytes in either precision)
-    float vp[MAXI * 3];            // v_posed of the items (template + blend offsets), for the reverse sweep
-    float vpo[MAXI * 3];           // the blend offsets alone (small numbers: fp32 sums of them carry ~1e-10 m)
+    Real  vp[MAXI * 3];            // v_posed of the items (template + blend offsets), for the reverse sweep
+    Real  vpo[MAXI * 3];           // the blend offsets alone (small numbers: fp32 sums of them carry ~1e-10 m)
     float vt[MAXI * 3];            // v_template rows of the items
-    alignas(16) float T[kScratch]; // item transforms [MAXI][12]; reused as scratch (>= 2048 floats) by the reverse sweep and, between
+    alignas(16) Real T[kScratch]; // item transforms [MAXI][12]; reused as scratch (>= 2048 floats) by the reverse sweep and, between
                                    // evaluations, as the working set of the optimiser tick (float4 accesses)
     fwd_t cd[2 * SFX_J * 12];     // kinematic chain in fp64: the two buffers of the pointer-jumping rounds
     fwd_t Jd[SFX_J * 3];          // rest joints, fp64
     fwd_t jd[SFX_MAX_K * 3];      // mapped joints, fp64 (what the projection reads)
-    float dvert[MAXI * 3];
-    float dvp[MAXI * 3];
+    Real  dvert[MAXI * 3];
+    Real  dvp[MAXI * 3];
     int   rl[MAXI * 3];            // compacted list of the blend-shape rows the adjoint streams (row = vertex * 3 + coordinate) ...
-    float rc[MAXI * 3];            // ... and their coefficients (d v_posed), nonzero entries only
+    Real  rc[MAXI * 3];            // ... and their coefficients (d v_posed), nonzero entries only
     int   ivid[MAXI];
     int   uslot[MAXI];             // static items: index of the item's vertex in the dense GEMM's export (BatchDev.uvp)
     float iw[MAXI];
@@ -165,42 +187,55 @@ struct __align__(16) FrameLDSx {
     int   djs[SFX_J + 1];          // the same for the dynamic-contour items of this frame's LUT row (DevModel.dynp_*)
     int   dji[kMaxDyn * SFX_NW];
     float djw[kMaxDyn * SFX_NW];
-    float joints[SFX_MAX_K * 3];
-    float dj[SFX_MAX_K * 3];
-    float dA[SFX_J * 12];
-    float dG[SFX_J * 12];
-    float drel[SFX_J * 3];
-    float dJ[SFX_J * 3];
-    float dR[SFX_J * 9];
-    float dfeat[SFX_KD_PAD];
-    float dpose[168];
-    float gc[SFX_NPAR_MAX];
-    float red[SFX_MAX_THREADS];
-    float lh45[SFX_NHAND], rh45[SFX_NHAND];    // } contiguous: saved / reloaded as one run of 2 * SFX_NHAND + 1 dwords
+    Real  joints[SFX_MAX_K * 3];
+    Real  dj[SFX_MAX_K * 3];
+    Real  dA[SFX_J * 12];
+    Real  dG[SFX_J * 12];
+    Real  drel[SFX_J * 3];
+    Real  dJ[SFX_J * 3];
+    Real  dR[SFX_J * 9];
+    Real  dfeat[SFX_KD_PAD];
+    Real  dpose[168];
+    Real  gc[SFX_NPAR_MAX];
+    Real  red[SFX_MAX_THREADS];
+    Real  lh45[SFX_NHAND], rh45[SFX_NHAND];    // } contiguous: saved / reloaded as one run of 2 * SFX_NHAND + 1 dwords
     int   lut_row;                             // }
     typename std::conditional<VP, VposerLDS, EmptyLDS>::type V;   // VPoser activations (use_vposer only)
     alignas(16) float fd[FD_N]; // this frame's keypoints / weights / camera / regression pose (image of BatchDev.fd)
     alignas(16) int meta[SFX_META_N];     // tree / joint-map tables (one coalesced load instead of
                                 // dependent global loads inside every level of the chain)
 };
+template <int MAXI, bool VP, int TH = 0>
+struct FrameLDSx : FrameLDSBase<MAXI, VP, TH, float> {};
 using FrameLDS = FrameLDSx<SFX_MAX_ITEMS, true>;
 using FrameLDSSmall = FrameLDSx<SFX_SMALL_ITEMS, false>;
 using FrameLDSSmall8 = FrameLDSx<SFX_SMALL_ITEMS, false, 512>;      // the same set on eight wavefronts (k_tick_dense, a workgroup per CU)
+// the body-only set in double (float64 mode, needed-rows path): one workgroup per CU
+struct FrameLDSSmall64 : FrameLDSBase<SFX_SMALL_ITEMS, false, 0, double> {};
+static_assert(sizeof(FrameLDSSmall64) + 4096 <= 160 * 1024, "float64 closure working set: LDS of one workgroup");
 
 __device__ __forceinline__ float wave_sum(float v) { return wave_sum_dpp(v); }
+__device__ __forceinline__ double wave_sum(double v) { return wave_sum_dpp(v); }
 template <int CTRL>
 __device__ __forceinline__ float lb_quad(float x) {       // DPP quad permutation of x (all lanes of the quad active)
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, true));
 }
+template <int CTRL>
+__device__ __forceinline__ double lb_quad(double x) {     // the same in fp64: both halves take the same permutation
+    const long long u = __double_as_longlong(x);
+    const int lo = __builtin_amdgcn_update_dpp(0, (int)u, CTRL, 0xf, 0xf, true);
+    const int hi = __builtin_amdgcn_update_dpp(0, (int)(u >> 32), CTRL, 0xf, 0xf, true);
+    return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
+}
 
 // fixed-order block reduction: DPP sum per wavefront, then the CT/64 partials in order
 // (2 barriers instead of a 9-barrier LDS tree); result in all threads
-template <int CT>
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    const float w = wave_sum_dpp(v);
+template <int CT, class Real>
+__device__ __forceinline__ Real block_sum(Real v, Real* red) {
+    const Real w = wave_sum_dpp(v);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
     __syncthreads();
-    float r = red[0];
+    Real r = red[0];
 #pragma unroll
     for (int i = 1; i < CT / 64; ++i) r += red[i];
     __syncthreads();
@@ -225,7 +260,8 @@ __device__ __forceinline__ void rodrigues_fwd(const float* th, float* R) {
 }
 
 // the same in fp64 (forward precision, see closure_body): R row-major
-__device__ __forceinline__ void rodrigues_fwd_d(const float* th, fwd_t* R) {
+template <class Tin>
+__device__ __forceinline__ void rodrigues_fwd_d(const Tin* th, fwd_t* R) {
     const fwd_t t0 = th[0], t1 = th[1], t2 = th[2];
     const fwd_t ex = t0 + (fwd_t)1e-8, ey = t1 + (fwd_t)1e-8, ez = t2 + (fwd_t)1e-8;
     const fwd_t a = sqrt(ex * ex + ey * ey + ez * ez);
@@ -244,30 +280,32 @@ __device__ __forceinline__ void rodrigues_fwd_d(const float* th, fwd_t* R) {
 }
 
 // reverse of rodrigues_fwd: dth += J^T dR
-__device__ __forceinline__ void rodrigues_bwd(const float* th, const float* dR, float* dth) {
-    const float ex = th[0] + 1e-8f, ey = th[1] + 1e-8f, ez = th[2] + 1e-8f;
-    const float a = sqrtf(ex * ex + ey * ey + ez * ez);
-    const float inv = 1.f / a;
-    const float d[3] = {th[0] * inv, th[1] * inv, th[2] * inv};
-    const float s = sinf(a), c = cosf(a), omc = 1.f - c;
-    const float K[9] = {0.f, -d[2], d[1], d[2], 0.f, -d[0], -d[1], d[0], 0.f};
-    float KK[9];
+template <class Real>
+__device__ __forceinline__ void rodrigues_bwd(const Real* th, const Real* dR, Real* dth) {
+    const Real eps = rodrigues_eps<Real>();
+    const Real ex = th[0] + eps, ey = th[1] + eps, ez = th[2] + eps;
+    const Real a = r_sqrt(ex * ex + ey * ey + ez * ez);
+    const Real inv = 1.f / a;
+    const Real d[3] = {th[0] * inv, th[1] * inv, th[2] * inv};
+    const Real s = r_sin(a), c = r_cos(a), omc = 1.f - c;
+    const Real K[9] = {0.f, -d[2], d[1], d[2], 0.f, -d[0], -d[1], d[0], 0.f};
+    Real KK[9];
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int j = 0; j < 3; ++j)
             KK[i * 3 + j] = K[i * 3 + 0] * K[j] + K[i * 3 + 1] * K[3 + j] + K[i * 3 + 2] * K[6 + j];
-    float dRK = 0.f, dRKK = 0.f;
+    Real dRK = 0.f, dRKK = 0.f;
 #pragma unroll
     for (int e = 0; e < 9; ++e) { dRK += dR[e] * K[e]; dRKK += dR[e] * KK[e]; }
-    float da = c * dRK + s * dRKK;
+    Real da = c * dRK + s * dRKK;
     // dK = s dR + (1-c) (dR K^T + K^T dR)
-    float dK[9];
+    Real dK[9];
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-            float t1 = 0.f, t2 = 0.f;
+            Real t1 = 0.f, t2 = 0.f;
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 t1 += dR[i * 3 + k] * K[j * 3 + k];     // dR K^T
@@ -275,27 +313,33 @@ __device__ __forceinline__ void rodrigues_bwd(const float* th, const float* dR, 
             }
             dK[i * 3 + j] = s * dR[i * 3 + j] + omc * (t1 + t2);
         }
-    const float dd[3] = {dK[7] - dK[5], dK[2] - dK[6], dK[3] - dK[1]};
-    const float ddth = dd[0] * th[0] + dd[1] * th[1] + dd[2] * th[2];
+    const Real dd[3] = {dK[7] - dK[5], dK[2] - dK[6], dK[3] - dK[1]};
+    const Real ddth = dd[0] * th[0] + dd[1] * th[1] + dd[2] * th[2];
     da -= ddth * inv * inv;
     dth[0] += dd[0] * inv + da * ex * inv;
     dth[1] += dd[1] * inv + da * ey * inv;
     dth[2] += dd[2] * inv + da * ez * inv;
 }
 
-__device__ __forceinline__ float gmof_grad(float r, float rho2) {
+template <class Real>
+__device__ __forceinline__ Real gmof_grad(Real r, Real rho2) {
     // d/dr [ rho^2 r^2 / (r^2 + rho^2) ] = 2 r rho^4 / (r^2 + rho^2)^2
-    const float den = r * r + rho2;
+    const Real den = r * r + rho2;
     return 2.f * r * (rho2 / den) * (rho2 / den);
 }
 
 // One closure evaluation of frame b by the whole workgroup (CT threads).  When `gflat` is not
 // NULL the flat gradient / loss are ALSO left in LDS (gflat[NVAR_MAX], *fout) for a consumer in
 // the same workgroup (fused kernels).
-template <class LDS>
+// Real = LDS::real_t: float, or double in the float64 mode (FrameLDSSmall64 with StageW64 weights; body-only needed-rows
+// path: the dense export, VPoser, the GMM prior and the interpenetration term are fp32-only and refused by api.hip).
+template <class LDS, class SW>
 __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const BatchDev& D,
-                                             const VarList* __restrict__ vls, const StageW* __restrict__ sws,
-                                             const ClosureArgs& args, const int b, float* gflat, float* fout) {
+                                             const VarList* __restrict__ vls, const SW* __restrict__ sws,
+                                             const ClosureArgs& args, const int b, typename LDS::real_t* gflat,
+                                             typename LDS::real_t* fout) {
+    using Real = typename LDS::real_t;
+    constexpr bool F64 = std::is_same<Real, double>::value;
     constexpr int CT = LDS::kThreads;
     const int t = threadIdx.x;
     const int lane = t & 63, wv = t >> 6;
@@ -305,7 +349,7 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
     const int stage = __builtin_amdgcn_readfirstlane((args.stage_override != -2) ? args.stage_override : D.stage[b]);
     if (stage >= C.n_stages && !args.forward_only) return;      // frame finished
     const bool cam_stage = (stage < 0);
-    const StageW sw = (cam_stage || args.forward_only) ? StageW{} : sws[stage];     // (11 scalars, requested here: the loss section is 20 k cycles away)
+    const SW sw = (cam_stage || args.forward_only) ? SW{} : sws[stage];     // (11 scalars, requested here: the loss section is 20 k cycles away)
 
     // Live keypoints of this evaluation.  Keypoints are ordered body | hands | face (+ contour) and the vertex items follow
     // that order; a stage whose hand / face joint weight is zero (fit_single_frame.py:569-572: the first three of the five
@@ -325,15 +369,17 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
     constexpr bool HAS_VP = !std::is_same<decltype(S.V), EmptyLDS>::value;
     constexpr int RIF = (LDS::kMaxItems <= SFX_SMALL_ITEMS) ? SFX_RIF_SMALL : SFX_RIF_BIG;
     constexpr int FWD_PREFIX = (int)(offsetof(LDS, vp) / sizeof(float));
-    static_assert(FWD_PREFIX % 4 == 0 && FWD_PREFIX + 96 + 2 * VP_H + 128 + 64 <= SFX_FWD_N, "forward-state blob layout");
+    static_assert(F64 || (FWD_PREFIX % 4 == 0 && FWD_PREFIX + 96 + 2 * VP_H + 128 + 64 <= SFX_FWD_N), "forward-state blob layout");
     static_assert(offsetof(LDS, Ad) % sizeof(fwd_t) == 0 && offsetof(LDS, cd) % sizeof(fwd_t) == 0, "forward-precision members");
-    const bool reuse = args.reuse_fwd != 0;
+    const bool reuse = !F64 && args.reuse_fwd != 0;      // (the forward-state blob is the dense path's: fp32 only)
     float* fwd = D.fwd ? D.fwd + (size_t)b * SFX_FWD_N : nullptr;
-    const float* xsrc = (args.from_X ? D.X : D.Xt) + (size_t)b * SFX_NPAR_MAX;
+    const Real* xsrc;
+    if constexpr (F64) xsrc = (args.from_X ? D.X64 : D.Xt64) + (size_t)b * SFX_NPAR_MAX;
+    else xsrc = (args.from_X ? D.X : D.Xt) + (size_t)b * SFX_NPAR_MAX;
     // every global source of this section goes to LDS asynchronously (lds_fill_async): one round trip for all of it
     if (!reuse) {
         if (args.x_lds) { for (int i = t; i < L.npar; i += CT) S.x[i] = args.x_lds[i]; }      // (published by the barrier below)
-        else lds_fill_async<CT>(S.x, xsrc, L.npar);
+        else lds_fill_async<CT>(S.x, xsrc, L.npar * (int)(sizeof(Real) / 4));
     }
     if (!args.keep_tables) {   // (a persistent workgroup keeps the tables and its frame's data in LDS between evaluations)
     static_assert(SFX_META_N % 4 == 0 && FD_N % 4 == 0 && offsetof(LDS, meta) % 16 == 0 && offsetof(LDS, fd) % 16 == 0, "16-byte copies");
@@ -352,7 +398,7 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
     }
     }
     if (reuse) {
-        static_assert(offsetof(LDS, lut_row) == offsetof(LDS, lh45) + 2 * SFX_NHAND * sizeof(float), "hand poses + LUT row are one run");
+        static_assert(F64 || offsetof(LDS, lut_row) == offsetof(LDS, lh45) + 2 * SFX_NHAND * sizeof(float), "hand poses + LUT row are one run");
         lds_fill_async16<CT>(&S, fwd, FWD_PREFIX / 4);
         const float* ex = fwd + FWD_PREFIX;
         lds_fill_async<CT>(S.lh45, ex, 2 * SFX_NHAND + 1);
@@ -368,7 +414,7 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
     for (int i = t; i < 168; i += CT) S.dpose[i] = 0.f;
     lds_dma_wait();
     __syncthreads();
-    const float* bodypose = S.x + L.emb;
+    const Real* bodypose = S.x + L.emb;
     if constexpr (HAS_VP) {
         if (C.use_vposer && !reuse) {          // body_pose = vposer.decode(pose_embedding) (fitting.py:236-238)
             vposer_forward<CT>(S.V, M, S.x + L.emb, S.T);
@@ -381,7 +427,7 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
     MARK(1);
     // ------------------------------------------------------------------ pose assembly
     if (t < SFX_POSE) {
-        float v;
+        Real v;
         if (t < 3) v = S.x[L.go + t];
         else if (t < 66) v = bodypose[t - 3];
         else if (t < 69) v = S.x[L.jaw + t - 66];
@@ -391,7 +437,7 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
             const bool left = t < 120;
             const int c = left ? t - 75 : t - 120;
             const float* comp = left ? M.comp_l : M.comp_r;
-            const float* pc = S.x + (left ? L.lh : L.rh);
+            const Real* pc = S.x + (left ? L.lh : L.rh);
             v = 0.f;
             for (int i = 0; i < L.NPCA; ++i) v += pc[i] * comp[i * SFX_NHAND + c];
             if (left) S.lh45[c] = v; else S.rh45[c] = v;
@@ -418,19 +464,27 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
         rodrigues_fwd_d(&S.full_pose[3 * t], R);
         fwd_t* src0 = (M.n_rounds & 1) ? (S.cd + SFX_J * 12) : S.cd;
 #pragma unroll
-        for (int e = 0; e < 9; ++e) { S.R[t * 9 + e] = (float)R[e]; src0[t * 12 + (e / 3) * 4 + e % 3] = R[e]; }
+        for (int e = 0; e < 9; ++e) { S.R[t * 9 + e] = (Real)R[e]; src0[t * 12 + (e / 3) * 4 + e % 3] = R[e]; }
         if (t > 0) {
 #pragma unroll
             for (int e = 0; e < 9; ++e)
-                S.feat[M.S + 9 * (t - 1) + e] = (float)(R[e] - ((e == 0 || e == 4 || e == 8) ? (fwd_t)1 : (fwd_t)0));
+                S.feat[M.S + 9 * (t - 1) + e] = (Real)(R[e] - ((e == 0 || e == 4 || e == 8) ? (fwd_t)1 : (fwd_t)0));
         }
     } else if (t >= 64 && t < 64 + SFX_J * 3) {
         const int i = t - 64;
+        if constexpr (F64) {        // (the folded regressor in double: J_regressor . v_shaped of the float64 model)
+            fwd_t v = M.J_template64[i];
+            const double* jd = M.J_dirs64 + (size_t)i * M.S;
+            for (int l = 0; l < M.S; ++l) v += jd[l] * S.feat[l];
+            S.Jd[i] = v;
+            S.Jr[i] = (Real)v;
+        } else {
         fwd_t v = M.J_template[i];
         const float* jd = M.J_dirs + (size_t)i * M.S;
         for (int l = 0; l < M.S; ++l) v += (fwd_t)jd[l] * (fwd_t)S.feat[l];
         S.Jd[i] = v;
-        S.Jr[i] = (float)v;
+        S.Jr[i] = (Real)v;
+        }
     }
     __syncthreads();
 
@@ -478,9 +532,9 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
             Adj[r * 4 + 0] = Gj[r * 4 + 0]; Adj[r * 4 + 1] = Gj[r * 4 + 1]; Adj[r * 4 + 2] = Gj[r * 4 + 2]; Adj[r * 4 + 3] = at;
             S.Gt[t * 3 + r] = Gj[r * 4 + 3];
 #pragma unroll
-            for (int c = 0; c < 4; ++c) S.G[t * 12 + r * 4 + c] = (float)Gj[r * 4 + c];
-            S.A[t * 12 + r * 4 + 0] = (float)Gj[r * 4 + 0]; S.A[t * 12 + r * 4 + 1] = (float)Gj[r * 4 + 1];
-            S.A[t * 12 + r * 4 + 2] = (float)Gj[r * 4 + 2]; S.A[t * 12 + r * 4 + 3] = (float)at;
+            for (int c = 0; c < 4; ++c) S.G[t * 12 + r * 4 + c] = (Real)Gj[r * 4 + c];
+            S.A[t * 12 + r * 4 + 0] = (Real)Gj[r * 4 + 0]; S.A[t * 12 + r * 4 + 1] = (Real)Gj[r * 4 + 1];
+            S.A[t * 12 + r * 4 + 2] = (Real)Gj[r * 4 + 2]; S.A[t * 12 + r * 4 + 3] = (Real)at;
         }
     }
     // dynamic-contour LUT row (smplx find_dynamic_lmk_idx_and_bcoords; no gradient)
@@ -490,7 +544,7 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
             float rel[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
             const int chain[5] = {12, 9, 6, 3, 0};
             for (int q = 0; q < 5; ++q) {
-                const float* Rk = &S.R[chain[q] * 9];
+                const Real* Rk = &S.R[chain[q] * 9];
                 float o[9];
                 for (int i = 0; i < 3; ++i)
                     for (int j = 0; j < 3; ++j)
@@ -511,7 +565,7 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
   }   // !reuse
     MARK(4);
     // ------------------------------------------------------------------ dense export
-    if (args.export_dense) {
+    if (!F64 && args.export_dense) {
         const int slot = D.slot[b];      // column of this frame in the GEMM operands (compacted)
         // coefficients of this frame: one contiguous 2-KiB row (entries >= KD are zero).  (As a COLUMN of a [K][frames]
         // matrix -- what the GEMM's A operand looks like in LDS -- these were 506 scattered 4-byte writes per frame into
@@ -569,7 +623,40 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
     // chunk of vertices that carry a penetration gradient)
     auto items_forward = [&](const int ib, const int ni) {       // items ib .. ib + ni - 1
     // v_posed rows: one wavefront per (item, coord) dot product of length KD_PAD
-    {
+    if constexpr (F64) {        // the same rows and passes; lane l holds feat[4l..4l+3] and feat[256+4l..], f64 products and sums
+        const double* fe = S.feat;
+        double fa[4], fb[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { fa[c] = fe[4 * lane + c]; fb[c] = fe[256 + 4 * lane + c]; }
+        const int nrow = ni * 3, rb = ib * 3;
+        const int rot = (int)((blockIdx.x * 40u) % (unsigned)nrow);
+        for (int w0 = wv * RIF; w0 < nrow; w0 += (CT / 64) * RIF) {
+            float4 da[RIF], db[RIF];
+            int myw, myrow;
+            {
+                const int u = lane < RIF ? lane : 0;
+                int w = ((w0 + u < nrow) ? w0 + u : w0) + rot;
+                w = w >= nrow ? w - nrow : w;
+                w += rb;
+                myw = w;
+                myrow = S.ivid[w / 3] * 3 + w % 3;
+            }
+#pragma unroll
+            for (int u = 0; u < RIF; ++u) {
+                const int r = __builtin_amdgcn_readlane(myrow, u);
+                const float4* row = reinterpret_cast<const float4*>(M.dirsT + (size_t)r * SFX_KD_PAD);
+                da[u] = row[lane]; db[u] = row[64 + lane];
+            }
+#pragma unroll
+            for (int u = 0; u < RIF; ++u) {
+                const int w = __builtin_amdgcn_readlane(myw, u);
+                double acc = fa[0] * (double)da[u].x + fa[1] * (double)da[u].y + fa[2] * (double)da[u].z + fa[3] * (double)da[u].w +
+                             fb[0] * (double)db[u].x + fb[1] * (double)db[u].y + fb[2] * (double)db[u].z + fb[3] * (double)db[u].w;
+                acc = wave_sum(acc);
+                if (lane == 0 && w0 + u < nrow) { S.vpo[w] = acc; S.vp[w] = (double)S.vt[w] + acc; }
+            }
+        }
+    } else {
         const float4* f4 = reinterpret_cast<const float4*>(S.feat);
         const float4 fa = f4[lane], fb = f4[64 + lane];
         // RIF rows per wavefront per pass: 2 RIF independent 1-KiB loads in flight before the reductions.
@@ -617,7 +704,7 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
     // (sparse weights: the static items' came with the tables, the dynamic items' with their LUT-row block)
     for (int w = t + ib * 12; w < (ib + ni) * 12; w += CT) {
         const int i = w / 12, e = w % 12;
-        float acc = 0.f;
+        Real acc = 0.f;
         if (S.wj[i * SFX_NW] >= 0) {
 #pragma unroll
             for (int q2 = 0; q2 < SFX_NW; ++q2) {
@@ -682,7 +769,7 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
             else for (int i = 0; i < n; ++i) v += item_vertex(i0 + i, r) * (fwd_t)S.iw[i0 + i];
         }
         S.jd[w] = v;
-        S.joints[w] = (float)v;
+        S.joints[w] = (Real)v;
     }
     __syncthreads();
     if (args.forward_only) {
@@ -696,22 +783,28 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
     // per-frame data was prefetched into LDS (S.fd) at kernel entry; all sums of this section go
     // through ONE fixed-order reduction (DPP per wavefront, then 4 partials): 2 barriers in total
     const float* fd = S.fd;
-    const float fx = fd[FD_CAM + 0], fy = fd[FD_CAM + 1], cx = fd[FD_CAM + 2], cy = fd[FD_CAM + 3];
-    const float dwt = fd[FD_CAM + 4], est_tz = fd[FD_CAM + 5];
+    Real fx, fy, cx, cy, dwt, est_tz;
+    if constexpr (F64) {        // (the float64 mode's camera record: data_weight = 1000 / H is no fp32 number)
+        const double* c64 = D.cam64 + (size_t)b * 8;
+        fx = c64[0]; fy = c64[1]; cx = c64[2]; cy = c64[3]; dwt = c64[4]; est_tz = c64[5];
+    } else {
+        fx = fd[FD_CAM + 0]; fy = fd[FD_CAM + 1]; cx = fd[FD_CAM + 2]; cy = fd[FD_CAM + 3];
+        dwt = fd[FD_CAM + 4]; est_tz = fd[FD_CAM + 5];
+    }
     const float* Rc = fd + FD_CAMR;
-    const float* ct = S.x + L.cam_t;
-    const float dw2 = dwt * dwt;
-    const float rho2 = C.rho * C.rho;
+    const Real* ct = S.x + L.cam_t;
+    const Real dw2 = dwt * dwt;
+    const Real rho2 = (Real)C.rho * (Real)C.rho;
 
     MARK(20);
-    float csum = 1.f;
+    Real csum = 1.f;
     if (cam_stage && C.use_conf_cam) {
-        float p = 0.f;
-        if (t < K) { const float cm = fd[FD_CMASK + t]; const float cf = fd[FD_CONF + t]; p = (cm != 0.f) ? cf * cf : 0.f; }
+        Real p = 0.f;
+        if (t < K) { const float cm = fd[FD_CMASK + t]; const Real cf = fd[FD_CONF + t]; p = (cm != 0.f) ? cf * cf : (Real)0.f; }
         csum = block_sum<CT>(p, S.red);
     }
     enum { Q_L = 0, Q_D0, Q_D1, Q_D2, Q_PP, Q_SH, Q_ANG, Q_LH, Q_RH, Q_EX, Q_JW, NQ };
-    float q[NQ];
+    Real q[NQ];
 #pragma unroll
     for (int i = 0; i < NQ; ++i) q[i] = 0.f;
     if (t >= KL && t < K) { S.dj[t * 3 + 0] = 0.f; S.dj[t * 3 + 1] = 0.f; S.dj[t * 3 + 2] = 0.f; }
@@ -722,41 +815,41 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
         // on the ftol test far from the minimum (1 of 96 reference frames, tests/golden/e2e_vposer_set.npz frame 14 --
         // the reference's fp32 run is exposed to the same coin toss).  Every later stage inherits this stage's camera;
         // its ~45 evaluations of K = 4 joints cost nothing.
-        float pcx, pcy, pcz, rx, ry;
+        Real pcx, pcy, pcz, rx, ry;
         if (cam_stage) project_residual<double>(&S.jd[t * 3], Rc, ct, fx, fy, cx, cy, fd[FD_GT + 2 * t], fd[FD_GT + 2 * t + 1], pcx, pcy, pcz, rx, ry);
-        else if (C.proj64) project_residual<double>(&S.jd[t * 3], Rc, ct, fx, fy, cx, cy, fd[FD_GT + 2 * t], fd[FD_GT + 2 * t + 1], pcx, pcy, pcz, rx, ry);      // (cfg float_dtype: float64)
+        else if (F64 || C.proj64) project_residual<double>(&S.jd[t * 3], Rc, ct, fx, fy, cx, cy, fd[FD_GT + 2 * t], fd[FD_GT + 2 * t + 1], pcx, pcy, pcz, rx, ry);      // (cfg float_dtype: float64)
         else project_residual<proj_t>(&S.jd[t * 3], Rc, ct, fx, fy, cx, cy, fd[FD_GT + 2 * t], fd[FD_GT + 2 * t + 1], pcx, pcy, pcz, rx, ry);
-        float du, dv;       // dL/du, dL/dv
+        Real du, dv;       // dL/du, dL/dv
         if (cam_stage) {
             if (fd[FD_CMASK + t] != 0.f) {
                 q[Q_L] = rx * rx + ry * ry;
                 du = -2.f * rx * csum * dw2; dv = -2.f * ry * csum * dw2;
             } else { du = 0.f; dv = 0.f; }
         } else {
-            float w = fd[FD_JW + t];
+            Real w = fd[FD_JW + t];
             if (t >= C.nbj) w = (t < C.nbj + 42) ? ((w != 0.f) ? sw.hand_jw : 0.f) : ((w != 0.f) ? sw.face_jw : 0.f);
             if (C.use_conf) w *= fd[FD_CONF + t];
-            const float w2 = w * w;
+            const Real w2 = w * w;
             if (w2 != 0.f) {
-                const float sx = rx * rx, sy = ry * ry;
-                const float gmx = rho2 * (sx / (sx + rho2)), gmy = rho2 * (sy / (sy + rho2));
+                const Real sx = rx * rx, sy = ry * ry;
+                const Real gmx = rho2 * (sx / (sx + rho2)), gmy = rho2 * (sy / (sy + rho2));
                 q[Q_L] = w2 * gmx + w2 * gmy;
                 du = -(w2 * dw2) * gmof_grad(rx, rho2);
                 dv = -(w2 * dw2) * gmof_grad(ry, rho2);
             } else { du = 0.f; dv = 0.f; }
         }
-        const float dix = du * fx, diy = dv * fy;
-        const float d0 = dix / pcz, d1 = diy / pcz, d2 = -(dix * pcx + diy * pcy) / (pcz * pcz);
+        const Real dix = du * fx, diy = dv * fy;
+        const Real d0 = dix / pcz, d1 = diy / pcz, d2 = -(dix * pcx + diy * pcy) / (pcz * pcz);
         q[Q_D0] = d0; q[Q_D1] = d1; q[Q_D2] = d2;
         S.dj[t * 3 + 0] = Rc[0] * d0 + Rc[3] * d1 + Rc[6] * d2;
         S.dj[t * 3 + 1] = Rc[1] * d0 + Rc[4] * d1 + Rc[7] * d2;
         S.dj[t * 3 + 2] = Rc[2] * d0 + Rc[5] * d1 + Rc[8] * d2;
     }
     MARK(21);
-    const float bpw2 = sw.bpw * sw.bpw, sw2 = sw.sw * sw.sw, h2 = sw.hpw * sw.hpw, e2 = sw.epw * sw.epw;
+    const Real bpw2 = sw.bpw * sw.bpw, sw2 = sw.sw * sw.sw, h2 = sw.hpw * sw.hpw, e2 = sw.epw * sw.epw;
     if (!cam_stage) {
         const bool latent_reg = C.use_vposer ? (stage + 1 == C.n_stages && C.has_reg) : (C.has_reg != 0);
-        const bool gmm = D.gmm_M > 0 && !C.use_vposer && !C.has_reg;
+        const bool gmm = !F64 && D.gmm_M > 0 && !C.use_vposer && !C.has_reg;
         if (gmm) {
             // MaxMixturePrior.merged_log_likelihood (prior.py:174-187) on body_pose = the embedding:
             //   min_m [ 0.5 (x - mu_m)^T P_m (x - mu_m) - log nll_weights_m ],  gradient through the minimum's component
@@ -779,24 +872,24 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
                 if (lane == 0 && m < D.gmm_M) S.red[m] = D.gmm_scale * quad + D.gmm_csel[m];      // (merged: 0.5 q - log nll_w; per component: q + const)
             }
             __syncthreads();
-            int best = 0; float bl = S.red[0];
-            for (int m = 1; m < D.gmm_M; ++m) { const float v = S.red[m]; if (v < bl) { bl = v; best = m; } }
+            int best = 0; Real bl = S.red[0];
+            for (int m = 1; m < D.gmm_M; ++m) { const Real v = S.red[m]; if (v < bl) { bl = v; best = m; } }
             __syncthreads();
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi)
                 if (wv + mi * (CT / 64) == best && lane < L.NEMB) S.gc[L.emb + lane] = (2.f * D.gmm_scale) * gy[mi] * bpw2;
             if (t == 0) q[Q_PP] = bl + D.gmm_cadd[best];
         } else if (t < L.NEMB) {       // pose prior on the embedding (fitting.py:390-401)
-            const float e = S.x[L.emb + t];
-            const float dlt = latent_reg ? (e - fd[FD_REG + t]) : e;
+            const Real e = S.x[L.emb + t];
+            const Real dlt = latent_reg ? (e - fd[FD_REG + t]) : e;
             q[Q_PP] = dlt * dlt;
             S.gc[L.emb + t] = 2.f * dlt * bpw2;
         }
-        if (t < L.NB) { const float bt = S.x[L.betas + t]; q[Q_SH] = bt * bt; S.gc[L.betas + t] = 2.f * bt * sw2; }
+        if (t < L.NB) { const Real bt = S.x[L.betas + t]; q[Q_SH] = bt * bt; S.gc[L.betas + t] = 2.f * bt * sw2; }
         if (t < 4) {            // angle prior: exp(pose[idx]*sign)^2 * bending weight (prior.py:73-89)
             const int idx = (t == 0) ? 52 : (t == 1) ? 55 : (t == 2) ? 9 : 12;
-            const float sg = (t == 0) ? 1.f : -1.f;
-            const float e = expf(S.full_pose[3 + idx] * sg);
+            const Real sg = (t == 0) ? 1.f : -1.f;
+            const Real e = r_exp(S.full_pose[3 + idx] * sg);
             q[Q_ANG] = e * e;
             S.dpose[3 + idx] = 2.f * (e * e) * sg * sw.bend;
         }
@@ -805,10 +898,10 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
             S.dpose[75 + t] = 2.f * S.lh45[t] * h2; S.dpose[120 + t] = 2.f * S.rh45[t] * h2;
         }
         if (C.use_face) {
-            if (t < L.NE) { const float ev = S.x[L.expr + t]; q[Q_EX] = ev * ev; S.gc[L.expr + t] = 2.f * ev * e2; }
+            if (t < L.NE) { const Real ev = S.x[L.expr + t]; q[Q_EX] = ev * ev; S.gc[L.expr + t] = 2.f * ev * e2; }
             if (t < 3) {    // (select, not sw.jaw[t]: a dynamically indexed struct becomes a per-thread LDS copy)
-                const float jwt = (t == 0) ? sw.jaw[0] : (t == 1) ? sw.jaw[1] : sw.jaw[2];
-                const float jv = S.x[L.jaw + t] * jwt; q[Q_JW] = jv * jv; S.gc[L.jaw + t] = 2.f * jv * jwt;
+                const Real jwt = (t == 0) ? sw.jaw[0] : (t == 1) ? sw.jaw[1] : sw.jaw[2];
+                const Real jv = S.x[L.jaw + t] * jwt; q[Q_JW] = jv * jv; S.gc[L.jaw + t] = 2.f * jv * jwt;
             }
         }
     }
@@ -820,32 +913,32 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
         if (wv < QW) {
 #pragma unroll
             for (int i = 0; i < NQ; ++i) {
-                const float w = wave_sum_dpp(q[i]);
+                const Real w = wave_sum_dpp(q[i]);
                 if (lane == 0) S.red[wv * NQ + i] = w;
             }
         }
         __syncthreads();
 #pragma unroll
         for (int i = 0; i < NQ; ++i) {
-            float r = S.red[i];
+            Real r = S.red[i];
 #pragma unroll
             for (int w = 1; w < QW; ++w) r += S.red[w * NQ + i];
             q[i] = r;
         }
     }
     MARK(23);
-    float total;
+    Real total;
     if (cam_stage) {
-        float joint = q[Q_L];
+        Real joint = q[Q_L];
         if (C.use_conf_cam) joint *= csum;
         joint *= dw2;
-        const float dz = ct[2] - est_tz;
-        float depth = 0.f;
-        if (C.depth_w > 0.f) depth = (C.depth_w * C.depth_w) * (dz * dz);
+        const Real dz = ct[2] - est_tz;
+        Real depth = 0.f;
+        if (C.depth_w > 0.f) depth = ((Real)C.depth_w * (Real)C.depth_w) * (dz * dz);
         total = joint + depth;
         if (t < 3) {
-            float g = (t == 0) ? q[Q_D0] : (t == 1) ? q[Q_D1] : q[Q_D2];
-            if (t == 2 && C.depth_w > 0.f) g += (C.depth_w * C.depth_w) * 2.f * dz;
+            Real g = (t == 0) ? q[Q_D0] : (t == 1) ? q[Q_D1] : q[Q_D2];
+            if (t == 2 && C.depth_w > 0.f) g += ((Real)C.depth_w * (Real)C.depth_w) * 2.f * dz;
             S.gc[L.cam_t + t] = g;
         }
     } else {
@@ -854,7 +947,7 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
         if (C.use_hands) total = total + q[Q_LH] * h2 + q[Q_RH] * h2;
         // interpenetration (fitting.py:437-455): evaluated on all vertices by csrc/collide.hip right
         // after the dense LBS; its vertex gradient enters the reverse sweep below
-        if (C.pen && args.use_dense_verts && sw.coll > 0.f) {
+        if (!F64 && C.pen && args.use_dense_verts && sw.coll > 0.f) {
             total = total + sw.coll * D.pen_loss[D.slot[b]];
             if (t == 0 && D.pen_over && D.pen_over[D.slot[b]]) D.pen_flag[b] = 1;      // (diagnostic: see BatchDev.pen_flag)
         }
@@ -890,7 +983,7 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
     for (int u = t; u < (SFX_J * 12) << gsh; u += CT) {
         const int w = u >> gsh, g = u & (gst - 1);
         const int j = w / 12, e = w % 12, r = e >> 2, c = e & 3;
-        float acc = 0.f;
+        Real acc = 0.f;
         const bool sj_lds = M.n_sj <= LDS::kMaxItems * SFX_NW;
         for (int pass = 0; pass < 2; ++pass) {
             const int* st = pass ? (dyn_lds ? S.djs : M.dj_start + (size_t)S.lut_row * (SFX_J + 1)) : (sj_lds ? S.sjs : M.sj_start);
@@ -900,8 +993,8 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
             for (int q2 = st[j] + g; q2 < st[j + 1]; q2 += gst) {
                 const int i = it[q2];
                 if (i >= NI) break;              // (lists ascend by item: the rest belongs to keypoints that are not live)
-                const float dv = S.dvert[i * 3 + r];
-                if (dv != 0.f) acc += wt[q2] * (dv * (c < 3 ? S.vp[i * 3 + c] : 1.f));
+                const Real dv = S.dvert[i * 3 + r];
+                if (dv != 0.f) acc += wt[q2] * (dv * (c < 3 ? S.vp[i * 3 + c] : (Real)1.f));
             }
         }
         if (gsh) {
@@ -921,16 +1014,16 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
         //    confidence contributes nothing and costs nothing)
         int nrows;
         {
-            float c3[3] = {0.f, 0.f, 0.f};
+            Real c3[3] = {0.f, 0.f, 0.f};
             if (t < ni) { c3[0] = S.dvp[t * 3]; c3[1] = S.dvp[t * 3 + 1]; c3[2] = S.dvp[t * 3 + 2]; }
             const unsigned long long b0 = __ballot(c3[0] != 0.f), b1 = __ballot(c3[1] != 0.f), b2 = __ballot(c3[2] != 0.f);
             const unsigned long long lt = (1ull << lane) - 1ull;
             int pos = __popcll(b0 & lt) + __popcll(b1 & lt) + __popcll(b2 & lt);
-            if (lane == 0) S.red[wv] = __int_as_float(__popcll(b0) + __popcll(b1) + __popcll(b2));
+            if (lane == 0) red_put_int(S.red[wv], __popcll(b0) + __popcll(b1) + __popcll(b2));
             __syncthreads();
             int tot = 0;
 #pragma unroll
-            for (int q2 = 0; q2 < CT / 64; ++q2) { const int n = __float_as_int(S.red[q2]); if (q2 < wv) pos += n; tot += n; }
+            for (int q2 = 0; q2 < CT / 64; ++q2) { const int n = red_get_int(S.red[q2]); if (q2 < wv) pos += n; tot += n; }
             nrows = tot;
             if (t < ni) {
                 const int v3 = S.ivid[t] * 3;
@@ -942,6 +1035,32 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
         // 2. stream them: lane u of a wavefront looks up entry u of the pass, v_readlane moves row index and coefficient
         //    into scalar registers, the loads use scalar base + lane offset (all RIF rows of a pass are requested back to back)
         constexpr int RW = LDS::kRowWaves;      // (<= CT / 64: wavefronts beyond it hold no rows and no partial)
+        if constexpr (F64) {        // the same streams with f64 partials, laid out as the float4 partials below
+            double pa[4] = {0., 0., 0., 0.}, pb[4] = {0., 0., 0., 0.};
+            if (wv < RW)
+            for (int w0 = wv * RIF; w0 < nrows; w0 += RW * RIF) {
+                float4 da[RIF], db[RIF];
+                const bool mine = lane < RIF && w0 + lane < nrows;
+                const int myrow = S.rl[mine ? w0 + lane : w0];
+                const double myc = mine ? S.rc[w0 + lane] : 0.;
+#pragma unroll
+                for (int u = 0; u < RIF; ++u) {
+                    const int r = __builtin_amdgcn_readlane(myrow, u);
+                    const float4* row = reinterpret_cast<const float4*>(M.dirsT + (size_t)r * SFX_KD_PAD);
+                    da[u] = row[lane]; db[u] = row[64 + lane];
+                }
+#pragma unroll
+                for (int u = 0; u < RIF; ++u) {
+                    const double dv = readlane_f64(myc, u);
+                    pa[0] += (double)da[u].x * dv; pa[1] += (double)da[u].y * dv; pa[2] += (double)da[u].z * dv; pa[3] += (double)da[u].w * dv;
+                    pb[0] += (double)db[u].x * dv; pb[1] += (double)db[u].y * dv; pb[2] += (double)db[u].z * dv; pb[3] += (double)db[u].w * dv;
+                }
+            }
+            if (wv < RW) {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) { S.T[wv * 512 + 4 * lane + c] = pa[c]; S.T[wv * 512 + 256 + 4 * lane + c] = pb[c]; }
+            }
+        } else {
         float4 pa = {0.f, 0.f, 0.f, 0.f}, pb = pa;
         if (wv < RW)
         for (int w0 = wv * RIF; w0 < nrows; w0 += RW * RIF) {
@@ -964,11 +1083,12 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
         }
         float4* part = reinterpret_cast<float4*>(S.T);          // S.T is dead here: one 512-float partial per wavefront
         if (wv < RW) { part[wv * 128 + lane] = pa; part[wv * 128 + 64 + lane] = pb; }
+        }
         __syncthreads();
         for (int k = t; k < SFX_KD_PAD; k += CT) {
             const int l4 = (k & 255) >> 2, hi = k >> 8, c = k & 3;
-            const float* pf = S.T + (hi * 64 + l4) * 4 + c;
-            float sumw = pf[0];
+            const Real* pf = S.T + (hi * 64 + l4) * 4 + c;
+            Real sumw = pf[0];
 #pragma unroll
             for (int w = 1; w < RW; ++w) sumw += pf[w * 512];
             S.dfeat[k] = accumulate ? S.dfeat[k] + sumw : sumw;
@@ -979,7 +1099,7 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
     items_dfeat(NI, false);
     // ---- interpenetration: its gradient lives on every vertex; lbs_adjoint.hip has already taken it
     // back to feat and to the skinning transforms (adjoint GEMM), the chain adjoint below does the rest
-    if (C.pen && args.use_dense_verts && !cam_stage && sw.coll > 0.f) {
+    if (!F64 && C.pen && args.use_dense_verts && !cam_stage && sw.coll > 0.f) {
         const int slot = D.slot[b];
         const float* pf = D.pen_dfeat + (size_t)slot * SFX_KD_PAD;
         const float* pa = D.pen_dA + (size_t)slot * SFX_J * 12;
@@ -995,29 +1115,30 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
     // atomics -> deterministic), pass C applies Gh_j^-T.  Then dR, d(rel) (pass D) and dJ (pass E).
     // (the 14 joint-regressor entries this thread needs for d(coefficients) below are requested here: they come from
     //  global memory and have the whole chain adjoint to arrive)
-    float jdv[14];
+    Real jdv[14];
     {
         const int l = t % 20, ch = t / 20;
 #pragma unroll
         for (int i = 0; i < 14; ++i) {
             const int row = ch * 14 + i;
-            jdv[i] = (ch < 12 && l < M.S && row < SFX_J * 3) ? M.J_dirs[(size_t)row * M.S + l] : 0.f;
+            if constexpr (F64) jdv[i] = (ch < 12 && l < M.S && row < SFX_J * 3) ? M.J_dirs64[(size_t)row * M.S + l] : 0.;
+            else jdv[i] = (ch < 12 && l < M.S && row < SFX_J * 3) ? M.J_dirs[(size_t)row * M.S + l] : 0.f;
         }
     }
-    float* Mpre = S.T;          // scratch: the item transforms are dead here
-    float* Ssub = S.T + 704;    // the subtree sums, before Gh_j^-T is applied (a second 660-float region of the same scratch)
+    Real* Mpre = S.T;          // scratch: the item transforms are dead here
+    Real* Ssub = S.T + 704;    // the subtree sums, before Gh_j^-T is applied (a second 660-float region of the same scratch)
     FOR_CT(w, SFX_J * 12) {
         const int d = w / 12, e = w % 12, r = e >> 2, k = e & 3;
-        const float* dAd = &S.dA[d * 12 + r * 4];
+        const Real* dAd = &S.dA[d * 12 + r * 4];
         // gradient on the joint's position from the keypoints mapped to it (a list of one or two entries: summed here by
         // each of the four threads of the row rather than in a pass of its own)
-        float dpj = 0.f;
+        Real dpj = 0.f;
         for (int q2 = S.meta[MO_SK0 + d]; q2 < S.meta[MO_SK0 + d + 1]; ++q2) dpj += S.dj[S.meta[MO_SKL + q2] * 3 + r];
-        const float l3 = dAd[3] + dpj;
-        float v = l3;
+        const Real l3 = dAd[3] + dpj;
+        Real v = l3;
         if (k < 3) {
-            const float* Gk = &S.G[d * 12 + k * 4];
-            const float* Jd = &S.Jr[d * 3];
+            const Real* Gk = &S.G[d * 12 + k * 4];
+            const Real* Jd = &S.Jr[d * 3];
             v = (dAd[0] - dAd[3] * Jd[0]) * Gk[0] + (dAd[1] - dAd[3] * Jd[1]) * Gk[1] + (dAd[2] - dAd[3] * Jd[2]) * Gk[2] + l3 * Gk[3];
         }
         Mpre[S.meta[MO_PRE + d] * 12 + e] = v;
@@ -1026,17 +1147,29 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
     FOR_CT(w, SFX_J * 12) {
         const int j = w / 12, e = w % 12;
         const int q0 = S.meta[MO_PRE + j], n = S.meta[MO_SUB + j];
-        float acc = 0.f;
+        Real acc = 0.f;
         for (int q2 = 0; q2 < n; ++q2) acc += Mpre[(q0 + q2) * 12 + e];
         Ssub[w] = acc;          // subtree sum, still in the basis of the world frame
     }
     __syncthreads();
     FOR_CT(w, SFX_J * 12) {
         const int j = w / 12, e = w % 12, r = e >> 2, c = e & 3;
-        const float* Sj = &Ssub[j * 12 + r * 4];
-        float v = Sj[3];
+        const Real* Sj = &Ssub[j * 12 + r * 4];
+        Real v = Sj[3];
         if (c < 3) {
-            const float* Gj = &S.G[j * 12];
+            const Real* Gj = &S.G[j * 12];
+            if constexpr (F64) {
+                // Gh_j^-T with the true inverse of the rotation block: batch_rodrigues' R is orthonormal only up to its 1e-8
+                // (|theta / ||theta + 1e-8||| != 1, ~1e-7 relative), which the transpose below absorbs in fp32 round-off but
+                // which is 1e-10 of the pose gradient in fp64.  Column k of R^-1 = (row k+1 x row k+2) / det R.
+                auto crs = [](const Real* p, const Real* q, const int i) {
+                    const int i1 = i == 2 ? 0 : i + 1, i2 = i == 0 ? 2 : i - 1;
+                    return p[i1] * q[i2] - p[i2] * q[i1]; };
+                const Real *a0 = Gj, *a1 = Gj + 4, *a2 = Gj + 8;
+                const Real det = a0[0] * crs(a1, a2, 0) + a0[1] * crs(a1, a2, 1) + a0[2] * crs(a1, a2, 2);
+                v = (crs(a1, a2, c) * (Sj[0] - Sj[3] * Gj[3]) + crs(a2, a0, c) * (Sj[1] - Sj[3] * Gj[7]) +
+                     crs(a0, a1, c) * (Sj[2] - Sj[3] * Gj[11])) / det;
+            } else
             v = Gj[c] * (Sj[0] - Sj[3] * Gj[3]) + Gj[4 + c] * (Sj[1] - Sj[3] * Gj[7]) + Gj[8 + c] * (Sj[2] - Sj[3] * Gj[11]);
         }
         S.dG[w] = v;
@@ -1045,26 +1178,26 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
     FOR_CT(w, SFX_J * 12) {
         const int j = w / 12, e = w % 12;
         const int p = S.meta[MO_PAR + j];
-        const float* dGj = &S.dG[j * 12];
+        const Real* dGj = &S.dG[j * 12];
         if (e < 9) {
             const int r = e / 3, c = e % 3;
-            float v;
+            Real v;
             if (p < 0) v = dGj[r * 4 + c];
-            else { const float* Gp = &S.G[p * 12]; v = Gp[0 + r] * dGj[0 + c] + Gp[4 + r] * dGj[4 + c] + Gp[8 + r] * dGj[8 + c]; }
+            else { const Real* Gp = &S.G[p * 12]; v = Gp[0 + r] * dGj[0 + c] + Gp[4 + r] * dGj[4 + c] + Gp[8 + r] * dGj[8 + c]; }
             if (j > 0) v += S.dfeat[M.S + 9 * (j - 1) + e];
             S.dR[j * 9 + e] = v;
         } else {
             const int r = e - 9;
-            float v;
+            Real v;
             if (p < 0) v = dGj[r * 4 + 3];
-            else { const float* Gp = &S.G[p * 12]; v = Gp[0 + r] * dGj[3] + Gp[4 + r] * dGj[7] + Gp[8 + r] * dGj[11]; }
+            else { const Real* Gp = &S.G[p * 12]; v = Gp[0 + r] * dGj[3] + Gp[4 + r] * dGj[7] + Gp[8 + r] * dGj[11]; }
             S.drel[j * 3 + r] = v;
         }
     }
     __syncthreads();
     for (int w = t; w < SFX_J * 3; w += CT) {
         const int j = w / 3, c = w % 3;
-        float v = -(S.G[j * 12 + 0 + c] * S.dA[j * 12 + 3] + S.G[j * 12 + 4 + c] * S.dA[j * 12 + 7] +
+        Real v = -(S.G[j * 12 + 0 + c] * S.dA[j * 12 + 3] + S.G[j * 12 + 4 + c] * S.dA[j * 12 + 7] +
                     S.G[j * 12 + 8 + c] * S.dA[j * 12 + 11]);
         for (int q2 = S.meta[MO_CS + j]; q2 < S.meta[MO_CS + j + 1]; ++q2) v -= S.drel[S.meta[MO_CL + q2] * 3 + c];
         S.dJ[w] = v + S.drel[w];
@@ -1073,20 +1206,20 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
     MARK(13);
     // Rodrigues adjoint -> dpose ; joint regression adjoint -> shape coefficients
     if (t < SFX_J) {
-        float dth[3] = {0.f, 0.f, 0.f};
+        Real dth[3] = {0.f, 0.f, 0.f};
         rodrigues_bwd(&S.full_pose[3 * t], &S.dR[t * 9], dth);
         S.dpose[3 * t] += dth[0]; S.dpose[3 * t + 1] += dth[1]; S.dpose[3 * t + 2] += dth[2];
     }
     {   // d(coefficients) = dfeat[0..S) + J_dirs^T dJ : 12 partial sums of 14 rows per coefficient
         const int ch = t / 20;
-        float acc = 0.f;
+        Real acc = 0.f;
 #pragma unroll
         for (int i = 0; i < 14; ++i) { const int row = ch * 14 + i; acc += jdv[i] * S.dJ[row < SFX_J * 3 ? row : 0]; }      // (rows past the end: jdv = 0)
         S.red[t] = acc;
     }
     __syncthreads();
     if (t < M.S) {
-        float acc = S.dfeat[t];
+        Real acc = S.dfeat[t];
         for (int ch = 0; ch < 12; ++ch) acc += S.red[ch * 20 + t];
         if (t < L.NB) S.gc[L.betas + t] += acc; else S.gc[L.expr + t - L.NB] += acc;
     }
@@ -1099,8 +1232,8 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
     if (t >= 128 && t < 128 + 2 * L.NPCA) {
         const int q = t - 128; const bool left = q < L.NPCA; const int i = left ? q : q - L.NPCA;
         const float* comp = (left ? M.comp_l : M.comp_r) + i * SFX_NHAND;
-        const float* dp = &S.dpose[left ? 75 : 120];
-        float acc = 0.f;
+        const Real* dp = &S.dpose[left ? 75 : 120];
+        Real acc = 0.f;
         for (int c = 0; c < SFX_NHAND; ++c) acc += comp[c] * dp[c];
         S.gc[(left ? L.lh : L.rh) + i] += acc;
     }
@@ -1108,9 +1241,15 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
     MARK(15);
     if constexpr (HAS_VP) if (C.use_vposer) vposer_backward<CT>(S.V, M, &S.dpose[3], &S.gc[L.emb], S.T);   // d body_pose -> d latent
     const VarList& vl = vls[cam_stage ? 0 : 1];
+    if constexpr (F64) {
+        double* gout = D.g64 + (size_t)b * SFX_NVAR_MAX;
+        for (int i = t; i < vl.n; i += CT) { const Real gv = S.gc[vl.idx[i]]; gout[i] = gv; if (gflat) gflat[i] = gv; }
+        if (t == 0) { D.f64[b] = total; if (fout) *fout = total; }
+    } else {
     float* gout = D.g + (size_t)b * SFX_NVAR_MAX;
-    for (int i = t; i < vl.n; i += CT) { const float gv = S.gc[vl.idx[i]]; gout[i] = gv; if (gflat) gflat[i] = gv; }
+    for (int i = t; i < vl.n; i += CT) { const Real gv = S.gc[vl.idx[i]]; gout[i] = gv; if (gflat) gflat[i] = gv; }
     if (t == 0) { D.f[b] = total; if (fout) *fout = total; }
+    }
     MARK(16);
 }
 

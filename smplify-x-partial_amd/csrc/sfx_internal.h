@@ -81,6 +81,9 @@ struct VarList {
 struct StageW {       // per body stage
     float bpw, sw, bend, hpw, epw, jaw[3], hand_jw, face_jw, coll;
 };
+struct StageW64 {     // the same in double: the float64 mode (sfx_batch_cfg.high_precision = 2)
+    double bpw, sw, bend, hpw, epw, jaw[3], hand_jw, face_jw, coll;
+};
 
 struct DevModel {
     int V, F, S, P, KD, K;            // S = NB+NE, P = 486, KD = S+P
@@ -155,6 +158,9 @@ struct DevModel {
     int vp_latent, vp_hidden;
     const float *vp_w1, *vp_b1, *vp_w2, *vp_b2, *vp_w3, *vp_b3;      // [512][L], [512][512], [126][512]
     const float *vp_w1T, *vp_w2T, *vp_w3T;                          // [L][512], [512][512], [512][128]
+    // the folded joint regressor before its rounding to fp32 (the float64 closure: J_regressor . v_shaped of a float64 model)
+    const double* J_template64;  // [J][3]
+    const double* J_dirs64;      // [J][3][S]
 };
 
 struct BatchCfgDev {
@@ -241,6 +247,13 @@ struct BatchDev {
     int*   trace_n;         // [B] records written
     int    trace_cap;
     int    trace_evals;     // 1: also one record (3, t, loss, |g|inf) per closure evaluation
+    // float64 mode (sfx_batch_cfg.high_precision = 2): typed twins of X, Xt, f, g (NULL in modes 0 / 1; a float64 batch keeps
+    // the fp32 ones allocated but never writes them) and the camera record -- fx fy cx cy data_weight est_tz - - -- in double
+    double* X64;            // [B][NPAR_MAX]
+    double* Xt64;           // [B][NPAR_MAX]
+    double* f64;            // [B]
+    double* g64;            // [B][NVAR_MAX]
+    double* cam64;          // [B][8]
 };
 
 enum { VEC_XINIT = 0, VEC_D, VEC_G, VEC_PREVG, VEC_GPREV, VEC_BG0, VEC_BG1, VEC_LSG0, NVEC };
@@ -269,6 +282,9 @@ static inline bool sfx_small_closure(const DevModel& M, const BatchDev& D) {
 }
 void launch_closure(const DevModel& M, const BatchDev& D, const VarList* vl_dev, const StageW* sw_dev,
                     const ClosureArgs& a, hipStream_t s);
+// the float64 closure (body-only needed-rows path: FrameLDSSmall64)
+void launch_closure64(const DevModel& M, const BatchDev& D, const VarList* vl_dev, const StageW64* sw_dev,
+                      const ClosureArgs& a, hipStream_t s);
 // d v_posed = T^T g of the interpenetration gradient, written by the kernel that forms g (k_pen_gather) when the caller is a
 // fitting batch: operand of the adjoint GEMM (lbs_adjoint.hip).  adj_G == nullptr: stand-alone operator, nothing to do.
 struct PenAdjPrep {

@@ -22,6 +22,31 @@ __device__ __forceinline__ float wave_sum_dpp(float x) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63));
 }
 
+// fp64 forms (sfx_batch_cfg.high_precision = 2): the two 32-bit halves travel through the same DPP moves (a source lane
+// that is absent gives +0.0 in both halves) and the adds are f64 -- the same fixed summation order as the fp32 sum
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ double dpp_shift_or_zero(double x) {
+    const long long u = __double_as_longlong(x);
+    const int lo = __builtin_amdgcn_update_dpp(0, (int)u, CTRL, ROW_MASK, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, (int)(u >> 32), CTRL, ROW_MASK, 0xf, false);
+    return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
+}
+// the value of lane `l` (wave-uniform l) in every lane
+__device__ __forceinline__ double readlane_f64(double x, int l) {
+    const long long u = __double_as_longlong(x);
+    const int lo = __builtin_amdgcn_readlane((int)u, l), hi = __builtin_amdgcn_readlane((int)(u >> 32), l);
+    return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
+}
+__device__ __forceinline__ double wave_sum_dpp(double x) {
+    x += dpp_shift_or_zero<0x111, 0xf>(x);   // row_shr:1
+    x += dpp_shift_or_zero<0x112, 0xf>(x);   // row_shr:2
+    x += dpp_shift_or_zero<0x114, 0xf>(x);   // row_shr:4
+    x += dpp_shift_or_zero<0x118, 0xf>(x);   // row_shr:8
+    x += dpp_shift_or_zero<0x142, 0xa>(x);   // row_bcast:15 into rows 1,3
+    x += dpp_shift_or_zero<0x143, 0xc>(x);   // row_bcast:31 into rows 2,3 -> lane 63 = total
+    return readlane_f64(x, 63);
+}
+
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ float dpp_shift_or_self(float x) {
     return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(x), __float_as_int(x), CTRL, ROW_MASK, 0xf, false));

@@ -24,9 +24,10 @@ def _jaw_weights(cfg, shape_weights):
     return [[float(v) for v in e.split(",")] if isinstance(e, str) else [float(v) for v in e] for e in jw]
 
 
-def stage_weights_from_cfg(cfg):
+def stage_weights_from_cfg(cfg, struct=None):
     """Per-stage weights exactly as fit_single_frame.py:133-207,330-353 assembles them
-    (defaults, zip-truncation to the shortest list)."""
+    (defaults, zip-truncation to the shortest list).  struct: capi.StageWeights (default) or capi.StageWeights64 (the
+    float64 mode: the Python floats kept unrounded)."""
     use_hands, use_face = cfg.get("use_hands", True), cfg.get("use_face", True)
     bpw = cfg.get("body_pose_prior_weights") or [4.04 * 1e2, 4.04 * 1e2, 57.4, 4.78]
     n = len(bpw)
@@ -48,7 +49,7 @@ def stage_weights_from_cfg(cfg):
     ns = min(len(v) for v in lists.values())
     out = []
     for i in range(ns):
-        w = capi.StageWeights()
+        w = (struct or capi.StageWeights)()
         w.body_pose_weight = lists["bpw"][i]
         w.shape_weight = lists["shape"][i]
         w.hand_prior_weight = lists["hprior"][i] if use_hands else 0.0
@@ -190,18 +191,69 @@ class DeviceModel(object):
             pass
 
 
+PRECISIONS = ("mixed", "float64")
+
+
+def check_precision(cfg, lbs_mode="rows", has_regression_pose=True, precision="mixed"):
+    """sfx_batch_cfg.high_precision of a FrameBatch (include/sfx.h):
+      "mixed" (default): cfg float_dtype picks 0 (float32) or 1 (float64: fp64 projection, fp32 parameters and reverse sweep);
+      "float64": 2, the closure in float64 -- the body-only needed-rows path, and only with float_dtype: float64.  An engine-level
+      option of FrameBatch (closure / last_grad): the device optimiser is fp32, so the driver and main never select it.
+    Raises ValueError naming the setting the float64 mode does not support (what sfx_batch_create would refuse)."""
+    precision = str(precision or "mixed")
+    if precision not in PRECISIONS:
+        raise ValueError("precision must be one of %s, got %r" % (", ".join(PRECISIONS), precision))
+    float64 = str(cfg.get("float_dtype", "float32")) == "float64"
+    if precision == "mixed":
+        return int(float64 or bool(cfg.get("high_precision", False)))
+    unsupported = [("float_dtype: %s (precision: float64 needs float_dtype: float64)" % cfg.get("float_dtype", "float32"), not float64),
+                   ("lbs_mode=%r (needs 'rows')" % lbs_mode, lbs_mode != "rows"),
+                   ("use_vposer", bool(cfg.get("use_vposer", True))),
+                   ("use_hands", bool(cfg.get("use_hands", True))),
+                   ("use_face", bool(cfg.get("use_face", True))),
+                   ("interpenetration", bool(cfg.get("interpenetration", False))),
+                   ("the GMM body pose prior (no regression pose)", not has_regression_pose and not cfg.get("use_vposer", True))]
+    bad = [name for name, hit in unsupported if hit]
+    if bad:
+        raise ValueError("precision: float64 does not support %s" % "; ".join(bad))
+    return 2
+
+
+def widen_stage_weights(stages):
+    """capi.StageWeights -> capi.StageWeights64 (the float values widened)."""
+    out = []
+    for w in stages:
+        d = capi.StageWeights64()
+        for name, _ in capi.StageWeights._fields_:
+            if name == "jaw_prior_weight":
+                for q in range(3):
+                    d.jaw_prior_weight[q] = w.jaw_prior_weight[q]
+            else:
+                setattr(d, name, getattr(w, name))
+        out.append(d)
+    return out
+
+
 class FrameBatch(object):
     """B frames under one configuration (sfx_batch)."""
 
     def __init__(self, model, B, cfg, lbs_mode="dense", reuse_entry_eval=True, has_regression_pose=True,
-                 stages=None, num_body_joints=None, side_view=False, slots=0):
+                 stages=None, num_body_joints=None, side_view=False, slots=0, precision="mixed"):
         """`cfg` uses the reference's key names (cmd_parser).  `stages` (list of
         capi.StageWeights) overrides the schedule derived from cfg; `num_body_joints` overrides
         where the per-stage hand/face joint weights start (K = never: weights passed verbatim).
         `slots` (dense mode): GEMM columns when B is larger -- the other frames queue and are admitted as
-        columns free up (continuous batching); 0 = one column per frame."""
+        columns free up (continuous batching); 0 = one column per frame.
+        `precision`: "mixed" (default; cfg float_dtype picks the mode as always) or "float64", a float64 batch
+        (check_precision): every real number it takes and returns is float64, and it evaluates closures (closure / last_grad)
+        only -- fit, step, guess_init, stats and trace are fp32-only and refused."""
         self.model, self.B, self.cfg = model, int(B), dict(cfg)
         self._lib = model._lib
+        hp = check_precision(cfg, lbs_mode, has_regression_pose, precision)
+        self.float64 = hp == 2
+        stages64 = None
+        if self.float64:
+            stages64 = stage_weights_from_cfg(cfg, capi.StageWeights64)[0] if stages is None else widen_stage_weights(stages)
         if stages is None:
             stages, _ = stage_weights_from_cfg(cfg)
         self.n_stages = len(stages)
@@ -242,8 +294,9 @@ class FrameBatch(object):
         c.lbfgs_max_eval = int(cfg.get("lbfgs_max_eval", 0) or 0)
         c.lbfgs_history_size = int(cfg.get("lbfgs_history_size", 0) or 0)
         c.lbfgs_max_iter = int(cfg.get("lbfgs_max_iter", 0) or 0)
-        # cfg float_dtype: float64 (main.py:99-105) -> the engine's high-precision mode (include/sfx.h sfx_batch_cfg.high_precision)
-        c.high_precision = int(str(cfg.get("float_dtype", "float32")) == "float64" or bool(cfg.get("high_precision", False)))
+        # cfg float_dtype: float64 (main.py:99-105) -> the engine's high-precision mode (include/sfx.h sfx_batch_cfg.high_precision);
+        # precision="float64" -> mode 2
+        c.high_precision = hp
         if c.interpenetration and lbs_mode != "dense":
             raise ValueError("interpenetration=True needs lbs_mode='dense' (the term reads every vertex)")
         self.use_vposer = bool(c.use_vposer)
@@ -254,11 +307,28 @@ class FrameBatch(object):
         self._h = h
         self.K = model.K
         self._trace_cap = 0
+        if self.float64:
+            arr64 = (capi.StageWeights64 * max(1, self.n_stages))(*stages64)
+            capi.check(self._lib.sfx_batch_set_stage_weights_f64(self._h, arr64))
 
     # ---- data ------------------------------------------------------------------------------
     def set_frames(self, keypoints, joint_weights, cam_init_mask, focal, center, data_weight, est_tz=None,
                    cam_rot=None):
         B, K = self.B, self.K
+        if self.float64:        # keypoints, weights, masks, rotation widened from fp32; the camera in double
+            kp = capi.f64(capi.f32(keypoints)).reshape(B, K, 3)
+            jw = capi.f64(np.broadcast_to(np.asarray(joint_weights, np.float32), (B, K)))
+            cm = capi.f64(np.broadcast_to(np.asarray(cam_init_mask, np.float32), (B, K)))
+            cam = np.zeros((B, 6), np.float64)
+            cam[:, 0] = cam[:, 1] = np.asarray(focal, np.float64)
+            cam[:, 2:4] = np.asarray(center, np.float64).reshape(-1, 2)
+            cam[:, 4] = np.asarray(data_weight, np.float64)
+            if est_tz is not None:
+                cam[:, 5] = np.asarray(est_tz, np.float64)
+            R = np.tile(np.eye(3).reshape(1, 9), (B, 1)) if cam_rot is None else capi.f64(capi.f32(cam_rot)).reshape(B, 9)
+            capi.check(self._lib.sfx_batch_set_frames_f64(self._h, capi.dptr(kp), capi.dptr(jw), capi.dptr(cm),
+                                                          capi.dptr(cam), capi.dptr(capi.f64(R))))
+            return
         kp = capi.f32(keypoints).reshape(B, K, 3)
         jw = capi.f32(np.broadcast_to(np.asarray(joint_weights, np.float32), (B, K)))
         cm = capi.f32(np.broadcast_to(np.asarray(cam_init_mask, np.float32), (B, K)))
@@ -279,6 +349,13 @@ class FrameBatch(object):
                      left_hand_pose=self.model.num_pca, right_hand_pose=self.model.num_pca,
                      expression=self.model.num_expr, jaw_pose=3, leye_pose=3, reye_pose=3,
                      pose_embedding=self.nemb)
+        if self.float64:
+            args = [None if p.get(n) is None else capi.f64(np.broadcast_to(np.asarray(p[n], np.float64).reshape(-1, sizes[n]),
+                                                                          (B, sizes[n]))) for n in PARAM_NAMES]
+            reg = None if regression_pose is None else capi.f64(capi.f32(
+                np.broadcast_to(np.asarray(regression_pose, np.float32).reshape(-1, self.nemb), (B, self.nemb))))
+            capi.check(self._lib.sfx_batch_set_params_f64(self._h, *[capi.dptr(a) for a in args], capi.dptr(reg)))
+            return
         args = []
         for n in PARAM_NAMES:
             v = p.get(n)
@@ -292,6 +369,10 @@ class FrameBatch(object):
         B = self.B
         sizes = [3, 3, self.model.num_betas, self.model.num_pca, self.model.num_pca, self.model.num_expr,
                  3, 3, 3, self.nemb, 63]
+        if self.float64:
+            outs = [np.zeros((B, n), np.float64) for n in sizes]
+            capi.check(self._lib.sfx_batch_get_params_f64(self._h, *[capi.dptr(a) for a in outs]))
+            return dict(zip(PARAM_NAMES + ("body_pose",), outs))
         outs = [np.zeros((B, n), np.float32) for n in sizes]
         capi.check(self._lib.sfx_batch_get_params(self._h, *[capi.fptr(a) for a in outs]))
         d = dict(zip(PARAM_NAMES + ("body_pose",), outs))
@@ -302,8 +383,13 @@ class FrameBatch(object):
         return self._lib.sfx_batch_num_vars(self._h, stage)
 
     def closure(self, stage):
-        """(loss[B], grad[B,N]) at the current parameters; stage -1 = camera-init loss."""
+        """(loss[B], grad[B,N]) at the current parameters; stage -1 = camera-init loss.  float64 on a float64 batch."""
         N = self.num_vars(stage)
+        if self.float64:
+            loss = np.zeros(self.B, np.float64)
+            grad = np.zeros((self.B, N), np.float64)
+            capi.check(self._lib.sfx_batch_closure_f64(self._h, stage, capi.dptr(loss), capi.dptr(grad), None))
+            return loss, grad
         loss = np.zeros(self.B, np.float32)
         grad = np.zeros((self.B, N), np.float32)
         capi.check(self._lib.sfx_batch_closure(self._h, stage, capi.fptr(loss), capi.fptr(grad), None))
@@ -376,7 +462,11 @@ class FrameBatch(object):
         return int(self._lib.sfx_batch_pen_launches(self._h))
 
     def last_grad(self, stage):
-        """Gradient [B,N] of the most recent closure evaluation (what var.grad holds after step())."""
+        """Gradient [B,N] of the most recent closure evaluation (what var.grad holds after step()); float64 on a float64 batch."""
+        if self.float64:
+            grad = np.zeros((self.B, self.num_vars(stage)), np.float64)
+            capi.check(self._lib.sfx_batch_get_grad_f64(self._h, stage, capi.dptr(grad)))
+            return grad
         grad = np.zeros((self.B, self.num_vars(stage)), np.float32)
         capi.check(self._lib.sfx_batch_get_grad(self._h, stage, capi.fptr(grad)))
         return grad
