@@ -54,6 +54,8 @@ typedef struct sfx_model_desc {
 } sfx_model_desc;
 
 int  sfx_model_create(const sfx_model_desc* desc, sfx_model** out);
+/* Releases the model's constants, the batch behind sfx_lbs_forward and the ONE collision handle the model retains (see
+ * sfx_batch_destroy).  Destroy the model's batches first.                                */
 void sfx_model_destroy(sfx_model* m);
 
 /* VPoser-v1 decoder weights (human_body_prior cvpr19; reference call sites
@@ -171,6 +173,9 @@ typedef struct sfx_batch_cfg {
 
 int  sfx_batch_create(sfx_model* m, const sfx_batch_cfg* cfg,
                       const sfx_stage_weights* stages /* [n_stages] */, sfx_batch** out);
+/* Releases everything the batch owns, EXCEPT the collision buffers of a batch with interpenetration = 1 (about 45 MB per GEMM
+ * column: 11.5 GB at 256): they go back to the model, which retains one such handle (the largest returned) for its next batch
+ * until sfx_model_set_parts or sfx_model_destroy.  No other entry point releases that memory.                          */
 void sfx_batch_destroy(sfx_batch* b);
 
 /* Per-frame inputs (HOST pointers, copied):

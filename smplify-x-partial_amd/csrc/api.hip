@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -96,28 +97,6 @@ extern "C" int sfx_prof_get(const char* name, double* total_ms, int64_t* launche
 }
 
 // ---------------------------------------------------------------------------------------
-struct DevAlloc {
-    std::vector<void*> ptrs;
-    bool failed = false;        // sticky: any hipMalloc / hipMemcpy / hipMemset of this owner failed (checked once by the creator)
-    template <typename T> T* up(const std::vector<T>& h) {
-        T* d = nullptr;
-        size_t n = std::max<size_t>(h.size(), 1) * sizeof(T);
-        if (hipMalloc((void**)&d, n) != hipSuccess) { failed = true; return nullptr; }
-        ptrs.push_back(d);
-        if (!h.empty() && hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) failed = true;
-        return d;
-    }
-    template <typename T> T* zeros(size_t count) {
-        T* d = nullptr;
-        size_t n = std::max<size_t>(count, 1) * sizeof(T);
-        if (hipMalloc((void**)&d, n) != hipSuccess) { failed = true; return nullptr; }
-        ptrs.push_back(d);
-        if (hipMemset(d, 0, n) != hipSuccess) failed = true;
-        return d;
-    }
-    void free_all() { for (void* p : ptrs) hipFree(p); ptrs.clear(); }
-};
-
 struct sfx_pen;
 extern "C" int sfx_pen_create(int32_t V, int32_t F, const int32_t* faces, const int32_t* segm, const int32_t* parents,
                               const int32_t* ign_pairs, int32_t n_ign, int32_t max_collisions, int32_t max_batch,
@@ -136,6 +115,10 @@ int sfx_pen_stats_from(const int* stats_dev, int n, int32_t* stats_host);
 int sfx_pen_stats_stride(void);
 const int* sfx_pen_stats_dev(const sfx_pen* h);
 
+extern "C" void sfx_batch_destroy(sfx_batch* b);
+// Who owns what: a model owns its constants (mem), the batch behind sfx_lbs_forward and the idle collision handle; a batch owns
+// its state (mem), its trace, pinned poll buffers, events, capture stream, graphs, and the collision handle while it lives.  Each
+// handle releases all of it in its destructor and nowhere else: sfx_*_destroy and every failing exit of sfx_*_create end there.
 struct sfx_model {
     DevModel M{};
     DevAlloc mem;
@@ -153,6 +136,7 @@ struct sfx_model {
     int pen_idle_cols = 0, pen_idle_cap = 0, pen_idle_gen = -1;
     int parts_gen = 0;            // bumped by sfx_model_set_parts: handles made for another part table are not reused
     std::mutex pen_mu;
+    ~sfx_model() { sfx_batch_destroy(fwd); sfx_pen_destroy(pen_idle); }
 };
 
 // The fused dense loop keeps `ahead` batches of 8 rounds queued beyond the one whose stage flags the host is waiting for: the
@@ -193,6 +177,23 @@ struct sfx_batch {
     bool pen_chunked = false;     // the most recent evaluation was chunked: sfx_batch_pen_stats reads pen_stats_all
     bool f64 = false;             // float64 mode (high_precision = 2): X, Xt, f, g hold doubles, closures run k_closure64
     StageW64* sw64_dev = nullptr; // [n_stages] its stage weights
+    DevAlloc trace_mem;           // D.trace / D.trace_n (sfx_batch_trace)
+    long long* dbg_buf = nullptr; // [64] clock buffer of the lab build (sfx_debug_clocks attaches it as D.dbg), owned by mem
+    ~sfx_batch() {
+        for (auto& kv : pen_graphs) hipGraphExecDestroy(kv.second);
+        if (cap_stream) hipStreamDestroy(cap_stream);
+        if (pen) {             // the collision buffers go back to the model's idle slot (see sfx_model)
+            (void)hipDeviceSynchronize();
+            std::lock_guard<std::mutex> lk(m->pen_mu);
+            if (pen_gen == m->parts_gen && (!m->pen_idle || m->pen_idle_cols <= pen_cols)) {
+                sfx_pen_destroy(m->pen_idle);
+                m->pen_idle = pen; m->pen_idle_cols = pen_cols; m->pen_idle_cap = pen_cap; m->pen_idle_gen = pen_gen;
+            } else sfx_pen_destroy(pen);
+        }
+        if (stage_host) hipHostFree(stage_host);
+        if (map_host) hipHostFree(map_host);
+        for (hipEvent_t e : poll_ev) if (e) hipEventDestroy(e);
+    }
 };
 
 // The float64 mode's guards.  Float inputs to a float64 batch are widened; float OUTPUTS are refused, so that no result is
@@ -223,7 +224,7 @@ extern "C" int sfx_model_create(const sfx_model_desc* d, sfx_model** out) {
     if (hipGetDeviceCount(&dev_count) != hipSuccess || dev_count == 0) {
         sfx_set_error("no HIP device: libsfx has no CPU fallback"); return -3;
     }
-    sfx_model* m = new sfx_model();
+    std::unique_ptr<sfx_model> m(new sfx_model());      // (every refusal below releases it, uploads included)
     DevModel& M = m->M;
     m->NB = d->num_betas; m->NE = d->num_expr; m->NPCA = d->num_pca;
     M.V = V; M.F = d->F; M.S = S; M.P = P; M.KD = KD; M.K = d->K;
@@ -335,10 +336,10 @@ extern "C" int sfx_model_create(const sfx_model_desc* d, sfx_model** out) {
         par[0] = -1;
         int maxd = 0;
         for (int j = 1; j < SFX_J; ++j) {
-            if (par[j] < 0 || par[j] >= j) { sfx_set_error("parents must be topologically ordered"); delete m; return -1; }
+            if (par[j] < 0 || par[j] >= j) { sfx_set_error("parents must be topologically ordered"); return -1; }
             depth[j] = depth[par[j]] + 1; maxd = std::max(maxd, depth[j]);
         }
-        if (maxd + 1 > SFX_MAX_LEVELS) { sfx_set_error("tree too deep"); delete m; return -1; }
+        if (maxd + 1 > SFX_MAX_LEVELS) { sfx_set_error("tree too deep"); return -1; }
         M.n_levels = maxd + 1;
         std::vector<int> lj;
         for (int l = 0; l <= maxd; ++l) {
@@ -372,7 +373,7 @@ extern "C" int sfx_model_create(const sfx_model_desc* d, sfx_model** out) {
         {
             int rounds = 0;
             while ((1 << rounds) < M.n_levels) ++rounds;
-            if (rounds > SFX_MAX_ROUNDS) { sfx_set_error("tree too deep"); delete m; return -1; }
+            if (rounds > SFX_MAX_ROUNDS) { sfx_set_error("tree too deep"); return -1; }
             M.n_rounds = rounds;
             std::vector<int> anc(par);
             for (int k = 0; k < rounds; ++k) {
@@ -411,7 +412,7 @@ extern "C" int sfx_model_create(const sfx_model_desc* d, sfx_model** out) {
         const int e0 = SFX_J, l0 = e0 + d->n_extra, d0 = l0 + d->n_lmk, end = d0 + d->n_dyn;
         for (int k = 0; k < K; ++k) {
             const int s = d->joint_map[k];
-            if (s < 0 || s >= end) { sfx_set_error("joint_map[%d]=%d out of range [0,%d)", k, s, end); delete m; return -1; }
+            if (s < 0 || s >= end) { sfx_set_error("joint_map[%d]=%d out of range [0,%d)", k, s, end); return -1; }
             if (s < e0) { jt[k] = 0; js[k] = s; readers[s].push_back(k); continue; }
             jt[k] = 1; ji0[k] = (int)ivid.size();
             if (s < l0) { ivid.push_back(d->extra_vertex_ids[s - e0]); iw.push_back(1.f); idyn.push_back(-1); ik.push_back(k); jn[k] = 1; }
@@ -426,7 +427,7 @@ extern "C" int sfx_model_create(const sfx_model_desc* d, sfx_model** out) {
                 jn[k] = 3;
             }
         }
-        if ((int)ivid.size() > SFX_MAX_ITEMS) { sfx_set_error("too many vertex items"); delete m; return -1; }
+        if ((int)ivid.size() > SFX_MAX_ITEMS) { sfx_set_error("too many vertex items"); return -1; }
         M.n_items = (int)ivid.size();
         std::vector<int> sk0(SFX_J + 1, 0), skl;
         for (int s = 0; s < SFX_J; ++s) { sk0[s] = (int)skl.size(); for (int k : readers[s]) skl.push_back(k); }
@@ -474,7 +475,7 @@ extern "C" int sfx_model_create(const sfx_model_desc* d, sfx_model** out) {
             // the same per LUT row in fixed-size blocks, together with the row's vertices, barycentric weights, template
             // rows and sparse skinning weights (closure_body fetches one block asynchronously)
             const int nd = (int)dynitems.size(), rows = nd ? d->n_dyn_rows : 0;
-            if (nd > SFX_MAX_DYN) { sfx_set_error("too many dynamic-contour items (%d > %d)", nd, SFX_MAX_DYN); delete m; return -1; }
+            if (nd > SFX_MAX_DYN) { sfx_set_error("too many dynamic-contour items (%d > %d)", nd, SFX_MAX_DYN); return -1; }
             std::vector<int> pv((size_t)rows * nd), pwj((size_t)rows * nd * SFX_NW, 0), pjs((size_t)rows * (SFX_J + 1), 0), pji((size_t)rows * nd * SFX_NW, 0);
             std::vector<float> pw((size_t)rows * nd), pvt((size_t)rows * nd * 3), pww((size_t)rows * nd * SFX_NW, 0.f), pjw((size_t)rows * nd * SFX_NW, 0.f);
             for (int row = 0; row < rows; ++row) {
@@ -539,7 +540,7 @@ extern "C" int sfx_model_create(const sfx_model_desc* d, sfx_model** out) {
                 uslot[i] = vslot[ivid[i]];
             }
             for (size_t i = 0; i + 1 < ivid.size(); ++i)
-                if (idyn[i] >= 0 && idyn[i + 1] < 0) { sfx_set_error("internal: dynamic items must trail the static ones"); delete m; return -1; }
+                if (idyn[i] >= 0 && idyn[i + 1] < 0) { sfx_set_error("internal: dynamic items must trail the static ones"); return -1; }
             std::vector<int> pus(dyn_pv.size(), -1);
             for (size_t o = 0; o < dyn_pv.size(); ++o) {
                 const int v = dyn_pv[o];
@@ -552,22 +553,15 @@ extern "C" int sfx_model_create(const sfx_model_desc* d, sfx_model** out) {
         }
         M.src_k0 = m->mem.up(sk0); M.src_klist = m->mem.up(skl);
     }
-    if (m->meta_host.size() != SFX_META_N) { sfx_set_error("internal: meta table"); delete m; return -1; }
+    if (m->meta_host.size() != SFX_META_N) { sfx_set_error("internal: meta table"); return -1; }
     M.meta = m->mem.up(m->meta_host);
-    if (m->mem.failed) { (void)hipGetLastError(); sfx_set_error("out of device memory (model constants)"); m->mem.free_all(); delete m; return -2; }
-    if (hipDeviceSynchronize() != hipSuccess) { sfx_set_error("model upload failed"); m->mem.free_all(); delete m; return -2; }
-    *out = m;
+    if (m->mem.failed) { (void)hipGetLastError(); sfx_set_error("out of device memory (model constants)"); return -2; }
+    if (hipDeviceSynchronize() != hipSuccess) { sfx_set_error("model upload failed"); return -2; }
+    *out = m.release();
     return 0;
 }
 
-extern "C" void sfx_batch_destroy(sfx_batch* b);
-extern "C" void sfx_model_destroy(sfx_model* m) {
-    if (!m) return;
-    if (m->fwd) sfx_batch_destroy(m->fwd);
-    if (m->pen_idle) sfx_pen_destroy(m->pen_idle);
-    m->mem.free_all();
-    delete m;
-}
+extern "C" void sfx_model_destroy(sfx_model* m) { delete m; }
 
 extern "C" int sfx_model_set_parts(sfx_model* m, const int32_t* segm, const int32_t* parents, const int32_t* ign_pairs,
                                    int32_t n_ign) {
@@ -624,6 +618,25 @@ static void add_group(VarList& v, int off, int len, int has) {
     for (int i = 0; i < len; ++i, ++v.n) if (v.n < SFX_NVAR_MAX) v.idx[v.n] = (short)(off + i);     // (n > NVAR_MAX: rejected by the caller)
 }
 
+// One entry of opt_weights as the kernels read it: a StageW from float weights, a StageW64 from float (widened) or double ones.
+// fit_single_frame.py:567-568: the bending weight, unless given, is a multiple of body_pose_weight, and the product is formed in
+// the destination's type from the source's values -- fp32 in the reference's float run, double in its float64 run.
+template <class W, class S>
+static std::vector<W> stage_weights(const S* st, int n, bool coll) {
+    using T = decltype(W::bpw);
+    std::vector<W> out(std::max(1, n));
+    for (int i = 0; i < n; ++i) {
+        W& w = out[i];
+        w.bpw = st[i].body_pose_weight; w.sw = st[i].shape_weight;
+        w.bend = st[i].bending_prior_weight >= 0 ? (T)st[i].bending_prior_weight : (T)3.17 * (T)st[i].body_pose_weight;
+        w.hpw = st[i].hand_prior_weight; w.epw = st[i].expr_prior_weight;
+        for (int q = 0; q < 3; ++q) w.jaw[q] = st[i].jaw_prior_weight[q];
+        w.hand_jw = st[i].hand_joint_weight; w.face_jw = st[i].face_joint_weight;
+        w.coll = coll ? (T)st[i].coll_loss_weight : (T)0;       // (fitting.py:437; no interpenetration term in float64 mode)
+    }
+    return out;
+}
+
 extern "C" int sfx_batch_create(sfx_model* m, const sfx_batch_cfg* c, const sfx_stage_weights* st, sfx_batch** out) {
     if (!m || !c || !out) { sfx_set_error("null argument"); return -1; }
     if (c->n_stages < 0 || c->n_stages > SFX_MAX_STAGES) { sfx_set_error("n_stages=%d unsupported", c->n_stages); return -1; }
@@ -634,45 +647,17 @@ extern "C" int sfx_batch_create(sfx_model* m, const sfx_batch_cfg* c, const sfx_
                           m->M.n_items > SFX_SMALL_ITEMS ? "a model whose keypoints need more than 32 vertex rows" : nullptr;
         if (why) { sfx_set_error("high_precision = 2 (float64) does not support %s", why); return -1; }
     }
-    sfx_batch* b = new sfx_batch();
-    b->m = m; b->K = m->M.K;
-    BatchDev& D = b->D;
     const int B = c->B, K = m->M.K;
-    D.cfg.B = B; D.cfg.n_stages = c->n_stages; D.cfg.use_vposer = c->use_vposer; D.cfg.use_hands = c->use_hands;
-    D.cfg.use_face = c->use_face; D.cfg.use_conf = c->use_joints_conf; D.cfg.has_reg = c->has_regression_pose;
-    D.cfg.use_conf_cam = c->use_conf_cam_init; D.cfg.nbj = c->num_body_joints; D.cfg.maxiters = c->maxiters;
-    D.cfg.lbfgs_max_iter = c->lbfgs_max_iter > 0 ? c->lbfgs_max_iter : c->maxiters;
-    D.cfg.max_eval = D.cfg.lbfgs_max_iter * 5 / 4; D.cfg.ftol = c->ftol; D.cfg.gtol = c->gtol;
-    D.cfg.lr = c->lr; D.cfg.rho = c->rho; D.cfg.depth_w = c->depth_loss_weight; D.cfg.lbs_mode = c->lbs_mode;
-    D.cfg.reuse = c->reuse_entry_eval;
-    D.cfg.side_thsh = c->side_view_thsh; D.cfg.lsh = c->left_shoulder_idx; D.cfg.rsh = c->right_shoulder_idx;
-    D.cfg.pen = c->interpenetration ? 1 : 0;
-    D.cfg.proj64 = c->high_precision ? 1 : 0;
-    b->f64 = c->high_precision == 2;
-    // negative = the reference's default; 0 is a legal value of lbfgs_ls.LBFGS (it disables the test) and reaches the device as 0
-    D.cfg.tol_grad = c->lbfgs_tolerance_grad >= 0 ? c->lbfgs_tolerance_grad : 1e-5;
-    D.cfg.tol_change = c->lbfgs_tolerance_change >= 0 ? c->lbfgs_tolerance_change : 1e-9;
-    if (c->lbfgs_max_eval > 0) D.cfg.max_eval = c->lbfgs_max_eval;
+    const bool pen_on = c->interpenetration != 0;
     // (round 5: a history_size beyond the default's 100 gets a ring of that many slots; the bound is the LDS array of the alphas)
-    if (c->lbfgs_history_size > SFX_HIST_MAX) { sfx_set_error("history_size %d > %d", c->lbfgs_history_size, SFX_HIST_MAX); delete b; return -1; }
-    D.cfg.hist_cap = c->lbfgs_history_size > 0 ? c->lbfgs_history_size : SFX_HIST;
-    D.cfg.hist_ring = std::max(D.cfg.hist_cap, SFX_HIST);
-    if (D.cfg.pen && c->lbs_mode != 1) {
-        sfx_set_error("interpenetration needs lbs_mode = 1 (the term reads every vertex)"); delete b; return -1; }
-    if (D.cfg.pen && !(c->df_cone_height > 0.f)) { sfx_set_error("df_cone_height must be positive"); delete b; return -1; }
+    if (c->lbfgs_history_size > SFX_HIST_MAX) { sfx_set_error("history_size %d > %d", c->lbfgs_history_size, SFX_HIST_MAX); return -1; }
+    if (pen_on && c->lbs_mode != 1) { sfx_set_error("interpenetration needs lbs_mode = 1 (the term reads every vertex)"); return -1; }
+    if (pen_on && !(c->df_cone_height > 0.f)) { sfx_set_error("df_cone_height must be positive"); return -1; }
     if (c->side_view_thsh > 0.f && (c->left_shoulder_idx < 0 || c->left_shoulder_idx >= K || c->right_shoulder_idx < 0 || c->right_shoulder_idx >= K)) {
-        sfx_set_error("shoulder indices out of range"); delete b; return -1; }
-    {   // keypoints (and their vertex items: ascending in keypoint order) that are live while the hand / face joint weights are zero
-        const int kl[3] = {std::min(K, c->num_body_joints), std::min(K, c->num_body_joints + 42), K};
-        for (int q = 0; q < 3; ++q) {
-            int n = 0;
-            for (int i = 0; i < m->M.n_items; ++i) if (m->meta_host[MO_IK + i] < kl[q]) ++n;
-            D.cfg.kl[q] = kl[q]; D.cfg.nil[q] = n;
-        }
-    }
-    build_layout(D.L, m->NB, m->NE, m->NPCA, c->use_vposer, m->M.vp_latent);
-    if (D.L.npar > SFX_NPAR_MAX) { sfx_set_error("parameter block too large"); delete b; return -1; }
-    const ParLayout& L = D.L;
+        sfx_set_error("shoulder indices out of range"); return -1; }
+    ParLayout L{};
+    build_layout(L, m->NB, m->NE, m->NPCA, c->use_vposer, m->M.vp_latent);
+    if (L.npar > SFX_NPAR_MAX) { sfx_set_error("parameter block too large"); return -1; }
     VarList cam{}, body{};
     add_group(cam, L.cam_t, 3, 1); add_group(cam, L.go, 3, 1);
     // order of smplx.SMPLX.parameters() then pose_embedding (fit_single_frame.py:554-559)
@@ -688,36 +673,44 @@ extern "C" int sfx_batch_create(sfx_model* m, const sfx_batch_cfg* c, const sfx_
     if (body.n > SFX_NVAR_MAX) {
         // e.g. all 45 hand components: more optimisation variables than the optimiser's vectors hold.  Such a batch can
         // still evaluate the forward (sfx_lbs_forward / sfx_batch_forward); n_stages = 0 declares that intent
-        if (c->n_stages > 0) { sfx_set_error("%d optimisation variables (limit %d): reduce num_pca_comps", body.n, SFX_NVAR_MAX); delete b; return -1; }
+        if (c->n_stages > 0) { sfx_set_error("%d optimisation variables (limit %d): reduce num_pca_comps", body.n, SFX_NVAR_MAX); return -1; }
         body.n = SFX_NVAR_MAX;
+    }
+    // every argument is accepted: from here on only the device can refuse, and ~sfx_batch releases whatever was acquired by then
+    std::unique_ptr<sfx_batch> b(new sfx_batch());
+    b->m = m; b->K = K;
+    BatchDev& D = b->D;
+    D.L = L;
+    D.cfg.B = B; D.cfg.n_stages = c->n_stages; D.cfg.use_vposer = c->use_vposer; D.cfg.use_hands = c->use_hands;
+    D.cfg.use_face = c->use_face; D.cfg.use_conf = c->use_joints_conf; D.cfg.has_reg = c->has_regression_pose;
+    D.cfg.use_conf_cam = c->use_conf_cam_init; D.cfg.nbj = c->num_body_joints; D.cfg.maxiters = c->maxiters;
+    D.cfg.lbfgs_max_iter = c->lbfgs_max_iter > 0 ? c->lbfgs_max_iter : c->maxiters;
+    D.cfg.max_eval = D.cfg.lbfgs_max_iter * 5 / 4; D.cfg.ftol = c->ftol; D.cfg.gtol = c->gtol;
+    D.cfg.lr = c->lr; D.cfg.rho = c->rho; D.cfg.depth_w = c->depth_loss_weight; D.cfg.lbs_mode = c->lbs_mode;
+    D.cfg.reuse = c->reuse_entry_eval;
+    D.cfg.side_thsh = c->side_view_thsh; D.cfg.lsh = c->left_shoulder_idx; D.cfg.rsh = c->right_shoulder_idx;
+    D.cfg.pen = pen_on ? 1 : 0;
+    D.cfg.proj64 = c->high_precision ? 1 : 0;
+    b->f64 = c->high_precision == 2;
+    // negative = the reference's default; 0 is a legal value of lbfgs_ls.LBFGS (it disables the test) and reaches the device as 0
+    D.cfg.tol_grad = c->lbfgs_tolerance_grad >= 0 ? c->lbfgs_tolerance_grad : 1e-5;
+    D.cfg.tol_change = c->lbfgs_tolerance_change >= 0 ? c->lbfgs_tolerance_change : 1e-9;
+    if (c->lbfgs_max_eval > 0) D.cfg.max_eval = c->lbfgs_max_eval;
+    D.cfg.hist_cap = c->lbfgs_history_size > 0 ? c->lbfgs_history_size : SFX_HIST;
+    D.cfg.hist_ring = std::max(D.cfg.hist_cap, SFX_HIST);
+    {   // keypoints (and their vertex items: ascending in keypoint order) that are live while the hand / face joint weights are zero
+        const int kl[3] = {std::min(K, c->num_body_joints), std::min(K, c->num_body_joints + 42), K};
+        for (int q = 0; q < 3; ++q) {
+            int n = 0;
+            for (int i = 0; i < m->M.n_items; ++i) if (m->meta_host[MO_IK + i] < kl[q]) ++n;
+            D.cfg.kl[q] = kl[q]; D.cfg.nil[q] = n;
+        }
     }
     b->vl_host[0] = cam; b->vl_host[1] = body;
     std::vector<VarList> vls = {cam, body};
     b->vl_dev = b->mem.up(vls);
-    std::vector<StageW> sws(std::max(1, c->n_stages));
-    for (int i = 0; i < c->n_stages; ++i) {
-        StageW& w = sws[i];
-        w.bpw = st[i].body_pose_weight; w.sw = st[i].shape_weight;
-        // fit_single_frame.py:567-568: bending = 3.17 * body_pose_weight (fp32 product) unless given
-        w.bend = (st[i].bending_prior_weight >= 0.f) ? st[i].bending_prior_weight : 3.17f * st[i].body_pose_weight;
-        w.hpw = st[i].hand_prior_weight; w.epw = st[i].expr_prior_weight;
-        for (int q = 0; q < 3; ++q) w.jaw[q] = st[i].jaw_prior_weight[q];
-        w.hand_jw = st[i].hand_joint_weight; w.face_jw = st[i].face_joint_weight;
-        w.coll = D.cfg.pen ? st[i].coll_loss_weight : 0.f;
-    }
-    b->sw_dev = b->mem.up(sws);
-    if (b->f64) {       // the float weights widened; the reference's float64 run forms 3.17 * body_pose_weight in double
-        std::vector<StageW64> w64(std::max(1, c->n_stages));
-        for (int i = 0; i < c->n_stages; ++i) {
-            StageW64& w = w64[i];
-            w.bpw = st[i].body_pose_weight; w.sw = st[i].shape_weight;
-            w.bend = (st[i].bending_prior_weight >= 0.f) ? (double)st[i].bending_prior_weight : 3.17 * (double)st[i].body_pose_weight;
-            w.hpw = st[i].hand_prior_weight; w.epw = st[i].expr_prior_weight;
-            for (int q = 0; q < 3; ++q) w.jaw[q] = st[i].jaw_prior_weight[q];
-            w.hand_jw = st[i].hand_joint_weight; w.face_jw = st[i].face_joint_weight; w.coll = 0.0;
-        }
-        b->sw64_dev = b->mem.up(w64);
-    }
+    b->sw_dev = b->mem.up(stage_weights<StageW>(st, c->n_stages, pen_on));
+    if (b->f64) b->sw64_dev = b->mem.up(stage_weights<StageW64>(st, c->n_stages, false));      // (the float weights widened)
     D.Bpad = ((B + 127) / 128) * 128;
     D.X = b->mem.zeros<float>((size_t)B * SFX_NPAR_MAX);
     D.Xt = b->mem.zeros<float>((size_t)B * SFX_NPAR_MAX);
@@ -763,7 +756,7 @@ extern "C" int sfx_batch_create(sfx_model* m, const sfx_batch_cfg* c, const sfx_
             int rc = sfx_pen_create(m->M.V, F, m->faces_host.data(), parts ? m->segm_host.data() : nullptr,
                                     parts ? m->parents_host.data() : nullptr, m->ign_host.empty() ? nullptr : m->ign_host.data(),
                                     (int)(m->ign_host.size() / 2), pen_cap, pen_cols, &b->pen);
-            if (rc) { b->mem.free_all(); delete b; return rc; }
+            if (rc) return rc;
             b->pen_cols = pen_cols;
         }
         b->pen_cap = pen_cap; b->pen_gen = m->parts_gen;
@@ -780,7 +773,6 @@ extern "C" int sfx_batch_create(sfx_model* m, const sfx_batch_cfg* c, const sfx_
         D.adj_part = b->mem.zeros<float>((size_t)sfx_adj_slices(m->M) * SFX_KD_PAD * D.Bpad);
         D.pen_dfeat = b->mem.zeros<float>((size_t)B * SFX_KD_PAD);
         D.pen_dA = b->mem.zeros<float>((size_t)B * SFX_J * 12);
-        if (!D.adj_G || !D.adj_part || !D.vposed) { sfx_set_error("out of device memory"); b->mem.free_all(); delete b; return -2; }
     }
     D.joints = b->mem.zeros<float>((size_t)B * K * 3);
     D.fullpose = b->mem.zeros<float>((size_t)B * SFX_POSE);
@@ -801,44 +793,18 @@ extern "C" int sfx_batch_create(sfx_model* m, const sfx_batch_cfg* c, const sfx_
     D.stage_loss2 = b->mem.zeros<float>((size_t)B * (1 + SFX_MAX_STAGES));
     D.try_both = b->mem.zeros<int>(B);
     D.orient_pass = b->mem.zeros<int>(B);
-    if (b->mem.failed || !D.hist || !D.verts) {
-        (void)hipGetLastError();
-        sfx_set_error("out of device memory (batch of %d frames)", B);
-        if (b->pen) sfx_pen_destroy(b->pen);
-        b->mem.free_all(); delete b; return -2; }
+    if (b->mem.failed) { (void)hipGetLastError(); sfx_set_error("out of device memory (batch of %d frames)", B); return -2; }
     if (hipHostMalloc((void**)&b->stage_host, (size_t)SFX_POLL_BUFS * B * sizeof(int)) != hipSuccess) b->stage_host = nullptr;      // poll buffers
     if (hipHostMalloc((void**)&b->map_host, (size_t)SFX_POLL_BUFS * 3 * B * sizeof(int)) != hipSuccess) b->map_host = nullptr;
     if (c->lbs_mode == 1 && (!b->stage_host || !b->map_host)) {       // the fused dense loop polls through pinned memory
-        sfx_set_error("out of pinned host memory"); sfx_batch_destroy(b); return -2; }
+        sfx_set_error("out of pinned host memory"); return -2; }
     for (int i = 0; i < SFX_POLL_BUFS; ++i)
-        if (hipEventCreateWithFlags(&b->poll_ev[i], hipEventDisableTiming) != hipSuccess) { sfx_set_error("event creation failed"); sfx_batch_destroy(b); return -2; }
-    *out = b;
+        if (hipEventCreateWithFlags(&b->poll_ev[i], hipEventDisableTiming) != hipSuccess) { sfx_set_error("event creation failed"); return -2; }
+    *out = b.release();
     return 0;
 }
 
-extern "C" void sfx_batch_destroy(sfx_batch* b) {
-    if (!b) return;
-    for (auto& kv : b->pen_graphs) hipGraphExecDestroy(kv.second);
-    b->pen_graphs.clear();
-    if (b->cap_stream) hipStreamDestroy(b->cap_stream);
-    if (b->pen) {          // the collision buffers go back to the model's idle slot (see sfx_model)
-        sfx_model* m = b->m;
-        (void)hipDeviceSynchronize();
-        std::lock_guard<std::mutex> lk(m->pen_mu);
-        if (b->pen_gen == m->parts_gen && (!m->pen_idle || m->pen_idle_cols <= b->pen_cols)) {
-            if (m->pen_idle) sfx_pen_destroy(m->pen_idle);
-            m->pen_idle = b->pen; m->pen_idle_cols = b->pen_cols; m->pen_idle_cap = b->pen_cap; m->pen_idle_gen = b->pen_gen;
-        } else sfx_pen_destroy(b->pen);
-        b->pen = nullptr;
-    }
-    if (b->D.trace) hipFree(b->D.trace);
-    if (b->D.trace_n) hipFree(b->D.trace_n);
-    b->mem.free_all();
-    if (b->stage_host) hipHostFree(b->stage_host);
-    if (b->map_host) hipHostFree(b->map_host);
-    for (int i = 0; i < SFX_POLL_BUFS; ++i) if (b->poll_ev[i]) hipEventDestroy(b->poll_ev[i]);
-    delete b;
-}
+extern "C" void sfx_batch_destroy(sfx_batch* b) { delete b; }
 
 // gt | conf | jw | cmask | cam | camR | regpose of frame b -> its packed record D.fd[b] (what the closure workgroup
 // loads in one 16-byte copy); launched after every host write to one of the seven arrays
@@ -888,25 +854,40 @@ static void put(std::vector<T>& X, int B, int off, int n, const S* src) {
     if (!src) return;
     for (int i = 0; i < B; ++i) for (int q = 0; q < n; ++q) X[(size_t)i * SFX_NPAR_MAX + off + q] = src[(size_t)i * n + q];
 }
-static void take(const std::vector<float>& X, int B, int off, int n, float* dst) {
+template <class T>
+static void take(const std::vector<T>& X, int B, int off, int n, T* dst) {
     if (!dst) return;
     for (int i = 0; i < B; ++i) for (int q = 0; q < n; ++q) dst[(size_t)i * n + q] = X[(size_t)i * SFX_NPAR_MAX + off + q];
 }
 
-// the parameter block of a float64 batch (doubles): sfx_batch_set_params widens float inputs into it
-template <class S>
-static int set_params64(sfx_batch* b, const S* cam_t, const S* go, const S* betas, const S* lh, const S* rh, const S* expr,
-                        const S* jaw, const S* leye, const S* reye, const S* emb) {
+// Host parameters into the parameter block of a batch, X / Xt (floats) or X64 / Xt64 (doubles: float inputs are widened); NULL = keep
+template <class T, class S>
+static int scatter_params(sfx_batch* b, T* X_dev, T* Xt_dev, const S* cam_t, const S* go, const S* betas, const S* lh, const S* rh,
+                          const S* expr, const S* jaw, const S* leye, const S* reye, const S* emb) {
     const int B = b->D.cfg.B; const ParLayout& L = b->D.L;
-    std::vector<double> X((size_t)B * SFX_NPAR_MAX);
-    SFX_CHECK(hipMemcpy(X.data(), b->D.X64, X.size() * 8, hipMemcpyDeviceToHost));
+    std::vector<T> X((size_t)B * SFX_NPAR_MAX);
+    SFX_CHECK(hipMemcpy(X.data(), X_dev, X.size() * sizeof(T), hipMemcpyDeviceToHost));
     put(X, B, L.cam_t, 3, cam_t); put(X, B, L.go, 3, go); put(X, B, L.betas, L.NB, betas);
     put(X, B, L.lh, L.NPCA, lh); put(X, B, L.rh, L.NPCA, rh); put(X, B, L.expr, L.NE, expr);
     put(X, B, L.jaw, 3, jaw); put(X, B, L.leye, 3, leye); put(X, B, L.reye, 3, reye);
     put(X, B, L.emb, L.NEMB, emb);
+    // body_model.reset_params(body_pose=pose_embedding) also fills the (dead) body_pose parameter
     if (L.has_bodyp && emb) put(X, B, L.bodyp, 63, emb);
-    SFX_CHECK(hipMemcpy(b->D.X64, X.data(), X.size() * 8, hipMemcpyHostToDevice));
-    SFX_CHECK(hipMemcpy(b->D.Xt64, X.data(), X.size() * 8, hipMemcpyHostToDevice));
+    SFX_CHECK(hipMemcpy(X_dev, X.data(), X.size() * sizeof(T), hipMemcpyHostToDevice));
+    SFX_CHECK(hipMemcpy(Xt_dev, X.data(), X.size() * sizeof(T), hipMemcpyHostToDevice));
+    return 0;
+}
+// ... and back.  emb63: the embedding read as the 63 body-pose values (batches without VPoser)
+template <class T>
+static int gather_params(sfx_batch* b, const T* X_dev, T* cam_t, T* go, T* betas, T* lh, T* rh, T* expr, T* jaw, T* leye, T* reye,
+                         T* emb, T* emb63) {
+    const int B = b->D.cfg.B; const ParLayout& L = b->D.L;
+    std::vector<T> X((size_t)B * SFX_NPAR_MAX);
+    SFX_CHECK(hipMemcpy(X.data(), X_dev, X.size() * sizeof(T), hipMemcpyDeviceToHost));
+    take(X, B, L.cam_t, 3, cam_t); take(X, B, L.go, 3, go); take(X, B, L.betas, L.NB, betas);
+    take(X, B, L.lh, L.NPCA, lh); take(X, B, L.rh, L.NPCA, rh); take(X, B, L.expr, L.NE, expr);
+    take(X, B, L.jaw, 3, jaw); take(X, B, L.leye, 3, leye); take(X, B, L.reye, 3, reye);
+    take(X, B, L.emb, L.NEMB, emb); take(X, B, L.emb, 63, emb63);
     return 0;
 }
 
@@ -915,20 +896,8 @@ extern "C" int sfx_batch_set_params(sfx_batch* b, const float* cam_t, const floa
                                     const float* leye, const float* reye, const float* emb, const float* reg) {
     if (!b) { sfx_set_error("null batch"); return -1; }
     const int B = b->D.cfg.B; const ParLayout& L = b->D.L;
-    if (b->f64) {       // float inputs to a float64 batch: widened
-        if (int rc = set_params64(b, cam_t, go, betas, lh, rh, expr, jaw, leye, reye, emb)) return rc;
-    } else {
-    std::vector<float> X((size_t)B * SFX_NPAR_MAX);
-    SFX_CHECK(hipMemcpy(X.data(), b->D.X, X.size() * 4, hipMemcpyDeviceToHost));
-    put(X, B, L.cam_t, 3, cam_t); put(X, B, L.go, 3, go); put(X, B, L.betas, L.NB, betas);
-    put(X, B, L.lh, L.NPCA, lh); put(X, B, L.rh, L.NPCA, rh); put(X, B, L.expr, L.NE, expr);
-    put(X, B, L.jaw, 3, jaw); put(X, B, L.leye, 3, leye); put(X, B, L.reye, 3, reye);
-    put(X, B, L.emb, L.NEMB, emb);
-    // body_model.reset_params(body_pose=pose_embedding) also fills the (dead) body_pose parameter
-    if (L.has_bodyp && emb) put(X, B, L.bodyp, 63, emb);
-    SFX_CHECK(hipMemcpy(b->D.X, X.data(), X.size() * 4, hipMemcpyHostToDevice));
-    SFX_CHECK(hipMemcpy(b->D.Xt, X.data(), X.size() * 4, hipMemcpyHostToDevice));
-    }
+    if (int rc = b->f64 ? scatter_params(b, b->D.X64, b->D.Xt64, cam_t, go, betas, lh, rh, expr, jaw, leye, reye, emb)
+                        : scatter_params(b, b->D.X, b->D.Xt, cam_t, go, betas, lh, rh, expr, jaw, leye, reye, emb)) return rc;
     if (reg) {
         std::vector<float> r((size_t)B * 63, 0.f);
         for (int i = 0; i < B; ++i) for (int q = 0; q < L.NEMB; ++q) r[(size_t)i * 63 + q] = reg[(size_t)i * L.NEMB + q];
@@ -943,21 +912,13 @@ extern "C" int sfx_batch_get_params(sfx_batch* b, float* cam_t, float* go, float
                                     float* expr, float* jaw, float* leye, float* reye, float* emb, float* body_pose) {
     if (!b) { sfx_set_error("null batch"); return -1; }
     if (refuse_f64(b, "sfx_batch_get_params")) return -1;
-    const int B = b->D.cfg.B; const ParLayout& L = b->D.L;
-    std::vector<float> X((size_t)B * SFX_NPAR_MAX);
-    SFX_CHECK(hipMemcpy(X.data(), b->D.X, X.size() * 4, hipMemcpyDeviceToHost));
-    take(X, B, L.cam_t, 3, cam_t); take(X, B, L.go, 3, go); take(X, B, L.betas, L.NB, betas);
-    take(X, B, L.lh, L.NPCA, lh); take(X, B, L.rh, L.NPCA, rh); take(X, B, L.expr, L.NE, expr);
-    take(X, B, L.jaw, 3, jaw); take(X, B, L.leye, 3, leye); take(X, B, L.reye, 3, reye);
-    take(X, B, L.emb, L.NEMB, emb);
-    if (body_pose) {
-        if (b->D.cfg.use_vposer) {      // decode the ACCEPTED latent (fit_single_frame.py:653-657)
-            ClosureArgs a{}; a.stage_override = 0; a.forward_only = 1; a.from_X = 1;
-            launch_closure(b->m->M, b->D, b->vl_dev, b->sw_dev, a, 0);
-            SFX_CHECK(hipDeviceSynchronize());
-            SFX_CHECK(hipMemcpy(body_pose, b->D.bodypose, (size_t)B * 63 * 4, hipMemcpyDeviceToHost));
-        }
-        else take(X, B, L.emb, 63, body_pose);
+    const bool decode = body_pose && b->D.cfg.use_vposer;
+    if (int rc = gather_params(b, b->D.X, cam_t, go, betas, lh, rh, expr, jaw, leye, reye, emb, decode ? nullptr : body_pose)) return rc;
+    if (decode) {       // the ACCEPTED latent decoded (fit_single_frame.py:653-657)
+        ClosureArgs a{}; a.stage_override = 0; a.forward_only = 1; a.from_X = 1;
+        launch_closure(b->m->M, b->D, b->vl_dev, b->sw_dev, a, 0);
+        SFX_CHECK(hipDeviceSynchronize());
+        SFX_CHECK(hipMemcpy(body_pose, b->D.bodypose, (size_t)b->D.cfg.B * 63 * 4, hipMemcpyDeviceToHost));
     }
     return 0;
 }
@@ -967,15 +928,7 @@ extern "C" int sfx_batch_set_stage_weights_f64(sfx_batch* b, const sfx_stage_wei
     if (need_f64(b, "sfx_batch_set_stage_weights_f64")) return -1;
     if (!st) { sfx_set_error("null argument"); return -1; }
     const int n = b->D.cfg.n_stages;
-    std::vector<StageW64> w64(std::max(1, n));
-    for (int i = 0; i < n; ++i) {
-        StageW64& w = w64[i];
-        w.bpw = st[i].body_pose_weight; w.sw = st[i].shape_weight;
-        w.bend = (st[i].bending_prior_weight >= 0.0) ? st[i].bending_prior_weight : 3.17 * st[i].body_pose_weight;
-        w.hpw = st[i].hand_prior_weight; w.epw = st[i].expr_prior_weight;
-        for (int q = 0; q < 3; ++q) w.jaw[q] = st[i].jaw_prior_weight[q];
-        w.hand_jw = st[i].hand_joint_weight; w.face_jw = st[i].face_joint_weight; w.coll = 0.0;
-    }
+    const std::vector<StageW64> w64 = stage_weights<StageW64>(st, n, false);
     SFX_CHECK(hipMemcpy(b->sw64_dev, w64.data(), (size_t)n * sizeof(StageW64), hipMemcpyHostToDevice));
     return 0;
 }
@@ -1013,7 +966,7 @@ extern "C" int sfx_batch_set_params_f64(sfx_batch* b, const double* cam_t, const
     const int B = b->D.cfg.B, nemb = b->D.L.NEMB;
     if (reg && !fp32_exact(reg, (size_t)B * nemb)) {
         sfx_set_error("sfx_batch_set_params_f64: the regression pose is kept in fp32 and must hold fp32 values"); return -1; }
-    if (int rc = set_params64(b, cam_t, go, betas, lh, rh, expr, jaw, leye, reye, emb)) return rc;
+    if (int rc = scatter_params(b, b->D.X64, b->D.Xt64, cam_t, go, betas, lh, rh, expr, jaw, leye, reye, emb)) return rc;
     if (reg) {
         std::vector<float> r(reg, reg + (size_t)B * nemb);
         return sfx_batch_set_params(b, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, r.data());
@@ -1024,34 +977,27 @@ extern "C" int sfx_batch_set_params_f64(sfx_batch* b, const double* cam_t, const
 extern "C" int sfx_batch_get_params_f64(sfx_batch* b, double* cam_t, double* go, double* betas, double* lh, double* rh,
                                         double* expr, double* jaw, double* leye, double* reye, double* emb, double* body_pose) {
     if (need_f64(b, "sfx_batch_get_params_f64")) return -1;
-    const int B = b->D.cfg.B; const ParLayout& L = b->D.L;
-    std::vector<double> X((size_t)B * SFX_NPAR_MAX);
-    SFX_CHECK(hipMemcpy(X.data(), b->D.X64, X.size() * 8, hipMemcpyDeviceToHost));
-    auto tk = [&](int off, int n, double* dst) {
-        if (dst) for (int i = 0; i < B; ++i) for (int q = 0; q < n; ++q) dst[(size_t)i * n + q] = X[(size_t)i * SFX_NPAR_MAX + off + q]; };
-    tk(L.cam_t, 3, cam_t); tk(L.go, 3, go); tk(L.betas, L.NB, betas); tk(L.lh, L.NPCA, lh); tk(L.rh, L.NPCA, rh);
-    tk(L.expr, L.NE, expr); tk(L.jaw, 3, jaw); tk(L.leye, 3, leye); tk(L.reye, 3, reye); tk(L.emb, L.NEMB, emb);
-    tk(L.emb, 63, body_pose);        // (no VPoser in this mode: body_pose is the embedding)
-    return 0;
+    // (no VPoser in this mode: body_pose is the embedding)
+    return gather_params(b, b->D.X64, cam_t, go, betas, lh, rh, expr, jaw, leye, reye, emb, body_pose);
 }
 
 #ifdef SFX_LAB       // include/sfx_lab.h
 extern "C" int sfx_debug_phase_clocks(sfx_batch* b, int32_t stage, int64_t* out /* [32] */) {
     if (!b) { sfx_set_error("null batch"); return -1; }
     if (refuse_f64(b, "sfx_debug_phase_clocks")) return -1;
-    long long* d = nullptr;
-    SFX_CHECK(hipMalloc((void**)&d, 64 * sizeof(long long)));
-    SFX_CHECK(hipMemset(d, 0, 64 * sizeof(long long)));
+    DevAlloc scratch;
+    long long* d = scratch.zeros<long long>(64);
+    if (scratch.failed) { (void)hipGetLastError(); sfx_set_error("out of device memory"); return -2; }
     { const long long freeze = 1 << 30; SFX_CHECK(hipMemcpy(d + 61, &freeze, sizeof(freeze), hipMemcpyHostToDevice)); }
     b->D.dbg = d;
     ClosureArgs a{}; a.stage_override = stage; a.from_X = 1;
     launch_closure(b->m->M, b->D, b->vl_dev, b->sw_dev, a, 0);
     launch_closure(b->m->M, b->D, b->vl_dev, b->sw_dev, a, 0);      // second launch: warm caches
-    SFX_CHECK(hipDeviceSynchronize());
-    b->D.dbg = nullptr;
+    const hipError_t es = hipDeviceSynchronize();
+    b->D.dbg = nullptr;         // (detached on every way out: the buffer goes with this call)
+    SFX_CHECK(es);
     long long h[64];
     SFX_CHECK(hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost));
-    hipFree(d);
     for (int i = 0; i < 32; ++i) out[i] = h[i];
     return 0;
 }
@@ -1115,7 +1061,8 @@ extern "C" int sfx_debug_lbs_dense_form(int32_t form) {
 extern "C" int sfx_debug_clocks(sfx_batch* b, int32_t enable, int64_t* out /* [64] or NULL */) {
     if (!b) { sfx_set_error("null batch"); return -1; }
     if (enable) {
-        if (!b->D.dbg) SFX_CHECK(hipMalloc((void**)&b->D.dbg, 64 * sizeof(long long)));
+        if (!b->dbg_buf && !(b->dbg_buf = b->mem.alloc<long long>(64))) { (void)hipGetLastError(); sfx_set_error("out of device memory"); return -2; }
+        b->D.dbg = b->dbg_buf;
         SFX_CHECK(hipMemset(b->D.dbg, 0, 64 * sizeof(long long)));
         const long long freeze = enable > 1 ? enable : 40;      // k_tick_dense: stamps freeze after this launch
         SFX_CHECK(hipMemcpy(b->D.dbg + 61, &freeze, sizeof(freeze), hipMemcpyHostToDevice));
@@ -1125,7 +1072,7 @@ extern "C" int sfx_debug_clocks(sfx_batch* b, int32_t enable, int64_t* out /* [6
     SFX_CHECK(hipDeviceSynchronize());
     long long h[64];
     SFX_CHECK(hipMemcpy(h, b->D.dbg, sizeof(h), hipMemcpyDeviceToHost));
-    hipFree(b->D.dbg); b->D.dbg = nullptr;
+    b->D.dbg = nullptr;         // (the buffer stays with the batch for the next attach)
     if (out) for (int i = 0; i < 64; ++i) out[i] = h[i];
     return 0;
 }
@@ -1314,15 +1261,15 @@ extern "C" int sfx_batch_guess_init(sfx_batch* b, const int32_t* pairs, int32_t 
     if (refuse_f64(b, "sfx_batch_guess_init")) return -1;
     hipStream_t s = (hipStream_t)stream;
     std::vector<int> pv(pairs, pairs + 2 * n_pairs);
-    int* pd = nullptr;
-    SFX_CHECK(hipMalloc((void**)&pd, pv.size() * sizeof(int)));
+    DevAlloc scratch;
+    int* pd = scratch.alloc<int>(pv.size());
+    if (!pd) { (void)hipGetLastError(); sfx_set_error("out of device memory"); return -2; }
     SFX_CHECK(hipMemcpyAsync(pd, pv.data(), pv.size() * sizeof(int), hipMemcpyHostToDevice, s));
     ClosureArgs a{}; a.stage_override = -1; a.forward_only = 1; a.from_X = 1;
     launch_closure(b->m->M, b->D, b->vl_dev, b->sw_dev, a, s);
     hipLaunchKernelGGL(k_guess_init, dim3((b->D.cfg.B + 63) / 64), dim3(64), 0, s, b->D, b->K, pd, n_pairs);
     pack_fd(b, s);          // (est_tz changed)
     SFX_CHECK(hipStreamSynchronize(s));
-    hipFree(pd);
     SFX_CHECK(hipGetLastError());
     return 0;
 }
@@ -1667,21 +1614,14 @@ extern "C" int sfx_batch_trace(sfx_batch* b, int32_t capacity) {
     D.trace_evals = capacity < 0 ? 1 : 0;          // negative capacity: also one record per closure evaluation (debug)
     if (capacity < 0) capacity = -capacity;
     SFX_CHECK(hipDeviceSynchronize());
-    if (D.trace) { hipFree(D.trace); D.trace = nullptr; }
-    if (D.trace_n) { hipFree(D.trace_n); D.trace_n = nullptr; }
-    D.trace_cap = 0;
+    b->trace_mem.clear(); D.trace = nullptr; D.trace_n = nullptr; D.trace_cap = 0;
     if (capacity == 0) return 0;
     // both buffers or neither: the kernels test D.trace alone, so a half-attached trace must never be left behind
-    float4* tr = nullptr; int* tn = nullptr;
-    hipError_t e = hipMalloc((void**)&tr, (size_t)D.cfg.B * capacity * sizeof(float4));
-    if (e == hipSuccess) e = hipMalloc((void**)&tn, (size_t)D.cfg.B * sizeof(int));
-    if (e == hipSuccess) e = hipMemset(tn, 0, (size_t)D.cfg.B * sizeof(int));
-    if (e != hipSuccess) {
-        if (tr) (void)hipFree(tr);
-        if (tn) (void)hipFree(tn);
-        sfx_set_error("sfx_batch_trace: %s", hipGetErrorString(e));
-        return -2;
-    }
+    DevAlloc fresh;
+    float4* tr = fresh.alloc<float4>((size_t)D.cfg.B * capacity);
+    int* tn = fresh.zeros<int>(D.cfg.B);
+    if (fresh.failed) { sfx_set_error("sfx_batch_trace: %s", hipGetErrorString(hipGetLastError())); return -2; }
+    std::swap(b->trace_mem.ptrs, fresh.ptrs);
     D.trace = tr; D.trace_n = tn; D.trace_cap = capacity;
     return 0;
 }
@@ -1757,7 +1697,8 @@ extern "C" int sfx_lbs_forward(sfx_model* m, int32_t B, const float* go, const f
     if (!m) { sfx_set_error("null model"); return -1; }
     hipStream_t s = (hipStream_t)stream;
     if (!m->fwd || m->fwd_B != B) {
-        if (m->fwd) sfx_batch_destroy(m->fwd);
+        sfx_batch_destroy(m->fwd);
+        m->fwd = nullptr; m->fwd_B = 0;      // (sfx_batch_create writes its result only on success)
         sfx_batch_cfg c{}; c.B = B; c.n_stages = 0; c.maxiters = 1; c.num_body_joints = m->M.K; c.lbs_mode = 1;   // forward only
         sfx_stage_weights w{};
         int rc = sfx_batch_create(m, &c, &w, &m->fwd);

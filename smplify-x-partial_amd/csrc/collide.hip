@@ -43,6 +43,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <memory>
 #include <vector>
 
 #define PEN_T 1024
@@ -193,19 +194,7 @@ struct sfx_pen {
     int Bmax = 0;
     int last_B = 0;              // meshes of the most recent evaluation: what sfx_pen_pairs / sfx_pen_stats may be asked about
     int form = 0;                // (lab build: sfx_debug_pen_form; the product has one form)
-    std::vector<void*> mem;
-    template <typename T> T* up(const std::vector<T>& h) {
-        T* d = nullptr;
-        if (hipMalloc((void**)&d, std::max<size_t>(h.size(), 1) * sizeof(T)) != hipSuccess) return nullptr;
-        if (!h.empty()) hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
-        mem.push_back(d); return d;
-    }
-    template <typename T> T* zeros(size_t n) {
-        T* d = nullptr;
-        if (hipMalloc((void**)&d, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return nullptr;
-        hipMemset(d, 0, std::max<size_t>(n, 1) * sizeof(T));
-        mem.push_back(d); return d;
-    }
+    DevAlloc mem;                // every device buffer of the handle
 };
 
 #ifdef SFX_LAB
@@ -218,7 +207,7 @@ extern "C" int sfx_pen_create(int32_t V, int32_t F, const int32_t* faces, const 
     if (!faces || !out || V < 3 || F < 1 || max_batch < 1 || max_collisions < 1) { sfx_set_error("bad arguments"); return -1; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { sfx_set_error("no HIP device: libsfx has no CPU fallback"); return -3; }
-    sfx_pen* h = new sfx_pen();
+    std::unique_ptr<sfx_pen> h(new sfx_pen());      // (a refusal below releases it, device memory included)
     PenDev& P = h->P;
     P.V = V; P.F = F; P.cap = max_collisions; h->Bmax = max_batch;
     P.work = pen_work_buffer(); P.over = nullptr;
@@ -226,8 +215,8 @@ extern "C" int sfx_pen_create(int32_t V, int32_t F, const int32_t* faces, const 
     std::vector<int> fv(faces, faces + (size_t)F * 3), sg(F, 0);
     int np = 1;
     if (segm) { for (int f = 0; f < F; ++f) { sg[f] = segm[f]; np = std::max(np, segm[f] + 1); } }
-    if (np > 64 || F >= (1 << 24)) { sfx_set_error("at most 64 parts and 2^24 faces"); delete h; return -1; }
-    for (int f = 0; f < F; ++f) if (sg[f] < 0) { sfx_set_error("negative part label"); delete h; return -1; }
+    if (np > 64 || F >= (1 << 24)) { sfx_set_error("at most 64 parts and 2^24 faces"); return -1; }
+    for (int f = 0; f < F; ++f) if (sg[f] < 0) { sfx_set_error("negative part label"); return -1; }
     // part-level table: same part, parent / child, or listed in ign_part_pairs (fit_single_frame.py:318-328)
     std::vector<unsigned char> skip((size_t)np * np, 0);
     if (segm) {
@@ -243,46 +232,44 @@ extern "C" int sfx_pen_create(int32_t V, int32_t F, const int32_t* faces, const 
     P.n_parts = np;
     std::vector<int> vs(V + 1, 0), vl((size_t)F * 3);
     for (size_t i = 0; i < fv.size(); ++i) {
-        if (fv[i] < 0 || fv[i] >= V) { sfx_set_error("face index out of range"); delete h; return -1; }
+        if (fv[i] < 0 || fv[i] >= V) { sfx_set_error("face index out of range"); return -1; }
         vs[fv[i] + 1]++;
     }
     for (int v = 0; v < V; ++v) vs[v + 1] += vs[v];
     { std::vector<int> cur(vs.begin(), vs.end() - 1); for (size_t i = 0; i < fv.size(); ++i) vl[cur[fv[i]]++] = (int)i; }
     std::vector<unsigned long long> skm(64, 0ull);
     for (int a = 0; a < np; ++a) for (int b2 = 0; b2 < np; ++b2) if (skip[(size_t)a * np + b2]) skm[a] |= 1ull << b2;
-    P.skipmask = h->up(skm);
-    { std::vector<int4> f4(F); for (int f = 0; f < F; ++f) f4[f] = make_int4(fv[(size_t)f * 3], fv[(size_t)f * 3 + 1], fv[(size_t)f * 3 + 2], 0); P.faces4 = h->up(f4); }
-    P.faces = h->up(fv); P.segm = h->up(sg); P.skip = h->up(skip); P.vf_start = h->up(vs); P.vf_list = h->up(vl);
+    P.skipmask = h->mem.up(skm);
+    { std::vector<int4> f4(F); for (int f = 0; f < F; ++f) f4[f] = make_int4(fv[(size_t)f * 3], fv[(size_t)f * 3 + 1], fv[(size_t)f * 3 + 2], 0); P.faces4 = h->mem.up(f4); }
+    P.faces = h->mem.up(fv); P.segm = h->mem.up(sg); P.skip = h->mem.up(skip); P.vf_start = h->mem.up(vs); P.vf_list = h->mem.up(vl);
     const size_t B = max_batch;
     P.ent_cap = F * 32;
-    P.aabb = h->zeros<float>(B * F * 6); P.entries = h->zeros<int2>(B * P.ent_cap);
-    P.tlist = nullptr; P.tcount = h->zeros<int>(B * 16);
-    P.cand = h->zeros<int2>(B * (size_t)P.ent_cap);
-    if (!P.cand) { sfx_set_error("out of device memory"); for (void* p : h->mem) hipFree(p); delete h; return -2; }
+    P.aabb = h->mem.zeros<float>(B * F * 6); P.entries = h->mem.zeros<int2>(B * P.ent_cap);
+    P.tlist = nullptr; P.tcount = h->mem.zeros<int>(B * 16);
+    P.cand = h->mem.zeros<int2>(B * (size_t)P.ent_cap);
     {   // part boxes start EMPTY (k_pen_g3 leaves them empty again after every evaluation)
         std::vector<int> pb(B * 64 * 6);
         for (size_t i = 0; i < pb.size(); ++i) pb[i] = (i % 6) < 3 ? 0x7fffffff : (int)0x80000000;
-        P.pbox = h->up(pb);
+        P.pbox = h->mem.up(pb);
     }
-    P.gpart = h->zeros<float>(B * PEN_GW * 8);
-    P.partners = h->zeros<int>(B * F * P.pcap); P.pcount = h->zeros<int>(B * F); P.pavail = h->zeros<int>(B * F);
-    P.ovq = h->zeros<int>(B * F); P.ovn = h->zeros<int>(B * 2); P.callno = h->zeros<int>(2); P.ovm = h->zeros<int>(B + 1);
+    P.gpart = h->mem.zeros<float>(B * PEN_GW * 8);
+    P.partners = h->mem.zeros<int>(B * F * P.pcap); P.pcount = h->mem.zeros<int>(B * F); P.pavail = h->mem.zeros<int>(B * F);
+    P.ovq = h->mem.zeros<int>(B * F); P.ovn = h->mem.zeros<int>(B * 2); P.callno = h->mem.zeros<int>(2); P.ovm = h->mem.zeros<int>(B + 1);
     P.pair_cap = (int)std::min<size_t>((size_t)F * P.cap, std::max<size_t>(65536, (size_t)16 * F));
-    P.hasp_words = (F + 31) / 32; P.hasp = h->zeros<unsigned>(B * P.hasp_words);
-    P.poff = h->zeros<int>(B * F); P.pown = h->zeros<int>(B * P.pair_cap); P.plist = h->zeros<int>(B * P.pair_cap);
-    P.pout = h->zeros<float>(B * 10 * P.pair_cap); P.ptotal = h->zeros<int>(B); P.stats = h->zeros<int>(B * PEN_STATS);
-    P.cells = h->zeros<int>(B * (PEN_CELLS + 1)); P.gridp = h->zeros<float>(B * 4);
+    P.hasp_words = (F + 31) / 32; P.hasp = h->mem.zeros<unsigned>(B * P.hasp_words);
+    P.poff = h->mem.zeros<int>(B * F); P.pown = h->mem.zeros<int>(B * P.pair_cap); P.plist = h->mem.zeros<int>(B * P.pair_cap);
+    P.pout = h->mem.zeros<float>(B * 10 * P.pair_cap); P.ptotal = h->mem.zeros<int>(B); P.stats = h->mem.zeros<int>(B * PEN_STATS);
+    P.cells = h->mem.zeros<int>(B * (PEN_CELLS + 1)); P.gridp = h->mem.zeros<float>(B * 4);
     P.wq_cap = std::max(1024, P.ent_cap / 8);      // (a block of 64 entries queues at most PEN_MAX_CHUNK - 1 chunks; a full queue makes the block walk on itself)
-    P.wq = h->zeros<int2>(B * (size_t)P.wq_cap); P.wqn = h->zeros<int>(B);
-    if (!P.wq || !P.wqn) { sfx_set_error("out of device memory"); for (void* p : h->mem) hipFree(p); delete h; return -2; }
-    P.tgrad = h->zeros<float>(B * F * 9); P.tloss = h->zeros<float>(B * F);
+    P.wq = h->mem.zeros<int2>(B * (size_t)P.wq_cap); P.wqn = h->mem.zeros<int>(B);
+    P.tgrad = h->mem.zeros<float>(B * F * 9); P.tloss = h->mem.zeros<float>(B * F);
 #ifdef SFX_LAB
     h->form = g_pen_form;
 #endif
     P.n_clus = (F + 63) / 64;
     P.cpm = nullptr; P.wbox = nullptr;        // (cluster boxes: only round 5's k_pen_frame read them)
-    P.heavy = h->zeros<int>(B); P.hlist = h->zeros<int>(B); P.nheavy = h->zeros<int>(1); P.pcnt = h->zeros<int>(B);
-    P.wl = h->zeros<int>(B); P.nw = h->zeros<int>(1); P.rb = h->zeros<int>((size_t)B * P.n_clus); P.nrb = h->zeros<int>(B); P.lq = h->zeros<int>((size_t)B * F); P.nlq = h->zeros<int>(B);
+    P.heavy = h->mem.zeros<int>(B); P.hlist = h->mem.zeros<int>(B); P.nheavy = h->mem.zeros<int>(1); P.pcnt = h->mem.zeros<int>(B);
+    P.wl = h->mem.zeros<int>(B); P.nw = h->mem.zeros<int>(1); P.rb = h->mem.zeros<int>((size_t)B * P.n_clus); P.nrb = h->mem.zeros<int>(B); P.lq = h->mem.zeros<int>((size_t)B * F); P.nlq = h->mem.zeros<int>(B);
     P.pbuf = reinterpret_cast<int2*>(P.partners);         // (the partner lists are unused on the fast path)
     P.pf_cap = (int)std::min<size_t>(PEN_FP, (size_t)F * P.pcap / 2);
 #ifdef SFX_LAB
@@ -290,10 +277,8 @@ extern "C" int sfx_pen_create(int32_t V, int32_t F, const int32_t* faces, const 
 #endif
     P.pf_cap = std::max(1, std::min(P.pf_cap, P.pair_cap / 2));      // (a mesh's pair list holds both orders of every pair the one-workgroup form accepts: small meshes too)
     P.fast_ok = ((unsigned long long)F * (unsigned long long)F < (1ull << 32)) && (2 * ((F + 31) / 32) + (V + 31) / 32 + V <= PEN_GRID_INTS) ? 1 : 0;
-    if (!P.heavy || !P.hlist || !P.nheavy || !P.pcnt || !P.wl || !P.nw || !P.rb || !P.nrb || !P.lq || !P.nlq) { sfx_set_error("out of device memory"); for (void* p : h->mem) hipFree(p); delete h; return -2; }
-    if (!P.cells || !P.gridp || !P.tgrad || !P.tloss || !P.tcount || !P.pbox || !P.gpart || !P.aabb || !P.entries) { sfx_set_error("out of device memory"); for (void* p : h->mem) hipFree(p); delete h; return -2; }
-    if (!P.stats || !P.pout || !P.plist || !P.pown || !P.poff || !P.partners || !P.pavail || !P.ptotal || !P.ovq || !P.ovn || !P.callno || !P.ovm) { sfx_set_error("out of device memory"); for (void* p : h->mem) hipFree(p); delete h; return -2; }
-    *out = h;
+    if (h->mem.failed) { (void)hipGetLastError(); sfx_set_error("out of device memory"); return -2; }
+    *out = h.release();
     return 0;
 }
 
@@ -313,8 +298,6 @@ extern "C" int sfx_pen_set_point2plane(sfx_pen* h, int32_t on) {
     return 0;
 }
 extern "C" void sfx_pen_destroy(sfx_pen* h) {
-    if (!h) return;
-    for (void* p : h->mem) hipFree(p);
     delete h;
 }
 

@@ -44,17 +44,13 @@ void k_debug_two_loop(OptState* gst, float* hist, const float* S_in, const float
 }
 
 int debug_two_loop(const float* S, const float* Y, int cnt, int hist_cap, const float* g, float* d_out) {
-    OptState* gst = nullptr; float *hist = nullptr, *dS = nullptr, *dY = nullptr, *dg = nullptr, *dd = nullptr;
-    const size_t row = SFX_NVAR_MAX * sizeof(float), hb = (size_t)2 * ((hist_cap > SFX_HIST ? hist_cap : SFX_HIST) + 8) * row;
-    int rc = 0;
-    auto ok = [&rc](hipError_t e) { if (e != hipSuccess && !rc) rc = (int)e; return e == hipSuccess; };
-    if (ok(hipMalloc(&gst, sizeof(OptState))) && ok(hipMalloc(&hist, hb)) && ok(hipMalloc(&dS, row * cnt)) && ok(hipMalloc(&dY, row * cnt)) &&
-        ok(hipMalloc(&dg, row)) && ok(hipMalloc(&dd, row)) && ok(hipMemset(gst, 0, sizeof(OptState))) && ok(hipMemset(hist, 0, hb)) &&
-        ok(hipMemcpy(dS, S, row * cnt, hipMemcpyHostToDevice)) && ok(hipMemcpy(dY, Y, row * cnt, hipMemcpyHostToDevice)) &&
-        ok(hipMemcpy(dg, g, row, hipMemcpyHostToDevice))) {
-        hipLaunchKernelGGL(k_debug_two_loop, dim3(1), dim3(64), 0, 0, gst, hist, dS, dY, cnt, hist_cap, dg, dd);
-        ok(hipDeviceSynchronize()); ok(hipMemcpy(d_out, dd, row, hipMemcpyDeviceToHost));
-    }
-    hipFree(gst); hipFree(hist); hipFree(dS); hipFree(dY); hipFree(dg); hipFree(dd);
-    return rc;
+    const size_t row = SFX_NVAR_MAX, hrows = (size_t)2 * ((hist_cap > SFX_HIST ? hist_cap : SFX_HIST) + 8);
+    DevAlloc scratch;       // all buffers or none: freed on every way out
+    OptState* gst = scratch.zeros<OptState>(1);
+    float *hist = scratch.zeros<float>(hrows * row), *dS = scratch.up(S, row * cnt), *dY = scratch.up(Y, row * cnt),
+          *dg = scratch.up(g, row), *dd = scratch.alloc<float>(row);
+    if (scratch.failed) { (void)hipGetLastError(); return -2; }
+    hipLaunchKernelGGL(k_debug_two_loop, dim3(1), dim3(64), 0, 0, gst, hist, dS, dY, cnt, hist_cap, dg, dd);
+    if (hipError_t e = hipDeviceSynchronize()) return (int)e;
+    return (int)hipMemcpy(d_out, dd, row * sizeof(float), hipMemcpyDeviceToHost);
 }

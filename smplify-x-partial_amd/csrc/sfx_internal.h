@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
+#include <vector>
 
 #define SFX_J 55            // SMPL-X kinematic joints
 #define SFX_POSE (3 * SFX_J)
@@ -262,6 +264,35 @@ enum { VEC_XINIT = 0, VEC_D, VEC_G, VEC_PREVG, VEC_GPREV, VEC_BG0, VEC_BG1, VEC_
     sfx_set_error("%s:%d %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(e_)); return -2; } } while (0)
 
 void sfx_set_error(const char* fmt, ...);
+
+// The one owner of device memory on the host side: a handle (sfx_model, sfx_batch, sfx_pen) or a function's scratch holds one,
+// and whatever it handed out is freed when it goes out of scope -- an early return (SFX_CHECK) after it leaks nothing.
+struct DevAlloc {
+    std::vector<void*> ptrs;
+    bool failed = false;        // sticky: any hipMalloc / hipMemcpy / hipMemset of this owner failed (checked once by the creator)
+    DevAlloc() = default;
+    DevAlloc(const DevAlloc&) = delete;
+    DevAlloc& operator=(const DevAlloc&) = delete;
+    ~DevAlloc() { clear(); }
+    void clear() { for (void* p : ptrs) (void)hipFree(p); ptrs.clear(); }
+    template <typename T> T* alloc(size_t count) {      // uninitialised; never a zero-byte request
+        T* d = nullptr;
+        if (hipMalloc((void**)&d, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) { failed = true; return nullptr; }
+        ptrs.push_back(d);
+        return d;
+    }
+    template <typename T> T* zeros(size_t count) {
+        T* d = alloc<T>(count);
+        if (d && hipMemset(d, 0, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) failed = true;
+        return d;
+    }
+    template <typename T> T* up(const T* h, size_t count) {
+        T* d = alloc<T>(count);
+        if (d && count && hipMemcpy(d, h, count * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) failed = true;
+        return d;
+    }
+    template <typename T> T* up(const std::vector<T>& h) { return up(h.data(), h.size()); }
+};
 
 // kernel launchers (defined in the .hip files)
 struct ClosureArgs {

@@ -553,3 +553,31 @@ def test_long_queue_through_a_small_column_pool(synth_model):
         res[slots] = fb.stats()["stage_loss"][:, :2].copy()
         fb.close()
     assert np.all(np.isfinite(res[32])) and np.array_equal(res[0], res[32])
+
+
+def test_a_refused_model_keeps_no_device_memory(synth_model, cfg_body):
+    """sfx_model_create refuses a joint_map entry out of range AFTER it has uploaded the blend-shape arrays (dirs, dirsT,
+    dirs_tiled: most of a model at any vertex count).  A refusal is an ordinary error return and must hand back everything
+    it took: eight of them in a row leave free device memory within m / 2 of where it was, m being what one successful model
+    occupies (a library that kept the uploads would lose several m; m / 2 is room for the allocator's own caching)."""
+    from smplifyx_amd import _capi
+    import gc
+    gc.collect()                                # (handles that earlier tests left to the collector go now, not in between)
+    T._dm(synth_model, cfg_body).close()        # (what the runtime takes once, at the library's first use, is not part of m)
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info()[0]
+    dm = T._dm(synth_model, cfg_body)
+    m = free0 - torch.cuda.mem_get_info()[0]
+    dm.close()
+    assert m > 32 << 20, "the model must be well above the allocator's granularity, got %d bytes" % m
+    jm = np.array(H.joint_map_for(cfg_body)).copy()
+    jm[-1] = 10 ** 6
+    from smplifyx_amd import engine
+    for _ in range(8):
+        with pytest.raises(_capi.SfxError, match="out of range"):
+            engine.DeviceModel(synth_model, joint_map=jm, num_betas=cfg_body["num_betas"],
+                               num_expression_coeffs=cfg_body["num_expression_coeffs"],
+                               num_pca_comps=cfg_body["num_pca_comps"], use_face_contour=cfg_body["use_face_contour"])
+    after = torch.cuda.mem_get_info()[0]
+    print("model %.1f MB; free memory at the start / after eight refusals: %.1f / %.1f MB" % (m / 2 ** 20, free0 / 2 ** 20, after / 2 ** 20))
+    assert abs(free0 - after) <= m / 2, (m, free0, after)
