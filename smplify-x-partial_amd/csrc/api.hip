@@ -4,6 +4,7 @@
 // device->host poll every POLL ticks.
 #include "../../include/sfx.h"
 #include "sfx_internal.h"
+#include "model_tables.h"
 
 #include <algorithm>
 #include <chrono>
@@ -124,7 +125,7 @@ struct sfx_model {
     DevAlloc mem;
     std::vector<int> faces_host, segm_host, parents_host, ign_host;   // interpenetration set-up
     int NB = 0, NE = 0, NPCA = 0;
-    std::vector<int> meta_host = std::vector<int>(SFX_META_N, 0);
+    std::vector<int> meta_host;   // DevModel.meta
     sfx_batch* fwd = nullptr;     // lazily created batch behind sfx_lbs_forward
     int fwd_B = 0;
     // The collision buffers of the interpenetration term (~45 MB per GEMM column: 11.5 GB for 256 columns) outlive the batch that
@@ -217,345 +218,47 @@ static bool fp32_exact(const double* v, size_t n) {
 extern "C" int sfx_model_create(const sfx_model_desc* d, sfx_model** out) {
     if (!d || !out) { sfx_set_error("null argument"); return -1; }
     if (d->J != SFX_J) { sfx_set_error("only J=55 (SMPL-X) is supported, got %d", d->J); return -1; }
-    const int V = d->V, S = d->num_betas + d->num_expr, P = 9 * (d->J - 1), KD = S + P;
+    const int V = d->V, S = d->num_betas + d->num_expr, KD = S + 9 * (d->J - 1);
     if (KD > SFX_KD_PAD) { sfx_set_error("blend-shape depth %d unsupported", KD); return -1; }
     if (d->K > SFX_MAX_K) { sfx_set_error("K=%d > %d", d->K, SFX_MAX_K); return -1; }
     int dev_count = 0;
     if (hipGetDeviceCount(&dev_count) != hipSuccess || dev_count == 0) {
         sfx_set_error("no HIP device: libsfx has no CPU fallback"); return -3;
     }
-    std::unique_ptr<sfx_model> m(new sfx_model());      // (every refusal below releases it, uploads included)
+    ModelTables T;
+    if (int rc = sfx_build_model_tables(d, &T)) return rc;      // every refusal: before the first device allocation
+    std::unique_ptr<sfx_model> m(new sfx_model());
     DevModel& M = m->M;
+    DevAlloc& mem = m->mem;
     m->NB = d->num_betas; m->NE = d->num_expr; m->NPCA = d->num_pca;
-    M.V = V; M.F = d->F; M.S = S; M.P = P; M.KD = KD; M.K = d->K;
-    M.n_extra = d->n_extra; M.n_lmk = d->n_lmk; M.n_dyn_rows = d->n_dyn_rows; M.n_dyn = d->n_dyn;
-    M.Vpad = ((V + 31) / 32) * 32;
-
-    std::vector<float> vt(d->v_template, d->v_template + (size_t)V * 3);
-    M.v_template = m->mem.up(vt);
-    // blend-shape matrix, k-major [KD_PAD][3*Vpad] (zero rows beyond KD) and vertex-major [V][3][KD_PAD]
-    {
-        const size_t LD = (size_t)3 * M.Vpad;
-        std::vector<float> dirs((size_t)SFX_KD_PAD * LD, 0.f), dirsT((size_t)V * 3 * SFX_KD_PAD, 0.f);
-        for (int v = 0; v < V; ++v)
-            for (int c = 0; c < 3; ++c) {
-                const float* sd = d->shapedirs + ((size_t)v * 3 + c) * S;
-                const float* pd = d->posedirs + ((size_t)v * 3 + c) * P;
-                float* row = &dirsT[((size_t)v * 3 + c) * SFX_KD_PAD];
-                for (int k = 0; k < S; ++k) { row[k] = sd[k]; dirs[(size_t)k * LD + (size_t)v * 3 + c] = sd[k]; }
-                for (int k = 0; k < P; ++k) { row[S + k] = pd[k]; dirs[(size_t)(S + k) * LD + (size_t)v * 3 + c] = pd[k]; }
-            }
-        M.dirs = m->mem.up(dirs);
-        M.dirsT = m->mem.up(dirsT);
-        {   // tile-major copy for the forward GEMM: [tile][k][16 vertices x 3 coordinates]
-            const int ntile = M.Vpad / 16;
-            std::vector<float> dt((size_t)ntile * SFX_KD_PAD * 48, 0.f);
-            for (int tl = 0; tl < ntile; ++tl)
-                for (int k = 0; k < SFX_KD_PAD; ++k)
-                    std::memcpy(&dt[((size_t)tl * SFX_KD_PAD + k) * 48], &dirs[(size_t)k * LD + (size_t)tl * 48], 48 * sizeof(float));
-            M.dirs_tiled = m->mem.up(dt);
-        }
-    }
-    {
-        std::vector<float> W(d->lbs_weights, d->lbs_weights + (size_t)V * SFX_J);
-        std::vector<float> WT((size_t)SFX_JPAD * M.Vpad, 0.f);
-        for (int v = 0; v < V; ++v)
-            for (int j = 0; j < SFX_J; ++j) WT[(size_t)j * M.Vpad + v] = W[(size_t)v * SFX_J + j];
-        std::vector<int> wj((size_t)V * SFX_NW, 0); std::vector<float> ww((size_t)V * SFX_NW, 0.f);
-        for (int v = 0; v < V; ++v) {
-            int n = 0;
-            for (int j = 0; j < SFX_J; ++j) {
-                const float w = W[(size_t)v * SFX_J + j];
-                if (w == 0.f) continue;
-                if (n < SFX_NW) { wj[(size_t)v * SFX_NW + n] = j; ww[(size_t)v * SFX_NW + n] = w; }
-                ++n;
-            }
-            // a row with more nonzeros than the packed form holds is flagged: the needed-rows path
-            // then reads the full row of lbs_weights for this vertex (same ascending joint order)
-            if (n > SFX_NW) wj[(size_t)v * SFX_NW] = -1;
-        }
-        M.Wsp_j = m->mem.up(wj); M.Wsp_w = m->mem.up(ww);
-        {   // transposed CSR: per joint the vertices it skins, ascending
-            std::vector<int> js(SFX_J + 1, 0), jv; std::vector<float> jw;
-            for (int j = 0; j < SFX_J; ++j) {
-                for (int v = 0; v < V; ++v) { const float w = W[(size_t)v * SFX_J + j]; if (w != 0.f) { jv.push_back(v); jw.push_back(w); } }
-                js[j + 1] = (int)jv.size();
-            }
-            M.jv_start = m->mem.up(js); M.jv_vid = m->mem.up(jv); M.jv_w = m->mem.up(jw);
-        }
-        M.W = m->mem.up(W);
-        M.WT = m->mem.up(WT);
-        // per 16-vertex tile: the joints with any nonzero weight (ascending), weights in MFMA B layout
-        const int nt = M.Vpad / 16;
-        std::vector<int> tn(nt, 0), tl((size_t)nt * SFX_JPAD, 0);
-        std::vector<float> tw((size_t)nt * SFX_JPAD * 16, 0.f);
-        for (int t = 0; t < nt; ++t) {
-            int n = 0;
-            for (int j = 0; j < SFX_J; ++j) {
-                bool used = false;
-                for (int q = 0; q < 16 && !used; ++q) { const int v = t * 16 + q; used = v < V && W[(size_t)v * SFX_J + j] != 0.f; }
-                if (!used) continue;
-                tl[(size_t)t * SFX_JPAD + n] = j;
-                for (int q = 0; q < 16; ++q) { const int v = t * 16 + q; tw[((size_t)t * SFX_JPAD + n) * 16 + q] = v < V ? W[(size_t)v * SFX_J + j] : 0.f; }
-                ++n;
-            }
-            tn[t] = ((n + 3) / 4) * 4;
-        }
-        M.tj_n = m->mem.up(tn); M.tj_list = m->mem.up(tl); M.tj_w = m->mem.up(tw);
-    }
-    // folded joint regressor: J = J_template + J_dirs . coeff   (J_regressor . v_shaped)
-    {
-        std::vector<float> Jt((size_t)SFX_J * 3), Jd((size_t)SFX_J * 3 * S);
-        std::vector<double> Jt64(Jt.size()), Jd64(Jd.size());
-        for (int j = 0; j < SFX_J; ++j) {
-            std::vector<double> acc(3 + 3 * S, 0.0);
-            const float* jr = d->J_regressor + (size_t)j * V;
-            for (int v = 0; v < V; ++v) {
-                const double w = jr[v];
-                if (w == 0.0) continue;
-                for (int c = 0; c < 3; ++c) {
-                    acc[c] += w * d->v_template[(size_t)v * 3 + c];
-                    const float* sd = d->shapedirs + ((size_t)v * 3 + c) * S;
-                    for (int l = 0; l < S; ++l) acc[3 + c * S + l] += w * sd[l];
-                }
-            }
-            for (int c = 0; c < 3; ++c) {
-                Jt[j * 3 + c] = (float)acc[c]; Jt64[j * 3 + c] = acc[c];
-                for (int l = 0; l < S; ++l) {
-                    Jd[((size_t)j * 3 + c) * S + l] = (float)acc[3 + c * S + l]; Jd64[((size_t)j * 3 + c) * S + l] = acc[3 + c * S + l]; }
-            }
-        }
-        M.J_template = m->mem.up(Jt);
-        M.J_dirs = m->mem.up(Jd);
-        M.J_template64 = m->mem.up(Jt64);
-        M.J_dirs64 = m->mem.up(Jd64);
-    }
-    // kinematic tree: depth levels and child lists
-    {
-        std::vector<int> par(d->parents, d->parents + SFX_J), depth(SFX_J, 0);
-        par[0] = -1;
-        int maxd = 0;
-        for (int j = 1; j < SFX_J; ++j) {
-            if (par[j] < 0 || par[j] >= j) { sfx_set_error("parents must be topologically ordered"); return -1; }
-            depth[j] = depth[par[j]] + 1; maxd = std::max(maxd, depth[j]);
-        }
-        if (maxd + 1 > SFX_MAX_LEVELS) { sfx_set_error("tree too deep"); return -1; }
-        M.n_levels = maxd + 1;
-        std::vector<int> lj;
-        for (int l = 0; l <= maxd; ++l) {
-            M.level_start[l] = (int)lj.size();
-            for (int j = 0; j < SFX_J; ++j) if (depth[j] == l) lj.push_back(j);
-        }
-        M.level_start[maxd + 1] = (int)lj.size();
-        std::vector<int> cs(SFX_J + 1, 0), cl;
-        for (int j = 0; j < SFX_J; ++j) {
-            cs[j] = (int)cl.size();
-            for (int c = j + 1; c < SFX_J; ++c) if (par[c] == j) cl.push_back(c);
-        }
-        cs[SFX_J] = (int)cl.size();
-        for (int j = 0; j < SFX_J; ++j) { m->meta_host[MO_PAR + j] = par[j]; m->meta_host[MO_LJ + j] = lj[j]; }
-        for (int j = 0; j <= SFX_J; ++j) m->meta_host[MO_CS + j] = cs[j];
-        for (size_t q = 0; q < cl.size(); ++q) m->meta_host[MO_CL + q] = cl[q];
-        // DFS pre-order (children in ascending joint order) and subtree sizes: the adjoint of the
-        // chain sums over subtrees, which are contiguous pre-order ranges
-        {
-            std::vector<int> pre(SFX_J, 0), sub(SFX_J, 1), stack{0};
-            int pos = 0;
-            while (!stack.empty()) {
-                const int j = stack.back(); stack.pop_back();
-                pre[j] = pos++;
-                for (int q = cs[j + 1] - 1; q >= cs[j]; --q) stack.push_back(cl[q]);
-            }
-            for (int j = SFX_J - 1; j > 0; --j) sub[par[j]] += sub[j];
-            for (int j = 0; j < SFX_J; ++j) { m->meta_host[MO_PRE + j] = pre[j]; m->meta_host[MO_SUB + j] = sub[j]; }
-        }
-        // 2^k-th ancestors for the pointer-jumping evaluation of the chain
-        {
-            int rounds = 0;
-            while ((1 << rounds) < M.n_levels) ++rounds;
-            if (rounds > SFX_MAX_ROUNDS) { sfx_set_error("tree too deep"); return -1; }
-            M.n_rounds = rounds;
-            std::vector<int> anc(par);
-            for (int k = 0; k < rounds; ++k) {
-                for (int j = 0; j < SFX_J; ++j) m->meta_host[MO_ANC + k * 56 + j] = anc[j];
-                std::vector<int> nxt(SFX_J);
-                for (int j = 0; j < SFX_J; ++j) nxt[j] = anc[j] < 0 ? -1 : anc[anc[j]];
-                anc = nxt;
-            }
-        }
-        M.parents = m->mem.up(par); M.level_joints = m->mem.up(lj);
-        M.child_start = m->mem.up(cs); M.child_list = m->mem.up(cl);
-    }
-    {
-        std::vector<float> cl(d->hands_comp_l, d->hands_comp_l + (size_t)d->num_pca * SFX_NHAND);
-        std::vector<float> cr(d->hands_comp_r, d->hands_comp_r + (size_t)d->num_pca * SFX_NHAND);
-        std::vector<float> pm(d->pose_mean, d->pose_mean + SFX_POSE);
-        M.comp_l = m->mem.up(cl); M.comp_r = m->mem.up(cr); M.pose_mean = m->mem.up(pm);
-    }
-    {
-        std::vector<int> faces(d->faces, d->faces + (size_t)d->F * 3);
-        M.faces = m->mem.up(faces);
-        m->faces_host = faces;
-        std::vector<int> df; std::vector<float> db;
-        if (d->n_dyn > 0) {
-            df.assign(d->dyn_lmk_faces_idx, d->dyn_lmk_faces_idx + (size_t)d->n_dyn_rows * d->n_dyn);
-            db.assign(d->dyn_lmk_bary, d->dyn_lmk_bary + (size_t)d->n_dyn_rows * d->n_dyn * 3);
-        }
-        M.dyn_faces = m->mem.up(df); M.dyn_bary = m->mem.up(db);
-    }
-    // mapped joints -> kinematic joints / vertex items
-    {
-        const int K = d->K;
-        std::vector<int> jt(K), js(K, 0), ji0(K, 0), jn(K, 0), ivid, idyn, ik;
-        std::vector<float> iw;
-        std::vector<std::vector<int>> readers(SFX_J);
-        const int e0 = SFX_J, l0 = e0 + d->n_extra, d0 = l0 + d->n_lmk, end = d0 + d->n_dyn;
-        for (int k = 0; k < K; ++k) {
-            const int s = d->joint_map[k];
-            if (s < 0 || s >= end) { sfx_set_error("joint_map[%d]=%d out of range [0,%d)", k, s, end); return -1; }
-            if (s < e0) { jt[k] = 0; js[k] = s; readers[s].push_back(k); continue; }
-            jt[k] = 1; ji0[k] = (int)ivid.size();
-            if (s < l0) { ivid.push_back(d->extra_vertex_ids[s - e0]); iw.push_back(1.f); idyn.push_back(-1); ik.push_back(k); jn[k] = 1; }
-            else if (s < d0) {
-                const int l = s - l0, f = d->lmk_faces_idx[l];
-                for (int c = 0; c < 3; ++c) { ivid.push_back(d->faces[(size_t)f * 3 + c]); iw.push_back(d->lmk_bary[l * 3 + c]);
-                                              idyn.push_back(-1); ik.push_back(k); }
-                jn[k] = 3;
-            } else {
-                const int l = s - d0;
-                for (int c = 0; c < 3; ++c) { ivid.push_back(-1); iw.push_back(0.f); idyn.push_back(l * 3 + c); ik.push_back(k); }
-                jn[k] = 3;
-            }
-        }
-        if ((int)ivid.size() > SFX_MAX_ITEMS) { sfx_set_error("too many vertex items"); return -1; }
-        M.n_items = (int)ivid.size();
-        std::vector<int> sk0(SFX_J + 1, 0), skl;
-        for (int s = 0; s < SFX_J; ++s) { sk0[s] = (int)skl.size(); for (int k : readers[s]) skl.push_back(k); }
-        sk0[SFX_J] = (int)skl.size();
-        for (int s2 = 0; s2 <= SFX_J; ++s2) m->meta_host[MO_SK0 + s2] = sk0[s2];
-        for (size_t q = 0; q < skl.size(); ++q) m->meta_host[MO_SKL + q] = skl[q];
-        for (int k = 0; k < K; ++k) { m->meta_host[MO_JT + k] = jt[k]; m->meta_host[MO_JS + k] = js[k];
-                                      m->meta_host[MO_JI0 + k] = ji0[k]; m->meta_host[MO_JN + k] = jn[k]; }
-        for (size_t q = 0; q < ik.size(); ++q) m->meta_host[MO_IK + q] = ik[q];
-        std::vector<int> dyn_pv;        // [rows][nd] vertices of the dynamic-contour items (filled below; the export table needs them)
-        // by-joint adjoint lists
-        {
-            auto build = [&](const std::vector<int>& vids, const std::vector<int>& items, std::vector<int>& start,
-                             std::vector<int>& it, std::vector<float>& wv, int base) {
-                for (int j = 0; j < SFX_J; ++j) {
-                    start.push_back(base + (int)it.size());
-                    for (size_t q = 0; q < items.size(); ++q) {
-                        const float w = d->lbs_weights[(size_t)vids[q] * SFX_J + j];
-                        if (w != 0.f) { it.push_back(items[q]); wv.push_back(w); }
-                    }
-                }
-                start.push_back(base + (int)it.size());
-            };
-            std::vector<int> svid, sitem, dynitems;
-            for (int i = 0; i < (int)ivid.size(); ++i) { if (idyn[i] < 0) { svid.push_back(ivid[i]); sitem.push_back(i); } else dynitems.push_back(i); }
-            std::vector<int> ss, si; std::vector<float> sw2;
-            build(svid, sitem, ss, si, sw2, 0);
-            M.sj_start = m->mem.up(ss); M.sj_item = m->mem.up(si); M.sj_w = m->mem.up(sw2); M.n_sj = (int)si.size();
-            std::vector<int> ds, di; std::vector<float> dw;
-            M.n_dyn_items = (int)dynitems.size();
-            for (int row = 0; row < d->n_dyn_rows && !dynitems.empty(); ++row) {
-                std::vector<int> vids;
-                for (int i : dynitems) {
-                    const int l = idyn[i] / 3, c = idyn[i] % 3;
-                    const int f = d->dyn_lmk_faces_idx[(size_t)row * d->n_dyn + l];
-                    vids.push_back(d->faces[(size_t)f * 3 + c]);
-                }
-                std::vector<int> st;
-                build(vids, dynitems, st, di, dw, 0);
-                // offsets are absolute into di/dw: rebuild with the running base
-                ds.insert(ds.end(), st.begin(), st.end());
-            }
-            // 'build' used base 0 relative to the current size of di at call time -> already absolute
-            M.dj_start = m->mem.up(ds); M.dj_item = m->mem.up(di); M.dj_w = m->mem.up(dw);
-            // the same per LUT row in fixed-size blocks, together with the row's vertices, barycentric weights, template
-            // rows and sparse skinning weights (closure_body fetches one block asynchronously)
-            const int nd = (int)dynitems.size(), rows = nd ? d->n_dyn_rows : 0;
-            if (nd > SFX_MAX_DYN) { sfx_set_error("too many dynamic-contour items (%d > %d)", nd, SFX_MAX_DYN); return -1; }
-            std::vector<int> pv((size_t)rows * nd), pwj((size_t)rows * nd * SFX_NW, 0), pjs((size_t)rows * (SFX_J + 1), 0), pji((size_t)rows * nd * SFX_NW, 0);
-            std::vector<float> pw((size_t)rows * nd), pvt((size_t)rows * nd * 3), pww((size_t)rows * nd * SFX_NW, 0.f), pjw((size_t)rows * nd * SFX_NW, 0.f);
-            for (int row = 0; row < rows; ++row) {
-                for (int q = 0; q < nd; ++q) {
-                    const int i = dynitems[q], l = idyn[i] / 3, c = idyn[i] % 3;
-                    const int f = d->dyn_lmk_faces_idx[(size_t)row * d->n_dyn + l];
-                    const int v = d->faces[(size_t)f * 3 + c];
-                    const size_t o = (size_t)row * nd + q;
-                    pv[o] = v; pw[o] = d->dyn_lmk_bary[((size_t)row * d->n_dyn + l) * 3 + c];
-                    for (int e = 0; e < 3; ++e) pvt[o * 3 + e] = d->v_template[(size_t)v * 3 + e];
-                    int n = 0;
-                    for (int j = 0; j < SFX_J; ++j) {
-                        const float w = d->lbs_weights[(size_t)v * SFX_J + j];
-                        if (w == 0.f) continue;
-                        if (n < SFX_NW) { pwj[o * SFX_NW + n] = j; pww[o * SFX_NW + n] = w; }
-                        ++n;
-                    }
-                    if (n > SFX_NW) pwj[o * SFX_NW] = -1;
-                }
-                const int* st = &ds[(size_t)row * (SFX_J + 1)];
-                const int n_row = st[SFX_J] - st[0];
-                if (n_row > nd * SFX_NW) {      // (> SFX_NW weights per vertex on average: the closure falls back to dj_*)
-                    pjs.clear(); break; }
-                for (int j = 0; j <= SFX_J; ++j) pjs[(size_t)row * (SFX_J + 1) + j] = st[j] - st[0];
-                for (int q = 0; q < n_row; ++q) { pji[(size_t)row * nd * SFX_NW + q] = di[st[0] + q]; pjw[(size_t)row * nd * SFX_NW + q] = dw[st[0] + q]; }
-            }
-            dyn_pv = pv;
-            M.dynp_vid = m->mem.up(pv); M.dynp_w = m->mem.up(pw); M.dynp_vt = m->mem.up(pvt);
-            M.dynp_wj = m->mem.up(pwj); M.dynp_ww = m->mem.up(pww);
-            M.dynp_js = pjs.empty() ? nullptr : m->mem.up(pjs);
-            M.dynp_ji = m->mem.up(pji); M.dynp_jw = m->mem.up(pjw);
-        }
-        M.jk_type = m->mem.up(jt); M.jk_src = m->mem.up(js); M.jk_item0 = m->mem.up(ji0); M.jk_nitem = m->mem.up(jn);
-        M.item_vid = m->mem.up(ivid); M.item_w = m->mem.up(iw); M.item_dyn = m->mem.up(idyn); M.item_k = m->mem.up(ik);
-        {   // template rows and packed skinning weights of the items, gathered per item: the per-frame kernels fetch them at
-            // entry in ONE round trip (through item_vid it took two, in every launch of the tick kernel)
-            const size_t ni = ivid.size();
-            std::vector<float> svt(ni * 3, 0.f), sww(ni * SFX_NW, 0.f); std::vector<int> swj(ni * SFX_NW, 0);
-            for (size_t i = 0; i < ni; ++i) {
-                const int v = ivid[i];
-                if (v < 0) continue;
-                for (int c = 0; c < 3; ++c) svt[i * 3 + c] = d->v_template[(size_t)v * 3 + c];
-                int n = 0;
-                for (int j = 0; j < SFX_J; ++j) {
-                    const float w = d->lbs_weights[(size_t)v * SFX_J + j];
-                    if (w == 0.f) continue;
-                    if (n < SFX_NW) { swj[i * SFX_NW + n] = j; sww[i * SFX_NW + n] = w; }
-                    ++n;
-                }
-                if (n > SFX_NW) swj[i * SFX_NW] = -1;      // (same flag as Wsp_j: the full row of lbs_weights is read instead)
-            }
-            M.item_vt = m->mem.up(svt); M.item_wj = m->mem.up(swj); M.item_ww = m->mem.up(sww);
-        }
-        {   // distinct vertices of the static items -- and of every vertex a dynamic-contour item can land on (all LUT rows):
-            // the dense GEMM hands their blend offsets to the per-frame kernel, which then streams no blend-shape row forward
-            std::vector<int> vslot(M.Vpad, -1), uslot(ivid.size(), -1);
-            int nu = 0, nstat = 0;
-            for (size_t i = 0; i < ivid.size(); ++i) {
-                if (idyn[i] >= 0) continue;
-                ++nstat;
-                if (vslot[ivid[i]] < 0) vslot[ivid[i]] = nu++;
-                uslot[i] = vslot[ivid[i]];
-            }
-            for (size_t i = 0; i + 1 < ivid.size(); ++i)
-                if (idyn[i] >= 0 && idyn[i + 1] < 0) { sfx_set_error("internal: dynamic items must trail the static ones"); return -1; }
-            std::vector<int> pus(dyn_pv.size(), -1);
-            for (size_t o = 0; o < dyn_pv.size(); ++o) {
-                const int v = dyn_pv[o];
-                if (vslot[v] < 0) vslot[v] = nu++;
-                pus[o] = vslot[v];
-            }
-            M.dynp_us = pus.empty() ? nullptr : m->mem.up(pus);
-            M.n_uniq = nu; M.n_static_items = nstat;
-            M.vslot = m->mem.up(vslot); M.item_uslot = m->mem.up(uslot);
-        }
-        M.src_k0 = m->mem.up(sk0); M.src_klist = m->mem.up(skl);
-    }
-    if (m->meta_host.size() != SFX_META_N) { sfx_set_error("internal: meta table"); return -1; }
-    M.meta = m->mem.up(m->meta_host);
-    if (m->mem.failed) { (void)hipGetLastError(); sfx_set_error("out of device memory (model constants)"); return -2; }
+    M.V = V; M.S = S; M.K = d->K; M.n_dyn = d->n_dyn; M.Vpad = T.Vpad; M.n_rounds = T.n_rounds;
+    M.n_items = T.n_items; M.n_static_items = T.n_static_items; M.n_uniq = T.n_uniq; M.n_sj = T.n_sj; M.n_dyn_items = T.n_dyn_items;
+    M.v_template = mem.up(d->v_template, (size_t)V * 3);
+#ifdef SFX_LAB
+    M.dirs = mem.up(T.dirs);
+#endif
+    M.dirsT = mem.up(T.dirsT); M.dirs_tiled = mem.up(T.dirs_tiled);
+    M.Wsp_j = mem.up(T.Wsp_j); M.Wsp_w = mem.up(T.Wsp_w);
+    M.jv_start = mem.up(T.jv_start); M.jv_vid = mem.up(T.jv_vid); M.jv_w = mem.up(T.jv_w);
+    M.W = mem.up(d->lbs_weights, (size_t)V * SFX_J);
+    M.tj_n = mem.up(T.tj_n); M.tj_list = mem.up(T.tj_list); M.tj_w = mem.up(T.tj_w);
+    M.J_template = mem.up(T.J_template); M.J_dirs = mem.up(T.J_dirs);
+    M.J_template64 = mem.up(T.J_template64); M.J_dirs64 = mem.up(T.J_dirs64);
+    M.comp_l = mem.up(d->hands_comp_l, (size_t)d->num_pca * SFX_NHAND); M.comp_r = mem.up(d->hands_comp_r, (size_t)d->num_pca * SFX_NHAND);
+    M.pose_mean = mem.up(d->pose_mean, SFX_POSE);
+    M.sj_start = mem.up(T.sj_start); M.sj_item = mem.up(T.sj_item); M.sj_w = mem.up(T.sj_w);
+    M.dj_start = mem.up(T.dj_start); M.dj_item = mem.up(T.dj_item); M.dj_w = mem.up(T.dj_w);
+    M.dynp_vid = mem.up(T.dynp_vid); M.dynp_w = mem.up(T.dynp_w); M.dynp_vt = mem.up(T.dynp_vt);
+    M.dynp_wj = mem.up(T.dynp_wj); M.dynp_ww = mem.up(T.dynp_ww);
+    M.dynp_js = T.dynp_js.empty() ? nullptr : mem.up(T.dynp_js);
+    M.dynp_ji = mem.up(T.dynp_ji); M.dynp_jw = mem.up(T.dynp_jw);
+    M.item_vid = mem.up(T.item_vid); M.item_w = mem.up(T.item_w);
+    M.item_vt = mem.up(T.item_vt); M.item_wj = mem.up(T.item_wj); M.item_ww = mem.up(T.item_ww);
+    M.dynp_us = T.dynp_us.empty() ? nullptr : mem.up(T.dynp_us);
+    M.vslot = mem.up(T.vslot); M.item_uslot = mem.up(T.item_uslot);
+    M.meta = mem.up(T.meta);
+    m->meta_host = std::move(T.meta); m->faces_host = std::move(T.faces);
+    if (mem.failed) { (void)hipGetLastError(); sfx_set_error("out of device memory (model constants)"); return -2; }
     if (hipDeviceSynchronize() != hipSuccess) { sfx_set_error("model upload failed"); return -2; }
     *out = m.release();
     return 0;

@@ -87,18 +87,27 @@ struct StageW64 {     // the same in double: the float64 mode (sfx_batch_cfg.hig
     double bpw, sw, bend, hpw, epw, jaw[3], hand_jw, face_jw, coll;
 };
 
+// The kernels take DevModel by value.  How the compiler groups their scalar argument loads -- and with it the SGPR spills and
+// scratch of the persistent kernels (k_tick_dense, k_fit_rows, k_closure) -- follows the members' offsets, so the members that
+// were dropped because nothing reads them (their tables are neither built nor uploaded any more) leave their bytes behind as
+// gap*_: every live member stays at the offset the kernels were tuned with, and the kernels compile to the same code.  Closing
+// the gaps was measured: other spill counts in eight kernels, scratch 68 -> 100 B in k_tick_dense, body fit -0.3 %.
 struct DevModel {
-    int V, F, S, P, KD, K;            // S = NB+NE, P = 486, KD = S+P
-    int n_extra, n_lmk, n_dyn_rows, n_dyn;
-    int n_levels, n_rounds;           // tree depth + 1; ceil(log2(n_levels)) pointer-jumping rounds
-    int level_start[SFX_MAX_LEVELS + 1];
+    int V, gap0_, S, gap1_[2], K;     // S = NB+NE (blend-shape depth KD = S + 486 <= SFX_KD_PAD)
+    int gap2_[3], n_dyn;
+    int gap3_, n_rounds;              // ceil(log2(tree depth + 1)) pointer-jumping rounds
+    int gap4_[SFX_MAX_LEVELS + 1];
     // constants
     const float* v_template;   // [V][3]
-    const float* dirs;         // [KD_PAD][3*Vpad]  k-major, coords interleaved (the adjoint GEMM's operand)
-    const float* dirs_tiled;   // [Vpad/16][KD_PAD][48]  the same matrix, one contiguous block per 16-vertex tile (dense GEMM B operand)
+#ifdef SFX_LAB
+    const float* dirs;         // [KD_PAD][3*Vpad]  k-major, coords interleaved (only the lab build's 32-frame dense GEMM reads it)
+#else
+    const void*  gap5_;
+#endif
+    const float* dirs_tiled;   // [Vpad/16][KD_PAD][48]  the same matrix, one contiguous block per 16-vertex tile (B operand of the dense and the adjoint GEMM)
     const float* dirsT;        // [V][3][KD_PAD] vertex-major (needed-rows path)
     const float* W;            // [V][J]
-    const float* WT;           // [JPAD][Vpad]   (dense skinning GEMM B operand)
+    const void*  gap6_;
     // dense skinning GEMM, compressed per 16-vertex tile to the joints that carry weight there
     const int*   tj_n;         // [ntile16] joints used by the tile, padded to a multiple of 4 (<= JPAD)
     const int*   tj_list;      // [ntile16][JPAD] joint ids (padding: joint 0 with zero weights)
@@ -110,21 +119,12 @@ struct DevModel {
     const float* Wsp_w;        // [V][SFX_NW]
     const float* J_template;   // [J][3]
     const float* J_dirs;       // [J][3][S]
-    const int*   parents;      // [J]
-    const int*   level_joints; // [J] joints ordered by tree depth
-    const int*   child_start;  // [J+1]
-    const int*   child_list;   // [J-1]
+    const void*  gap7_[4];
     const float* comp_l;       // [NPCA][45]
     const float* comp_r;
     const float* pose_mean;    // [165]
-    const int*   faces;        // [F][3]
-    const int*   dyn_faces;    // [rows][n_dyn]
-    const float* dyn_bary;     // [rows][n_dyn][3]
-    // mapped-joint description
-    const int*   jk_type;      // [K] 0 = kinematic joint, 1 = vertex items
-    const int*   jk_src;       // [K] joint id (type 0)
-    const int*   jk_item0;     // [K] first item (type 1)
-    const int*   jk_nitem;     // [K]
+    const void*  gap8_[7];
+    // mapped joints: their description (kinematic joint | vertex items, item owners) and the tree are in meta
     int n_items, n_static_items;
     int n_uniq;                // distinct vertices of the static items: the dense GEMM exports their v_posed and T
     const int* vslot;          // [Vpad] vertex -> index into the export arrays, or -1
@@ -134,10 +134,7 @@ struct DevModel {
     const float* item_vt;      // [n_items][3] v_template row of the item's vertex     } gathered copies for the static items:
     const int*   item_wj;      // [n_items][SFX_NW] = Wsp_j[item_vid]                  } one round trip at kernel entry
     const float* item_ww;      // [n_items][SFX_NW] = Wsp_w[item_vid]                  }
-    const int*   item_dyn;     // [n_items] -1, or (landmark*3 + corner) of the dynamic LUT
-    const int*   item_k;       // [n_items] owning mapped joint
-    const int*   src_k0;       // [J+1] CSR: mapped joints that read kinematic joint s
-    const int*   src_klist;    // [..]
+    const void*  gap9_[4];
     int Vpad;
     // per-joint lists of (item, skinning weight): static items, and dynamic items per LUT row
     const int *sj_start, *sj_item; const float* sj_w;      // [J+1], [..]
@@ -155,7 +152,7 @@ struct DevModel {
     const float* dynp_jw;      // [rows][nd*SFX_NW]
     const int*   dynp_us;      // [rows][nd]      export index of the item's vertex in the dense GEMM's uvp (nullptr: no dynamic items)
     int n_sj;                  // entries of sj_item / sj_w
-    const int*   meta;         // [SFX_META_N] packed copy of the tables above
+    const int*   meta;         // [SFX_META_N] the MO_* tables: tree, mapped joints, item owners
     // VPoser decoder
     int vp_latent, vp_hidden;
     const float *vp_w1, *vp_b1, *vp_w2, *vp_b2, *vp_w3, *vp_b3;      // [512][L], [512][512], [126][512]

@@ -556,10 +556,11 @@ def test_long_queue_through_a_small_column_pool(synth_model):
 
 
 def test_a_refused_model_keeps_no_device_memory(synth_model, cfg_body):
-    """sfx_model_create refuses a joint_map entry out of range AFTER it has uploaded the blend-shape arrays (dirs, dirsT,
-    dirs_tiled: most of a model at any vertex count).  A refusal is an ordinary error return and must hand back everything
-    it took: eight of them in a row leave free device memory within m / 2 of where it was, m being what one successful model
-    occupies (a library that kept the uploads would lose several m; m / 2 is room for the allocator's own caching)."""
+    """sfx_model_create derives every table of a model on the host (csrc/model_tables.h) and refuses a bad descriptor -- here
+    a joint_map entry out of range -- there, BEFORE its first device allocation: a refused descriptor never touches the device.
+    Eight refusals in a row leave free device memory within m / 2 of where it was, m being what one successful model
+    occupies (a library that uploaded first and kept the uploads would lose several m; m / 2 is room for the allocator's own
+    caching)."""
     from smplifyx_amd import _capi
     import gc
     gc.collect()                                # (handles that earlier tests left to the collector go now, not in between)
