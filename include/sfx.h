@@ -88,6 +88,28 @@ int  sfx_lbs_forward(sfx_model* m, int32_t B,
                      float* full_pose_out_dev,         /* [B][3J]    or NULL */
                      void* stream);
 
+/* ---- backward pass of the stand-alone LBS ------------------------------------------------
+ * Replaces autograd through smplx.SMPLX.forward / smplx.lbs.lbs (what `loss.backward()` walks in any
+ * objective written on body_model(...).vertices / .joints): the gradient of
+ *     sum(dvertices * vertices) + sum(djoints * joints)
+ * with respect to the nine inputs of sfx_lbs_forward, for B meshes at once.  All pointers are DEVICE
+ * pointers to contiguous fp32.  The call is stateless: it takes the nine inputs again and re-evaluates
+ * the forward at them (the price of a vertex gradient is one more dense GEMM than a backward that kept
+ * state would run), so nothing depends on which sfx_lbs_forward came before.  Either upstream may be
+ * NULL (= zero); both NULL is an error (-1).  With dvertices NULL no GEMM runs in either direction.
+ * Any output may be NULL.  The buffers of this path are allocated by its first call (-2: out of device
+ * memory; the model keeps serving sfx_lbs_forward).  No gradient flows through the dynamic-contour
+ * look-up (as in the reference); fp32 arithmetic, keypoint forward in fp64 as everywhere in the library. */
+int  sfx_lbs_backward(sfx_model* m, int32_t B,
+                      const float* global_orient_dev, const float* body_pose_dev, const float* betas_dev,
+                      const float* expression_dev, const float* jaw_dev, const float* leye_dev, const float* reye_dev,
+                      const float* lhand_dev, const float* rhand_dev,           /* as sfx_lbs_forward */
+                      const float* dvertices_dev,       /* [B][V][3] or NULL */
+                      const float* djoints_dev,         /* [B][K][3] or NULL */
+                      float* d_global_orient_dev, float* d_body_pose_dev, float* d_betas_dev, float* d_expression_dev,
+                      float* d_jaw_dev, float* d_leye_dev, float* d_reye_dev, float* d_lhand_dev, float* d_rhand_dev,
+                      void* stream);
+
 /* ---- a batch of independent frames -------------------------------------------------------
  * Replaces, for B frames at once, the objects fit_single_frame() wires together
  * (fit_single_frame.py:413-445: create_loss('camera_init'), create_loss('smplify'),

@@ -78,6 +78,8 @@ SYMBOLS = {
     "sfx_model_set_parts": (C.c_int, [C.c_void_p, i32p, i32p, i32p, C.c_int32]),
     "sfx_model_set_vposer": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [f32p] * 6),
     "sfx_lbs_forward": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 12 + [C.c_void_p]),
+    # model, B, nine inputs, dvertices, djoints, nine gradients, stream
+    "sfx_lbs_backward": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 20 + [C.c_void_p]),
     "sfx_batch_create": (C.c_int, [C.c_void_p, C.POINTER(BatchCfg), C.POINTER(StageWeights), C.POINTER(C.c_void_p)]),
     "sfx_batch_destroy": (None, [C.c_void_p]),
     "sfx_batch_set_frames": (C.c_int, [C.c_void_p] + [f32p] * 5),

@@ -180,6 +180,11 @@ struct sfx_batch {
     StageW64* sw64_dev = nullptr; // [n_stages] its stage weights
     DevAlloc trace_mem;           // D.trace / D.trace_n (sfx_batch_trace)
     long long* dbg_buf = nullptr; // [64] clock buffer of the lab build (sfx_debug_clocks attaches it as D.dbg), owned by mem
+    // sfx_lbs_backward (the model's forward batch only), allocated by its first call and owned by mem: the parameter block's
+    // gradient, and -- first call with a vertex gradient -- what the adjoint of a gradient on every vertex needs.  They are NOT
+    // attached to D: the forward keeps launching what it launched (a non-NULL D.vposed makes the dense GEMM write it).
+    float* bwd_gc = nullptr;      // [B][SFX_NPAR_MAX]
+    struct { float *vposed, *adj_G, *adj_part, *dfeat, *dA; int* want; } bwd = {};      // as BatchDev's members of the interpenetration term
     ~sfx_batch() {
         for (auto& kv : pen_graphs) hipGraphExecDestroy(kv.second);
         if (cap_stream) hipStreamDestroy(cap_stream);
@@ -1393,12 +1398,8 @@ __global__ void k_pack_params(BatchDev D, const float* go, const float* bp, cons
     cp(L.expr, L.NE, expr); cp(L.jaw, 3, jaw); cp(L.leye, 3, leye); cp(L.reye, 3, reye); cp(L.emb, 63, bp);
 }
 
-extern "C" int sfx_lbs_forward(sfx_model* m, int32_t B, const float* go, const float* bp, const float* betas,
-                               const float* expr, const float* jaw, const float* leye, const float* reye,
-                               const float* lh, const float* rh, float* verts_out, float* joints_out,
-                               float* full_pose_out, void* stream) {
-    if (!m) { sfx_set_error("null model"); return -1; }
-    hipStream_t s = (hipStream_t)stream;
+// the batch behind sfx_lbs_forward / sfx_lbs_backward: made for the first call, remade when B changes
+static int fwd_batch(sfx_model* m, int32_t B) {
     if (!m->fwd || m->fwd_B != B) {
         sfx_batch_destroy(m->fwd);
         m->fwd = nullptr; m->fwd_B = 0;      // (sfx_batch_create writes its result only on success)
@@ -1408,11 +1409,82 @@ extern "C" int sfx_lbs_forward(sfx_model* m, int32_t B, const float* go, const f
         if (rc) return rc;
         m->fwd_B = B;
     }
+    return 0;
+}
+
+extern "C" int sfx_lbs_forward(sfx_model* m, int32_t B, const float* go, const float* bp, const float* betas,
+                               const float* expr, const float* jaw, const float* leye, const float* reye,
+                               const float* lh, const float* rh, float* verts_out, float* joints_out,
+                               float* full_pose_out, void* stream) {
+    if (!m) { sfx_set_error("null model"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = fwd_batch(m, B)) return rc;
     sfx_batch* b = m->fwd;
     hipLaunchKernelGGL(k_pack_params, dim3(B), dim3(64), 0, s, b->D, go, bp, betas, expr, jaw, leye, reye, lh, rh);
     int rc = sfx_batch_forward(b, verts_out, joints_out, s);
     if (rc) return rc;
     if (full_pose_out) SFX_CHECK(hipMemcpyAsync(full_pose_out, b->D.fullpose, (size_t)B * SFX_POSE * 4, hipMemcpyDeviceToDevice, s));
     SFX_CHECK(hipStreamSynchronize(s));
+    return 0;
+}
+
+// Buffers of sfx_lbs_backward, on first use.  All of a group or none: a failed group is released at once, the batch keeps what
+// it had and stays usable (forward, and a backward that needs less).
+static int bwd_buffers(sfx_batch* b, bool verts) {
+    const int B = b->D.cfg.B; const DevModel& M = b->m->M;
+    if (!b->bwd_gc) {
+        DevAlloc fresh;
+        float* gc = fresh.zeros<float>((size_t)B * SFX_NPAR_MAX);
+        if (fresh.failed) { (void)hipGetLastError(); sfx_set_error("sfx_lbs_backward: out of device memory (%d meshes)", B); return -2; }
+        b->mem.ptrs.insert(b->mem.ptrs.end(), fresh.ptrs.begin(), fresh.ptrs.end()); fresh.ptrs.clear();
+        b->bwd_gc = gc;
+    }
+    if (verts && !b->bwd.adj_G) {
+        DevAlloc fresh;
+        auto w = b->bwd;
+        w.vposed = fresh.zeros<float>((size_t)B * M.V * 3);
+        w.adj_G = fresh.zeros<float>((size_t)b->D.Bpad * 3 * M.Vpad);
+        w.adj_part = fresh.zeros<float>((size_t)sfx_adj_slices(M) * SFX_KD_PAD * b->D.Bpad);
+        w.dfeat = fresh.zeros<float>((size_t)B * SFX_KD_PAD);
+        w.dA = fresh.zeros<float>((size_t)B * SFX_J * 12);
+        w.want = fresh.up(std::vector<int>((size_t)B, 1));      // every column carries a vertex gradient
+        if (fresh.failed) { (void)hipGetLastError(); sfx_set_error("sfx_lbs_backward: out of device memory (%d meshes)", B); return -2; }
+        b->mem.ptrs.insert(b->mem.ptrs.end(), fresh.ptrs.begin(), fresh.ptrs.end()); fresh.ptrs.clear();
+        b->bwd = w;
+    }
+    return 0;
+}
+
+extern "C" int sfx_lbs_backward(sfx_model* m, int32_t B, const float* go, const float* bp, const float* betas,
+                                const float* expr, const float* jaw, const float* leye, const float* reye,
+                                const float* lh, const float* rh, const float* dverts, const float* djoints,
+                                float* d_go, float* d_bp, float* d_betas, float* d_expr, float* d_jaw, float* d_leye,
+                                float* d_reye, float* d_lh, float* d_rh, void* stream) {
+    if (!m) { sfx_set_error("null model"); return -1; }
+    if (!dverts && !djoints) { sfx_set_error("sfx_lbs_backward: dvertices and djoints are both NULL (no upstream gradient)"); return -1; }
+    if (B <= 0) { sfx_set_error("sfx_lbs_backward: B=%d", B); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = fwd_batch(m, B)) return rc;
+    sfx_batch* b = m->fwd;
+    if (int rc = bwd_buffers(b, dverts != nullptr)) return rc;
+    const DevModel& M = m->M;
+    // stateless: the forward is evaluated again at the inputs of THIS call (nothing of an earlier sfx_lbs_forward is read)
+    hipLaunchKernelGGL(k_pack_params, dim3(B), dim3(64), 0, s, b->D, go, bp, betas, expr, jaw, leye, reye, lh, rh);
+    BatchDev D = b->D;       // (by value to every kernel: the adjoint's pointers are attached to this copy only)
+    ClosureArgs a{}; a.stage_override = 0; a.from_X = 1;
+    if (dverts) {
+        D.vposed = b->bwd.vposed; D.adj_G = b->bwd.adj_G; D.adj_part = b->bwd.adj_part; D.pen_dfeat = b->bwd.dfeat;
+        D.pen_dA = b->bwd.dA; D.pen_want = b->bwd.want; D.pen_dverts = const_cast<float*>(dverts);      // (only ever read)
+        ClosureArgs e{}; e.stage_override = 0; e.export_dense = 1; e.forward_only = 2; e.from_X = 1;
+        launch_closure(M, D, b->vl_dev, b->sw_dev, e, s);
+        { ProfScope p("lbs_dense", s, D.nact); launch_lbs_dense(M, D, s); }      // (writes v_posed of every vertex as well: D.vposed)
+        { ProfScope p("lbs_adjoint", s, D.nact); launch_adj_prep(M, D, s); launch_pen_adjoint(M, D, s); }
+        a.use_dense_verts = 1;
+    }
+    // joints only: no GEMM in either direction -- the keypoints' blend-shape rows are evaluated by the sweep's own forward
+    launch_closure_ext(M, D, b->vl_dev, b->sw_dev, a, djoints, dverts ? 1 : 0, b->bwd_gc, s);
+    launch_scatter_gc(D, b->bwd_gc, LbsGradOut{d_go, d_bp, d_betas, d_expr, d_jaw, d_leye, d_reye, d_lh, d_rh}, s);
+    SFX_CHECK(hipStreamSynchronize(s));
+    SFX_CHECK(hipGetLastError());
     return 0;
 }

@@ -328,18 +328,32 @@ __device__ __forceinline__ Real gmof_grad(Real r, Real rho2) {
     return 2.f * r * (rho2 / den) * (rho2 / den);
 }
 
+// Reverse sweep with a caller-supplied upstream (lbs_backward.hip: the backward pass of the stand-alone LBS).  Passed as the last
+// argument of closure_body it selects, at compile time, the form in which the loss section (priors, projection) is skipped: d joints
+// comes from `djoints`, the adjoint of a gradient on every vertex (lbs_adjoint.hip) is added with weight 1, and the gradient of
+// the parameter block (S.gc, SFX_NPAR_MAX layout) is the result.  NoUpstream (the default) is the fitting closure, whose
+// instantiations do not see any of it.
+struct NoUpstream {};
+struct ExtUpstream {
+    const float* djoints;   // [B][K][3] gradient on the mapped joints (NULL: zero)
+    int has_dverts;         // 1: D.pen_dfeat / D.pen_dA hold the adjoint of the caller's vertex gradient (column = frame)
+    float* gc;              // [B][SFX_NPAR_MAX] out: gradient with respect to the parameter block
+};
+
 // One closure evaluation of frame b by the whole workgroup (CT threads).  When `gflat` is not
 // NULL the flat gradient / loss are ALSO left in LDS (gflat[NVAR_MAX], *fout) for a consumer in
 // the same workgroup (fused kernels).
 // Real = LDS::real_t: float, or double in the float64 mode (FrameLDSSmall64 with StageW64 weights; body-only needed-rows
 // path: the dense export, VPoser, the GMM prior and the interpenetration term are fp32-only and refused by api.hip).
-template <class LDS, class SW>
+template <class LDS, class SW, class EXT = NoUpstream>
 __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const BatchDev& D,
                                              const VarList* __restrict__ vls, const SW* __restrict__ sws,
                                              const ClosureArgs& args, const int b, typename LDS::real_t* gflat,
-                                             typename LDS::real_t* fout) {
+                                             typename LDS::real_t* fout, const EXT& ext = EXT{}) {
     using Real = typename LDS::real_t;
     constexpr bool F64 = std::is_same<Real, double>::value;
+    constexpr bool kExt = !std::is_same<EXT, NoUpstream>::value;
+    static_assert(!kExt || !F64, "the external-upstream sweep is fp32");
     constexpr int CT = LDS::kThreads;
     const int t = threadIdx.x;
     const int lane = t & 63, wv = t >> 6;
@@ -347,16 +361,16 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
     const BatchCfgDev& C = D.cfg;
 
     const int stage = __builtin_amdgcn_readfirstlane((args.stage_override != -2) ? args.stage_override : D.stage[b]);
-    if (stage >= C.n_stages && !args.forward_only) return;      // frame finished
+    if constexpr (!kExt) { if (stage >= C.n_stages && !args.forward_only) return; }     // frame finished (a forward batch has no stages)
     const bool cam_stage = (stage < 0);
-    const SW sw = (cam_stage || args.forward_only) ? SW{} : sws[stage];     // (11 scalars, requested here: the loss section is 20 k cycles away)
+    const SW sw = (kExt || cam_stage || args.forward_only) ? SW{} : sws[stage];     // (11 scalars, requested here: the loss section is 20 k cycles away)
 
     // Live keypoints of this evaluation.  Keypoints are ordered body | hands | face (+ contour) and the vertex items follow
     // that order; a stage whose hand / face joint weight is zero (fit_single_frame.py:569-572: the first three of the five
     // stages of fit_smplx_smplifyx.yaml) multiplies everything those keypoints produce by zero -- loss terms and gradients
     // alike -- so their vertex rows, skinning, projection and adjoint lists are not walked at all (exact: the skipped terms
     // are zeros).  Forward-only passes and the camera stage keep every keypoint.
-    const int cls = (cam_stage || args.forward_only) ? 2 : ((sw.face_jw != 0.f) ? 2 : ((sw.hand_jw != 0.f) ? 1 : 0));
+    const int cls = (kExt || cam_stage || args.forward_only) ? 2 : ((sw.face_jw != 0.f) ? 2 : ((sw.hand_jw != 0.f) ? 1 : 0));
     const int KL = __builtin_amdgcn_readfirstlane(cls == 2 ? M.K : C.kl[cls]);             // keypoints < KL are live
     const int NIL = __builtin_amdgcn_readfirstlane(cls == 2 ? M.n_items : C.nil[cls]);     // items < NIL belong to them
 
@@ -778,6 +792,12 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
         return;
     }
 
+    Real total = 0.f;
+  if constexpr (kExt) {
+    // external upstream: no loss section; d joints is the caller's (every keypoint is live: cls = 2)
+    for (int w = t; w < K * 3; w += CT) S.dj[w] = ext.djoints ? ext.djoints[(size_t)b * K * 3 + w] : 0.f;
+    __syncthreads();
+  } else {
     MARK(8);
     // ------------------------------------------------------------------ losses
     // per-frame data was prefetched into LDS (S.fd) at kernel entry; all sums of this section go
@@ -927,7 +947,6 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
         }
     }
     MARK(23);
-    Real total;
     if (cam_stage) {
         Real joint = q[Q_L];
         if (C.use_conf_cam) joint *= csum;
@@ -954,6 +973,7 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
         if (t < 3) S.gc[L.cam_t + t] = (t == 0) ? q[Q_D0] : (t == 1) ? q[Q_D1] : q[Q_D2];
     }
     __syncthreads();
+  }   // !kExt
 
     MARK(9);
     // ------------------------------------------------------------------ reverse sweep
@@ -1099,6 +1119,15 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
     items_dfeat(NI, false);
     // ---- interpenetration: its gradient lives on every vertex; lbs_adjoint.hip has already taken it
     // back to feat and to the skinning transforms (adjoint GEMM), the chain adjoint below does the rest
+    if constexpr (kExt) {
+        if (ext.has_dverts) {      // the caller's vertex gradient, taken back by the adjoint GEMM: weight 1
+            const float* pf = D.pen_dfeat + (size_t)D.slot[b] * SFX_KD_PAD;
+            const float* pa = D.pen_dA + (size_t)D.slot[b] * SFX_J * 12;
+            for (int k = t; k < SFX_KD_PAD; k += CT) S.dfeat[k] += pf[k];
+            for (int w = t; w < SFX_J * 12; w += CT) S.dA[w] += pa[w];
+            __syncthreads();
+        }
+    } else
     if (!F64 && C.pen && args.use_dense_verts && !cam_stage && sw.coll > 0.f) {
         const int slot = D.slot[b];
         const float* pf = D.pen_dfeat + (size_t)slot * SFX_KD_PAD;
@@ -1240,6 +1269,10 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
     __syncthreads();
     MARK(15);
     if constexpr (HAS_VP) if (C.use_vposer) vposer_backward<CT>(S.V, M, &S.dpose[3], &S.gc[L.emb], S.T);   // d body_pose -> d latent
+    if constexpr (kExt) {       // the parameter block's gradient itself: a forward batch has no stage, hence no variable list
+        for (int i = t; i < SFX_NPAR_MAX; i += CT) ext.gc[(size_t)b * SFX_NPAR_MAX + i] = S.gc[i];
+        return;
+    }
     const VarList& vl = vls[cam_stage ? 0 : 1];
     if constexpr (F64) {
         double* gout = D.g64 + (size_t)b * SFX_NVAR_MAX;

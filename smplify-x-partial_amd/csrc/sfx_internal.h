@@ -324,6 +324,14 @@ struct PenAdjPrep {
     int Bpad, Vpad;
 };
 void launch_pen_adjoint(const DevModel& M, const BatchDev& D, hipStream_t s);
+// backward pass of the stand-alone LBS (lbs_backward.hip; sfx_lbs_backward): the adjoint GEMM's operand from a vertex gradient the
+// caller supplies (D.pen_dverts -> D.adj_G), the reverse sweep with external upstream (result: the gradient of the parameter
+// block, gc [B][SFX_NPAR_MAX]) and its scatter to the nine named gradients
+struct LbsGradOut { float *go, *bp, *betas, *expr, *jaw, *leye, *reye, *lh, *rh; };      // device pointers, any may be NULL
+void launch_adj_prep(const DevModel& M, const BatchDev& D, hipStream_t s);
+void launch_closure_ext(const DevModel& M, const BatchDev& D, const VarList* vl_dev, const StageW* sw_dev, const ClosureArgs& a,
+                        const float* djoints, int has_dverts, float* gc, hipStream_t s);
+void launch_scatter_gc(const BatchDev& D, const float* gc, const LbsGradOut& o, hipStream_t s);
 int sfx_adj_slices(const DevModel& M);
 void launch_lbs_dense(const DevModel& M, const BatchDev& D, hipStream_t s);
 #ifdef SFX_LAB

@@ -179,6 +179,42 @@ class DeviceModel(object):
         capi.check(self._lib.sfx_lbs_forward(self._h, B, *[ptr(t) for t in ins], ptr(verts), ptr(joints), ptr(fp), s))
         return verts, joints, fp
 
+    # the nine inputs of lbs_forward / lbs_backward under the reference's parameter names, in the C ABI's order
+    LBS_INPUTS = ("global_orient", "body_pose", "betas", "expression", "jaw_pose", "leye_pose", "reye_pose",
+                  "left_hand_pose", "right_hand_pose")
+
+    def lbs_backward(self, global_orient, body_pose, betas, expression, jaw_pose, leye_pose, reye_pose,
+                     left_hand_pose, right_hand_pose, dvertices=None, djoints=None, stream=None):
+        """Gradient of sum(dvertices * vertices) + sum(djoints * joints) with respect to the nine inputs of lbs_forward
+        (sfx_lbs_backward: what autograd through smplx.SMPLX.forward returns in the reference's ecosystem).  Stateless: the
+        inputs are given again and the forward is re-evaluated at them.  dvertices [B][V][3] / djoints [B][K][3] are torch CUDA
+        tensors, either may be None (joints only: no GEMM runs), not both.  Returns {name: float32 CUDA tensor} keyed by the
+        reference's parameter names (LBS_INPUTS)."""
+        import torch
+        if dvertices is None and djoints is None:
+            raise ValueError("lbs_backward needs an upstream gradient: dvertices, djoints or both")
+        B = global_orient.shape[0]
+        dev = global_orient.device
+        ins = [t.detach().to(dev, torch.float32).contiguous() for t in
+               (global_orient, body_pose, betas, expression, jaw_pose, leye_pose, reye_pose, left_hand_pose, right_hand_pose)]
+        ins[1] = ins[1].reshape(B, -1)
+        want = (3, 63, self.num_betas, self.num_expr, 3, 3, 3, self.num_pca, self.num_pca)
+        for name, t, n in zip(self.LBS_INPUTS, ins, want):
+            if tuple(t.shape) != (B, n):
+                raise ValueError("%s: shape %s, expected %s" % (name, tuple(t.shape), (B, n)))
+        ups = []
+        for name, t, shape in (("dvertices", dvertices, (B, self.V, 3)), ("djoints", djoints, (B, self.K, 3))):
+            if t is not None:
+                if tuple(t.shape) != shape:
+                    raise ValueError("%s: shape %s, expected %s" % (name, tuple(t.shape), shape))
+                t = t.detach().to(dev, torch.float32).contiguous()
+            ups.append(t)
+        outs = [torch.empty_like(t) for t in ins]
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        s = C.c_void_p(stream if stream is not None else torch.cuda.current_stream().cuda_stream)
+        capi.check(self._lib.sfx_lbs_backward(self._h, B, *[ptr(t) for t in ins + ups + outs], s))
+        return dict(zip(self.LBS_INPUTS, outs))
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.sfx_model_destroy(self._h)

@@ -2,9 +2,11 @@
 (reference call sites smplifyx/main.py:109-127, fitting.py:82,248, fit_single_frame.py:274,
 551,611, camera.py:27): `create()`, `SMPLX` with `.parameters()`, `.reset_params()`,
 `.forward(return_verts, body_pose, return_full_pose)`, `.faces_tensor`, `.faces`, and
-`lbs.transform_mat`.  The forward is the HIP dense-LBS path of libsfx.so; torch tensors are
-containers only (no autograd graph: gradients come from the engine's hand-written adjoint,
-see fitting.py).  Model file keys: SURVEY.md appendix A.1.
+`lbs.transform_mat`.  The forward is the HIP dense-LBS path of libsfx.so; by default torch tensors
+are containers only (no autograd graph: the fitting gradients come from the engine's hand-written
+adjoint, see fitting.py).  `SMPLX(..., differentiable=True)` returns vertices and joints WITH a graph:
+their backward is the engine's sfx_lbs_backward, so any torch loss written on them reaches the
+parameters.  Model file keys: SURVEY.md appendix A.1.
 """
 import os
 import types
@@ -40,6 +42,31 @@ def _transform_mat(R, t):
 lbs = types.SimpleNamespace(transform_mat=_transform_mat)
 
 
+class _LBS(torch.autograd.Function):
+    """vertices, joints = LBS(nine inputs) with the engine on both sides: forward = sfx_lbs_forward, backward =
+    sfx_lbs_backward at the SAVED inputs (the engine call is stateless, so forwards made in between change nothing).
+    First derivatives only (once_differentiable); full_pose carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, dm, return_verts, *ins):
+        ins = [t.detach() for t in ins]
+        verts, joints, full_pose = dm.lbs_forward(*ins, return_verts=return_verts, return_full_pose=True)
+        ctx.dm = dm
+        ctx.save_for_backward(*ins)
+        ctx.set_materialize_grads(False)        # an output the loss does not use stays None: joints only = no GEMM
+        ctx.mark_non_differentiable(full_pose)
+        return verts, joints, full_pose
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dverts, djoints, _dfull_pose):
+        if dverts is None and djoints is None:
+            return (None,) * 11
+        g = ctx.dm.lbs_backward(*ctx.saved_tensors, dvertices=dverts, djoints=djoints)
+        grads = [g[name].reshape(t.shape) for name, t in zip(engine.DeviceModel.LBS_INPUTS, ctx.saved_tensors)]
+        return (None, None) + tuple(gi if need else None for gi, need in zip(grads, ctx.needs_input_grad[2:]))
+
+
 class SMPLX(nn.Module):
     NUM_JOINTS = 54
     NUM_BODY_JOINTS = 21
@@ -49,7 +76,7 @@ class SMPLX(nn.Module):
                  create_expression=True, create_jaw_pose=True, create_leye_pose=True, create_reye_pose=True,
                  create_transl=False, dtype=torch.float32, batch_size=1, use_pca=True, num_pca_comps=6,
                  flat_hand_mean=False, num_betas=10, num_expression_coeffs=10, use_face_contour=False,
-                 gender="neutral", ext="npz", vposer=None, **kwargs):
+                 gender="neutral", ext="npz", vposer=None, differentiable=False, **kwargs):
         super().__init__()
         if dtype not in (torch.float32, torch.float64):
             raise ValueError("Unknown float type {}".format(dtype))
@@ -70,6 +97,11 @@ class SMPLX(nn.Module):
         self._model_data = data
         self.dtype = dtype
         self.batch_size = batch_size
+        # differentiable=False (default): inputs are detached, outputs carry no graph (the fitting path differentiates its own
+        # objective on the device).  True: forward returns `vertices` and `joints` with an autograd graph whose backward is the
+        # engine's sfx_lbs_backward -- gradients reach the module's own parameters (arguments left out) or the caller's tensors
+        # (arguments given).  full_pose, the hand poses and the echoed inputs of the output stay detached either way.
+        self.differentiable = bool(differentiable)
         self.use_pca, self.num_pca_comps = use_pca, num_pca_comps
         self.num_betas, self.num_expression_coeffs = num_betas, num_expression_coeffs
         self.use_face_contour, self.flat_hand_mean = use_face_contour, flat_hand_mean
@@ -127,6 +159,9 @@ class SMPLX(nn.Module):
         dev = self.faces_tensor.device
         if dev.type != "cuda":
             raise RuntimeError("move the model to the GPU first (.to('cuda')): no CPU fallback")
+        if self.differentiable:
+            return self._forward_differentiable(dm, dev, betas, global_orient, body_pose, left_hand_pose, right_hand_pose,
+                                                expression, jaw_pose, leye_pose, reye_pose, return_verts, return_full_pose)
         pick = lambda v, name, n: (v.detach() if v is not None else self._p(name, n, dev)).to(dev, torch.float32)
         go = pick(global_orient, "global_orient", 3)
         bp = pick(body_pose, "body_pose", 63).reshape(go.shape[0], -1)
@@ -148,6 +183,36 @@ class SMPLX(nn.Module):
                            left_hand_pose=full_pose[:, 75:120] - torch.as_tensor(dm_pose_mean(self, 75), device=dev, dtype=full_pose.dtype),
                            right_hand_pose=full_pose[:, 120:165] - torch.as_tensor(dm_pose_mean(self, 120), device=dev, dtype=full_pose.dtype),
                            jaw_pose=jw)
+        out._model, out._inputs = self, inputs
+        return out
+
+    def _forward_differentiable(self, dm, dev, betas, global_orient, body_pose, left_hand_pose, right_hand_pose, expression,
+                                jaw_pose, leye_pose, reye_pose, return_verts, return_full_pose):
+        """forward of a module made with differentiable=True: the same engine forward behind torch.autograd (_LBS)."""
+        def pick(v, name, n):       # the caller's tensor, else the module's own parameter: NOT detached (float64: cast in, grads cast back)
+            if v is None:
+                v = getattr(self, name, None)
+            if v is None:
+                v = torch.zeros([self.batch_size, n], dtype=self.dtype, device=dev)
+            return v.to(dev, torch.float32)
+        go = pick(global_orient, "global_orient", 3)
+        bp = pick(body_pose, "body_pose", 63).reshape(go.shape[0], -1)
+        be = pick(betas, "betas", self.num_betas)
+        ex = pick(expression, "expression", self.num_expression_coeffs)
+        jw, le, re = pick(jaw_pose, "jaw_pose", 3), pick(leye_pose, "leye_pose", 3), pick(reye_pose, "reye_pose", 3)
+        lh = pick(left_hand_pose, "left_hand_pose", self.num_pca_comps)
+        rh = pick(right_hand_pose, "right_hand_pose", self.num_pca_comps)
+        verts, joints, full_pose = _LBS.apply(dm, return_verts, go, bp, be, ex, jw, le, re, lh, rh)
+        cast = lambda x: x.to(self.dtype) if x is not None else None
+        verts, joints, full_pose = cast(verts), cast(joints), cast(full_pose)
+        be, go, bp, ex, jw = (cast(x.detach()) for x in (be, go, bp, ex, jw))
+        le, re, lh, rh = le.detach(), re.detach(), lh.detach(), rh.detach()
+        inputs = dict(global_orient=go, body_pose=bp, betas=be, expression=ex, jaw_pose=jw, leye_pose=le, reye_pose=re,
+                      left_hand_pose=lh, right_hand_pose=rh)
+        pm = lambda start: torch.as_tensor(dm_pose_mean(self, start), device=dev, dtype=full_pose.dtype)
+        out = ModelOutput(vertices=verts, joints=joints, full_pose=full_pose if return_full_pose else None, betas=be,
+                          global_orient=go, body_pose=bp, expression=ex, left_hand_pose=full_pose[:, 75:120] - pm(75),
+                          right_hand_pose=full_pose[:, 120:165] - pm(120), jaw_pose=jw)
         out._model, out._inputs = self, inputs
         return out
 
