@@ -65,6 +65,27 @@ int  sfx_model_set_vposer(sfx_model* m, int32_t latent, int32_t hidden,
                           const float* fc2_w, const float* fc2_b,
                           const float* out_w, const float* out_b);
 
+/* ---- stand-alone VPoser decoder ---------------------------------------------------------
+ * Replaces `vposer.decode(pose_embedding, output_type='aa')` of human_body_prior (cvpr19) wherever the reference calls it
+ * outside the fitting closure (fitting.py:72,197,236, fit_single_frame.py:265,515,607,620,654, render_pkl.py:97) and what
+ * autograd walks behind it, for B latents at once.  The handle is independent of any sfx_model, as the reference's `vposer`
+ * is independent of `body_model`.  Weights are HOST pointers in the layouts of sfx_model_set_vposer and are refused like
+ * there (hidden 512, latent a multiple of 4 and <= 60), before any device memory is touched.  decode / decode_backward take
+ * DEVICE pointers to contiguous fp32 and only ENQUEUE on `stream`: they do not synchronise, allocate nothing and use no
+ * scratch; B = 0 returns 0 without a launch.  decode_backward is stateless: it takes z again and re-evaluates the forward;
+ * dz = d sum(dbody * body_pose) / d z.  A frame's result depends on its own latent only, bit for bit (not on B or its
+ * position in the batch).                                                                  */
+typedef struct sfx_vposer sfx_vposer;
+int  sfx_vposer_create(int32_t latent, int32_t hidden,
+                       const float* fc1_w, const float* fc1_b,
+                       const float* fc2_w, const float* fc2_b,
+                       const float* out_w, const float* out_b, sfx_vposer** out);
+void sfx_vposer_destroy(sfx_vposer* v);
+int  sfx_vposer_decode(sfx_vposer* v, int32_t B, const float* z_dev /* [B][latent] */,
+                       float* body_pose_dev /* [B][63] */, void* stream);
+int  sfx_vposer_decode_backward(sfx_vposer* v, int32_t B, const float* z_dev /* [B][latent] */,
+                                const float* dbody_dev /* [B][63] */, float* dz_dev /* [B][latent] */, void* stream);
+
 /* ---- stand-alone LBS forward ----------------------------------------------------------
  * Replaces body_model(return_verts=True, body_pose=..., return_full_pose=True)
  * (fitting.py:82,248; fit_single_frame.py:611).  All pointers are DEVICE pointers to

@@ -77,6 +77,10 @@ SYMBOLS = {
     "sfx_model_destroy": (None, [C.c_void_p]),
     "sfx_model_set_parts": (C.c_int, [C.c_void_p, i32p, i32p, i32p, C.c_int32]),
     "sfx_model_set_vposer": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [f32p] * 6),
+    "sfx_vposer_create": (C.c_int, [C.c_int32, C.c_int32] + [f32p] * 6 + [C.POINTER(C.c_void_p)]),
+    "sfx_vposer_destroy": (None, [C.c_void_p]),
+    "sfx_vposer_decode": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sfx_vposer_decode_backward": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sfx_lbs_forward": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 12 + [C.c_void_p]),
     # model, B, nine inputs, dvertices, djoints, nine gradients, stream
     "sfx_lbs_backward": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 20 + [C.c_void_p]),

@@ -5,6 +5,7 @@
 #include "../../include/sfx.h"
 #include "sfx_internal.h"
 #include "model_tables.h"
+#include "vposer_pack.h"
 
 #include <algorithm>
 #include <chrono>
@@ -291,19 +292,16 @@ extern "C" int sfx_model_set_parts(sfx_model* m, const int32_t* segm, const int3
 extern "C" int sfx_model_set_vposer(sfx_model* m, int32_t latent, int32_t hidden, const float* w1, const float* b1,
                                     const float* w2, const float* b2, const float* w3, const float* b3) {
     if (!m) { sfx_set_error("null model"); return -1; }
-    if (hidden != 512 || latent < 4 || latent > 60 || latent % 4) {
-        sfx_set_error("VPoser v1 decoder expected (hidden 512, latent a multiple of 4 <= 60), got %d/%d", latent, hidden); return -1; }
+    if (!vposer_shape_ok(latent, hidden)) return -1;
     auto v = [](const float* p, size_t n) { return std::vector<float>(p, p + n); };
     const int H = hidden, L = latent;
-    std::vector<float> w1T((size_t)L * H), w2T((size_t)H * H), w3T((size_t)H * 128, 0.f);
-    for (int o = 0; o < H; ++o) for (int i = 0; i < L; ++i) w1T[(size_t)i * H + o] = w1[(size_t)o * L + i];
-    for (int o = 0; o < H; ++o) for (int i = 0; i < H; ++i) w2T[(size_t)i * H + o] = w2[(size_t)o * H + i];
-    for (int o = 0; o < 126; ++o) for (int i = 0; i < H; ++i) w3T[(size_t)i * 128 + o] = w3[(size_t)o * H + i];
+    VposerPack P;
+    vposer_pack(L, H, w1, w2, w3, P);
     m->M.vp_latent = latent; m->M.vp_hidden = hidden;
     m->M.vp_w1 = m->mem.up(v(w1, (size_t)H * L)); m->M.vp_b1 = m->mem.up(v(b1, H));
     m->M.vp_w2 = m->mem.up(v(w2, (size_t)H * H)); m->M.vp_b2 = m->mem.up(v(b2, H));
     m->M.vp_w3 = m->mem.up(v(w3, (size_t)126 * H)); m->M.vp_b3 = m->mem.up(v(b3, 126));
-    m->M.vp_w1T = m->mem.up(w1T); m->M.vp_w2T = m->mem.up(w2T); m->M.vp_w3T = m->mem.up(w3T);
+    m->M.vp_w1T = m->mem.up(P.w1T); m->M.vp_w2T = m->mem.up(P.w2T); m->M.vp_w3T = m->mem.up(P.w3T);
     if (m->mem.failed) { (void)hipGetLastError(); m->M.vp_latent = 0; sfx_set_error("out of device memory (VPoser weights)"); return -2; }
     if (m->fwd) { sfx_batch_destroy(m->fwd); m->fwd = nullptr; }
     return 0;

@@ -227,6 +227,80 @@ class DeviceModel(object):
             pass
 
 
+class VPoserDecoder(object):
+    """VPoser-v1 decoder weights resident in HBM (sfx_vposer): `decode` / `decode_backward` for whole batches of latents,
+    outside any fit (inside one the closure workgroup decodes: csrc/vposer.h).  `weights` is the numpy dict
+    DeviceModel.set_vposer takes (fc1_w [512][L], fc1_b, fc2_w, fc2_b, out_w [126][512], out_b).  The handle lives on the
+    device that is current when it is made."""
+
+    def __init__(self, weights):
+        lib = capi.load()
+        a = {k: capi.f32(weights[k]) for k in ("fc1_w", "fc1_b", "fc2_w", "fc2_b", "out_w", "out_b")}
+        hidden, latent = (int(n) for n in a["fc1_w"].shape)
+        want = dict(fc1_b=(hidden,), fc2_w=(hidden, hidden), fc2_b=(hidden,), out_w=(126, hidden), out_b=(126,))
+        for k, shape in want.items():
+            if tuple(a[k].shape) != shape:
+                raise ValueError("%s: shape %s, expected %s" % (k, tuple(a[k].shape), shape))
+        h = C.c_void_p()
+        capi.check(lib.sfx_vposer_create(latent, hidden, capi.fptr(a["fc1_w"]), capi.fptr(a["fc1_b"]), capi.fptr(a["fc2_w"]),
+                                         capi.fptr(a["fc2_b"]), capi.fptr(a["out_w"]), capi.fptr(a["out_b"]), C.byref(h)))
+        self._h, self._lib = h, lib
+        self.latent = latent
+
+    def _in(self, name, t, n, B=None):
+        import torch
+        if not torch.is_tensor(t) or t.dim() != 2 or t.shape[1] != n or (B is not None and t.shape[0] != B):
+            raise ValueError("%s: shape %s, expected %s" % (name, tuple(getattr(t, "shape", ())), ("B" if B is None else B, n)))
+        if t.device.type != "cuda":
+            raise ValueError("%s: a CUDA tensor is needed (no CPU fallback), got device %s" % (name, t.device))
+        return t.detach().to(torch.float32).contiguous()
+
+    def decode(self, z, out=None, stream=None):
+        """z [B][latent] (torch CUDA tensor) -> body_pose [B][63], axis-angle of the 21 body joints.  `out`: a float32
+        contiguous [B][63] tensor on z's device to write into.  Only enqueues on the current (or the given) stream."""
+        import torch
+        z = self._in("z", z, self.latent)
+        B = z.shape[0]
+        if out is None:
+            out = torch.empty([B, 63], dtype=torch.float32, device=z.device)
+        elif tuple(out.shape) != (B, 63) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != z.device:
+            raise ValueError("out: a contiguous float32 %s tensor on %s is needed" % ((B, 63), z.device))
+        s = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(z.device).cuda_stream)
+        capi.check(self._lib.sfx_vposer_decode(self._h, B, C.c_void_p(z.data_ptr()), C.c_void_p(out.data_ptr()), s))
+        return out
+
+    def decode_backward(self, z, dbody, out=None, stream=None):
+        """d sum(dbody * decode(z)) / d z: [B][latent].  Stateless: z is given again and the forward re-evaluated at it."""
+        import torch
+        z = self._in("z", z, self.latent)
+        B = z.shape[0]
+        if torch.is_tensor(dbody) and dbody.dim() > 2:
+            dbody = dbody.reshape(dbody.shape[0], -1)
+        dbody = self._in("dbody", dbody, 63, B)
+        if dbody.device != z.device:
+            raise ValueError("dbody: on %s, z on %s" % (dbody.device, z.device))
+        if out is None:
+            out = torch.empty([B, self.latent], dtype=torch.float32, device=z.device)
+        elif (tuple(out.shape) != (B, self.latent) or out.dtype != torch.float32 or not out.is_contiguous()
+              or out.device != z.device):
+            raise ValueError("out: a contiguous float32 %s tensor on %s is needed" % ((B, self.latent), z.device))
+        s = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(z.device).cuda_stream)
+        capi.check(self._lib.sfx_vposer_decode_backward(self._h, B, C.c_void_p(z.data_ptr()), C.c_void_p(dbody.data_ptr()),
+                                                        C.c_void_p(out.data_ptr()), s))
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.sfx_vposer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 PRECISIONS = ("mixed", "float64")
 
 

@@ -178,6 +178,10 @@ class EngineClosure(object):
             self._fb.close()
         bm, loss, cam = self.body_model, self.loss, self.camera
         dm = bm.device_model
+        if self.use_vposer and not dm.vposer_latent and getattr(self.vposer, "weights", None) is not None:
+            # the reference hands the decoder to the closure as an object (vposer=); a model made without smplx.create(vposer=)
+            # gets its in-loop copy of the weights from it (a model that has weights keeps them)
+            dm.set_vposer(self.vposer.weights)
         K = dm.K
         opt = self.optimizer
         w = capi.StageWeights()

@@ -13,11 +13,19 @@ follows the public VPoser-v1 definition:
 
 `.sample()` makes the reference non-deterministic; `encode` returns the mean by default and
 draws the sample only when given a seeded generator.
+
+`VPoser` / `load_vposer_model` are the OBJECT the reference holds (`vposer, _ = load_vposer(ckpt,
+vp_model='snapshot'); vposer = vposer.to(device); vposer.eval()`): `decode(z, output_type='aa')`
+runs the batched HIP decoder of csrc/vposer_batch.hip (engine.VPoserDecoder) and carries an
+autograd graph whose backward is that kernel's; `encode(pose)` returns the Normal the reference
+samples from, computed by the host encoder above.
 """
 import glob
 import os
 
 import numpy as np
+import torch
+import torch.nn as nn
 
 _DEC = (("fc1_w", "bodyprior_dec_fc1.weight"), ("fc1_b", "bodyprior_dec_fc1.bias"),
         ("fc2_w", "bodyprior_dec_fc2.weight"), ("fc2_b", "bodyprior_dec_fc2.bias"),
@@ -100,13 +108,8 @@ def _aa_to_matrot(pose):
     return R.reshape(pose.shape[0], -1)
 
 
-def encode(w, pose, generator=None):
-    """VPoser-v1 encoder on [B, 63] body poses -> latent [B, latentD] (float32).
-
-    Returns the mean of the posterior; with `generator` (numpy Generator) draws
-    mean + sigma * N(0, 1), the reference's `.sample()` made reproducible.  An encoder whose
-    first layer is 189 wide (rotation-matrix input, `data_shape [1, 21, 9]`) gets the poses as
-    rotation matrices, a 63-wide one gets them as they are."""
+def _encoder_trunk(w, pose):
+    """(x, f): the encoder's last hidden layer [B, 512] in float64 for [B, 63] poses, and the float64 weight accessor."""
     if "enc_fc1_w" not in w:
         raise ValueError("these VPoser weights carry no encoder (bodyprior_enc_*)")
     x = np.asarray(pose, np.float64).reshape(-1, 63)
@@ -120,8 +123,107 @@ def encode(w, pose, generator=None):
     x = _leaky(x @ f("enc_fc1_w").T + f("enc_fc1_b"))
     x = (x - f("enc_bn2_mean")) / np.sqrt(f("enc_bn2_var") + BN_EPS) * f("enc_bn2_w") + f("enc_bn2_b")
     x = _leaky(x @ f("enc_fc2_w").T + f("enc_fc2_b"))
+    return x, f
+
+
+def encode(w, pose, generator=None):
+    """VPoser-v1 encoder on [B, 63] body poses -> latent [B, latentD] (float32).
+
+    Returns the mean of the posterior; with `generator` (numpy Generator) draws
+    mean + sigma * N(0, 1), the reference's `.sample()` made reproducible.  An encoder whose
+    first layer is 189 wide (rotation-matrix input, `data_shape [1, 21, 9]`) gets the poses as
+    rotation matrices, a 63-wide one gets them as they are."""
+    x, f = _encoder_trunk(w, pose)
     mu = x @ f("enc_mu_w").T + f("enc_mu_b")
     if generator is not None:
         sigma = _softplus(x @ f("enc_logvar_w").T + f("enc_logvar_b"))
         mu = mu + sigma * generator.standard_normal(mu.shape)
     return mu.astype(np.float32)
+
+
+def encode_stats(w, pose):
+    """(mean, sigma) of the encoder's posterior for [B, 63] body poses, both [B, latentD] float64: the two parameters of the
+    Normal that `vposer.encode(pose)` returns in the reference (sigma = softplus(fc_logvar))."""
+    x, f = _encoder_trunk(w, pose)
+    return x @ f("enc_mu_w").T + f("enc_mu_b"), _softplus(x @ f("enc_logvar_w").T + f("enc_logvar_b"))
+
+
+class _Decode(torch.autograd.Function):
+    """body_pose [B, 63] = decode(z) with the engine on both sides: forward = sfx_vposer_decode, backward =
+    sfx_vposer_decode_backward at the SAVED z (stateless).  First derivatives only."""
+
+    @staticmethod
+    def forward(ctx, dec, z):
+        z = z.detach()
+        ctx.dec = dec
+        ctx.save_for_backward(z)
+        return dec.decode(z)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dbody):
+        z, = ctx.saved_tensors
+        with torch.cuda.device(z.device):
+            return None, ctx.dec.decode_backward(z, dbody)
+
+
+class VPoser(nn.Module):
+    """The object `load_vposer(...)` returns in the reference, over the HIP decoder: `.latentD`, `.to(device)`, `.eval()`,
+    `.decode(z, output_type='aa')`, `.encode(pose)`.  `weights` is the numpy dict of load_vposer() above -- the same dict
+    smplx.create(vposer=) / DeviceModel.set_vposer accept; it stays on the host (`.weights`), the device copy is an
+    engine.VPoserDecoder per GPU, made at the first decode there."""
+
+    def __init__(self, weights):
+        super().__init__()
+        missing = [k for k, _ in _DEC if k not in weights]
+        if missing:
+            raise KeyError("VPoser weights: missing %s" % missing)
+        self.weights = {k: np.ascontiguousarray(v, np.float32) for k, v in weights.items()}
+        self.latentD = int(self.weights["fc1_w"].shape[1])
+        self._decoders = {}
+
+    def _decoder(self, device):
+        from . import engine
+        key = device.index if device.index is not None else torch.cuda.current_device()
+        if key not in self._decoders:
+            with torch.cuda.device(key):
+                self._decoders[key] = engine.VPoserDecoder(self.weights)
+        return self._decoders[key]
+
+    def decode(self, Zin, output_type="aa"):
+        """[B, latentD] -> [B, 1, 21, 3] axis-angle (the reference then calls .view(1, -1)).  With a Zin that requires grad
+        the result carries the graph back to it; float64 latents are cast in and out."""
+        if output_type != "aa":
+            raise ValueError("output_type=%r: only 'aa' (axis-angle) is provided" % (output_type,))
+        if not torch.is_tensor(Zin) or Zin.device.type != "cuda":
+            raise RuntimeError("VPoser.decode needs a latent on the GPU: the HIP decoder has no CPU fallback")
+        if Zin.dim() != 2 or Zin.shape[1] != self.latentD:
+            raise ValueError("Zin: shape %s, expected (B, %d)" % (tuple(Zin.shape), self.latentD))
+        with torch.cuda.device(Zin.device):
+            body = _Decode.apply(self._decoder(Zin.device), Zin.to(torch.float32))
+        return body.to(Zin.dtype).view(Zin.shape[0], 1, 21, 3)
+
+    @torch.no_grad()
+    def encode(self, Pin):
+        """torch.distributions.Normal(mean, stddev) of the posterior for poses [B, 63] (any shape with 63 values per row), on
+        Pin's device and dtype, without a graph: computed by the host encoder (encode_stats), once per frame in the reference."""
+        P = Pin.detach().to("cpu", torch.float64).reshape(Pin.shape[0], -1).numpy()
+        mu, sigma = encode_stats(self.weights, P)
+        t = lambda a: torch.as_tensor(a).to(device=Pin.device, dtype=Pin.dtype)
+        return torch.distributions.normal.Normal(t(mu), t(sigma))
+
+    def forward(self, Pin):
+        raise NotImplementedError("VPoser.forward (encode -> sample -> decode) is not used by the reference's fitting path")
+
+    def close(self):
+        for d in self._decoders.values():
+            d.close()
+        self._decoders = {}
+
+
+def load_vposer_model(vposer_ckpt, vp_model="snapshot"):
+    """`load_vposer(expr_dir, vp_model='snapshot')` of human_body_prior as the reference unpacks it
+    (fit_single_frame.py:241): (VPoser, None) -- the second element is the training configuration, which nothing reads."""
+    if vp_model != "snapshot":
+        raise ValueError("vp_model=%r: only 'snapshot' is provided" % (vp_model,))
+    return VPoser(load_vposer(vposer_ckpt)), None
