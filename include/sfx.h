@@ -86,6 +86,38 @@ int  sfx_vposer_decode(sfx_vposer* v, int32_t B, const float* z_dev /* [B][laten
 int  sfx_vposer_decode_backward(sfx_vposer* v, int32_t B, const float* z_dev /* [B][latent] */,
                                 const float* dbody_dev /* [B][63] */, float* dz_dev /* [B][latent] */, void* stream);
 
+/* ---- stand-alone VPoser encoder ---------------------------------------------------------
+ * Replaces `vposer.encode(full_pose_prior)` of human_body_prior (cvpr19; reference call site fit_single_frame.py:245: the
+ * Normal the starting latent is sampled from) for B poses at once, with its backward: the pose prior
+ * `vposer.encode(body_pose).mean.pow(2).sum()` of code that optimises the pose itself, and the manifold projection
+ * decode(encode(p).mean).  A handle of its own -- a checkpoint may carry no encoder, and sfx_vposer stays as it is.
+ * Weights are HOST pointers in the checkpoint's layouts ([out][in]): bn1 / bn2 [n_in] / [hidden] (weight, bias, running_mean,
+ * running_var), fc1 [hidden][n_in], fc2 [hidden][hidden], mu and logvar [latent][hidden].  Eval-mode batch norm (eps 1e-5) is
+ * folded into the linear layer behind it, in double.  n_in = 63: the first layer takes the axis-angle pose; n_in = 189: the
+ * row-major rotation matrices of the 21 joints (plain Rodrigues, first-order below 1e-6 rad).  Refused before any device
+ * memory is touched (-1): hidden != 512, latent not a multiple of 4 in 4 .. 60, n_in not 63 or 189, running_var + 1e-5 <= 0
+ * or a non-finite value in a batch-norm table; -3: no HIP device; -2: out of device memory.
+ * encode / encode_backward take DEVICE pointers to contiguous fp32 and only ENQUEUE on `stream`: they do not synchronise,
+ * allocate nothing and use no global scratch (B = 0: nothing is launched).  mean = mu, sigma = softplus(logvar): the two
+ * parameters of the Normal.  encode_backward is stateless (the forward is re-evaluated at pose_dev):
+ * dpose = d (sum(dmean * mean) + sum(dsigma * sigma)) / d pose; one of dmean / dsigma may be NULL (= zeros), both NULL is
+ * refused.  A frame's result depends on its own pose only, bit for bit (not on B or its position in the batch).  */
+typedef struct sfx_vposer_encoder sfx_vposer_encoder;
+int  sfx_vposer_encoder_create(int32_t latent, int32_t hidden, int32_t n_in,
+                               const float* bn1_w, const float* bn1_b, const float* bn1_mean, const float* bn1_var,
+                               const float* fc1_w, const float* fc1_b,
+                               const float* bn2_w, const float* bn2_b, const float* bn2_mean, const float* bn2_var,
+                               const float* fc2_w, const float* fc2_b,
+                               const float* mu_w, const float* mu_b, const float* logvar_w, const float* logvar_b,
+                               sfx_vposer_encoder** out);
+void sfx_vposer_encoder_destroy(sfx_vposer_encoder* e);
+int  sfx_vposer_encode(sfx_vposer_encoder* e, int32_t B, const float* pose_dev /* [B][63] */,
+                       float* mean_dev /* [B][latent] */, float* sigma_dev /* [B][latent], may be NULL */, void* stream);
+int  sfx_vposer_encode_backward(sfx_vposer_encoder* e, int32_t B, const float* pose_dev /* [B][63] */,
+                                const float* dmean_dev /* [B][latent], may be NULL */,
+                                const float* dsigma_dev /* [B][latent], may be NULL */,
+                                float* dpose_dev /* [B][63] */, void* stream);
+
 /* ---- stand-alone LBS forward ----------------------------------------------------------
  * Replaces body_model(return_verts=True, body_pose=..., return_full_pose=True)
  * (fitting.py:82,248; fit_single_frame.py:611).  All pointers are DEVICE pointers to

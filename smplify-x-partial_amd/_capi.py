@@ -81,6 +81,11 @@ SYMBOLS = {
     "sfx_vposer_destroy": (None, [C.c_void_p]),
     "sfx_vposer_decode": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sfx_vposer_decode_backward": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # latent, hidden, n_in, bn1 (w, b, mean, var), fc1 (w, b), bn2 (w, b, mean, var), fc2 (w, b), mu (w, b), logvar (w, b), out
+    "sfx_vposer_encoder_create": (C.c_int, [C.c_int32] * 3 + [f32p] * 16 + [C.POINTER(C.c_void_p)]),
+    "sfx_vposer_encoder_destroy": (None, [C.c_void_p]),
+    "sfx_vposer_encode": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sfx_vposer_encode_backward": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.c_void_p]),
     "sfx_lbs_forward": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 12 + [C.c_void_p]),
     # model, B, nine inputs, dvertices, djoints, nine gradients, stream
     "sfx_lbs_backward": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 20 + [C.c_void_p]),

@@ -301,6 +301,115 @@ class VPoserDecoder(object):
             pass
 
 
+_ENC_KEYS = ("enc_bn1_w", "enc_bn1_b", "enc_bn1_mean", "enc_bn1_var", "enc_fc1_w", "enc_fc1_b",
+             "enc_bn2_w", "enc_bn2_b", "enc_bn2_mean", "enc_bn2_var", "enc_fc2_w", "enc_fc2_b",
+             "enc_mu_w", "enc_mu_b", "enc_logvar_w", "enc_logvar_b")
+
+
+class VPoserEncoder(object):
+    """VPoser-v1 encoder weights resident in HBM (sfx_vposer_encoder): `encode` / `encode_backward` for whole batches of
+    poses.  `weights` is the numpy dict of vposer.load_vposer with its `enc_*` keys (bn1, fc1 [512][63 | 189], bn2, fc2, mu and
+    logvar [L][512]); the batch norms are folded into the linear layers on the host.  The handle lives on the device that is
+    current when it is made."""
+
+    def __init__(self, weights):
+        lib = capi.load()
+        missing = [k for k in _ENC_KEYS if k not in weights]
+        if missing:
+            raise ValueError("these VPoser weights carry no encoder (bodyprior_enc_*): missing %s" % missing)
+        a = {k: capi.f32(weights[k]) for k in _ENC_KEYS}
+        if a["enc_fc1_w"].ndim != 2 or a["enc_mu_w"].ndim != 2:
+            raise ValueError("enc_fc1_w / enc_mu_w: two-dimensional [out][in] arrays are needed")
+        hidden, n_in = (int(n) for n in a["enc_fc1_w"].shape)
+        latent = int(a["enc_mu_w"].shape[0])
+        want = dict(enc_bn1_w=(n_in,), enc_bn1_b=(n_in,), enc_bn1_mean=(n_in,), enc_bn1_var=(n_in,), enc_fc1_b=(hidden,),
+                    enc_bn2_w=(hidden,), enc_bn2_b=(hidden,), enc_bn2_mean=(hidden,), enc_bn2_var=(hidden,),
+                    enc_fc2_w=(hidden, hidden), enc_fc2_b=(hidden,), enc_mu_w=(latent, hidden), enc_mu_b=(latent,),
+                    enc_logvar_w=(latent, hidden), enc_logvar_b=(latent,))
+        for k, shape in want.items():
+            if tuple(a[k].shape) != shape:
+                raise ValueError("%s: shape %s, expected %s" % (k, tuple(a[k].shape), shape))
+        h = C.c_void_p()
+        capi.check(lib.sfx_vposer_encoder_create(latent, hidden, n_in, *[capi.fptr(a[k]) for k in _ENC_KEYS], C.byref(h)))
+        import torch
+        self._h, self._lib = h, lib
+        self.latent, self.n_in = latent, n_in
+        self.device_index = torch.cuda.current_device()      # where the weights live: every tensor of a call must be there
+
+    def _in(self, name, t, n, B=None):
+        import torch
+        if not torch.is_tensor(t) or t.dim() != 2 or t.shape[1] != n or (B is not None and t.shape[0] != B):
+            raise ValueError("%s: shape %s, expected %s" % (name, tuple(getattr(t, "shape", ())), ("B" if B is None else B, n)))
+        if t.device.type != "cuda":
+            raise ValueError("%s: a CUDA tensor is needed (no CPU fallback), got device %s" % (name, t.device))
+        return t.detach().to(torch.float32).contiguous()
+
+    def _out(self, name, out, shape, device):
+        import torch
+        if out is None:
+            return torch.empty(list(shape), dtype=torch.float32, device=device)
+        if tuple(out.shape) != tuple(shape) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != device:
+            raise ValueError("%s: a contiguous float32 %s tensor on %s is needed" % (name, tuple(shape), device))
+        return out
+
+    def _pose(self, pose):
+        import torch
+        if torch.is_tensor(pose) and pose.dim() > 2:
+            pose = pose.reshape(pose.shape[0], -1)
+        pose = self._in("pose", pose, 63)
+        if pose.device.index != self.device_index:
+            raise ValueError("pose: on %s, the encoder's weights on cuda:%d" % (pose.device, self.device_index))
+        return pose
+
+    def encode(self, pose, out_mean=None, out_sigma=None, stream=None):
+        """pose [B][63] (torch CUDA tensor; [B][21][3] and [B][1][21][3] are flattened) -> (mean, sigma), both [B][latent]: the
+        two parameters of the Normal `vposer.encode(pose)` returns in the reference.  `out_mean` / `out_sigma`: float32
+        contiguous [B][latent] tensors on pose's device to write into.  `out_sigma=False`: sigma is not wanted (a prior on the
+        mean alone) -- it is neither evaluated nor stored, and (mean, None) is returned.  Only enqueues on the current (or the
+        given) stream."""
+        import torch
+        pose = self._pose(pose)
+        B = pose.shape[0]
+        mean = self._out("out_mean", out_mean, (B, self.latent), pose.device)
+        sigma = None if out_sigma is False else self._out("out_sigma", out_sigma, (B, self.latent), pose.device)
+        s = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(pose.device).cuda_stream)
+        capi.check(self._lib.sfx_vposer_encode(self._h, B, C.c_void_p(pose.data_ptr()), C.c_void_p(mean.data_ptr()),
+                                               C.c_void_p(sigma.data_ptr()) if sigma is not None else None, s))
+        return mean, sigma
+
+    def encode_backward(self, pose, dmean, dsigma, out=None, stream=None):
+        """d (sum(dmean * mean) + sum(dsigma * sigma)) / d pose: [B][63].  One of dmean / dsigma may be None (= zeros).
+        Stateless: pose is given again and the forward re-evaluated at it."""
+        import torch
+        pose = self._pose(pose)
+        B = pose.shape[0]
+        if dmean is None and dsigma is None:
+            raise ValueError("dmean and dsigma: at least one is needed")
+        grads = []
+        for name, d in (("dmean", dmean), ("dsigma", dsigma)):
+            if d is not None:
+                d = self._in(name, d, self.latent, B)
+                if d.device != pose.device:
+                    raise ValueError("%s: on %s, pose on %s" % (name, d.device, pose.device))
+            grads.append(d)
+        out = self._out("out", out, (B, 63), pose.device)
+        s = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(pose.device).cuda_stream)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        capi.check(self._lib.sfx_vposer_encode_backward(self._h, B, ptr(pose), ptr(grads[0]), ptr(grads[1]), ptr(out), s))
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.sfx_vposer_encoder_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 PRECISIONS = ("mixed", "float64")
 
 

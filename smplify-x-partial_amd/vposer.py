@@ -18,7 +18,9 @@ draws the sample only when given a seeded generator.
 vp_model='snapshot'); vposer = vposer.to(device); vposer.eval()`): `decode(z, output_type='aa')`
 runs the batched HIP decoder of csrc/vposer_batch.hip (engine.VPoserDecoder) and carries an
 autograd graph whose backward is that kernel's; `encode(pose)` returns the Normal the reference
-samples from, computed by the host encoder above.
+samples from, computed by the host encoder above -- or, for an object made with
+`differentiable=True` and poses on the GPU, by the batched HIP encoder of csrc/vposer_encode.hip
+(engine.VPoserEncoder) with a graph back to the poses.
 """
 import glob
 import os
@@ -167,20 +169,55 @@ class _Decode(torch.autograd.Function):
             return None, ctx.dec.decode_backward(z, dbody)
 
 
+class _Encode(torch.autograd.Function):
+    """(mean, sigma) [B, latentD] = encode(pose [B, 63]) with the engine on both sides: forward = sfx_vposer_encode, backward =
+    sfx_vposer_encode_backward at the SAVED pose (stateless).  First derivatives only."""
+
+    @staticmethod
+    def forward(ctx, enc, pose):
+        pose = pose.detach()
+        ctx.enc = enc
+        ctx.save_for_backward(pose)
+        return enc.encode(pose)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dmean, dsigma):
+        pose, = ctx.saved_tensors
+        with torch.cuda.device(pose.device):
+            return None, ctx.enc.encode_backward(pose, dmean, dsigma)
+
+
 class VPoser(nn.Module):
     """The object `load_vposer(...)` returns in the reference, over the HIP decoder: `.latentD`, `.to(device)`, `.eval()`,
     `.decode(z, output_type='aa')`, `.encode(pose)`.  `weights` is the numpy dict of load_vposer() above -- the same dict
     smplx.create(vposer=) / DeviceModel.set_vposer accept; it stays on the host (`.weights`), the device copy is an
-    engine.VPoserDecoder per GPU, made at the first decode there."""
+    engine.VPoserDecoder per GPU, made at the first decode there.
 
-    def __init__(self, weights):
+    `differentiable=True` (the convention of smplx.create(differentiable=)): `encode` of poses on the GPU runs the HIP encoder
+    (one engine.VPoserEncoder per GPU, made at the first encode there) and returns a Normal whose mean and scale carry a graph
+    back to the poses, and `forward` (encode -> rsample -> decode) is provided.  The default object keeps the host encoder."""
+
+    def __init__(self, weights, differentiable=False):
         super().__init__()
         missing = [k for k, _ in _DEC if k not in weights]
         if missing:
             raise KeyError("VPoser weights: missing %s" % missing)
         self.weights = {k: np.ascontiguousarray(v, np.float32) for k, v in weights.items()}
         self.latentD = int(self.weights["fc1_w"].shape[1])
+        self.differentiable = bool(differentiable)
         self._decoders = {}
+        self._encoders = {}
+
+    def _encoder(self, device):
+        from . import engine
+        key = device.index if device.index is not None else torch.cuda.current_device()
+        if key not in self._encoders:
+            if "enc_fc1_w" not in self.weights:
+                raise ValueError("these VPoser weights carry no encoder (bodyprior_enc_*)")
+            with torch.cuda.device(key):
+                self._encoders[key] = engine.VPoserEncoder(self.weights)
+        return self._encoders[key]
 
     def _decoder(self, device):
         from . import engine
@@ -203,27 +240,51 @@ class VPoser(nn.Module):
             body = _Decode.apply(self._decoder(Zin.device), Zin.to(torch.float32))
         return body.to(Zin.dtype).view(Zin.shape[0], 1, 21, 3)
 
-    @torch.no_grad()
     def encode(self, Pin):
         """torch.distributions.Normal(mean, stddev) of the posterior for poses [B, 63] (any shape with 63 values per row), on
-        Pin's device and dtype, without a graph: computed by the host encoder (encode_stats), once per frame in the reference."""
+        Pin's device and dtype.  Default object, or a Pin on the CPU: without a graph, computed by the host encoder
+        (encode_stats), once per frame in the reference.  `differentiable=True` and a Pin on the GPU: computed by the HIP
+        encoder; mean and scale carry the graph back to Pin (first derivatives only), float64 poses are cast in and out."""
+        if self.differentiable and torch.is_tensor(Pin) and Pin.device.type == "cuda":
+            P = Pin.reshape(Pin.shape[0], -1)
+            if P.shape[1] != 63:
+                raise ValueError("Pin: shape %s, expected 63 values per row" % (tuple(Pin.shape),))
+            with torch.cuda.device(Pin.device):
+                mean, sigma = _Encode.apply(self._encoder(Pin.device), P.to(torch.float32))
+            return torch.distributions.normal.Normal(mean.to(Pin.dtype), sigma.to(Pin.dtype))
+        with torch.no_grad():
+            return self._encode_host(Pin)
+
+    def _encode_host(self, Pin):
         P = Pin.detach().to("cpu", torch.float64).reshape(Pin.shape[0], -1).numpy()
         mu, sigma = encode_stats(self.weights, P)
         t = lambda a: torch.as_tensor(a).to(device=Pin.device, dtype=Pin.dtype)
         return torch.distributions.normal.Normal(t(mu), t(sigma))
 
-    def forward(self, Pin):
-        raise NotImplementedError("VPoser.forward (encode -> sample -> decode) is not used by the reference's fitting path")
+    def forward(self, Pin, output_type="aa"):
+        """The VAE round trip of a `differentiable=True` object: q = encode(Pin), z = q.rsample() (torch's global generator),
+        decode(z) -> {'mean': q.mean, 'std': q.scale, 'pose_aa': [B, 1, 21, 3]}.  This is the cvpr19 package's `forward` as
+        recalled from its public source: human_body_prior is not available to compare against, so, like the rest of the VPoser
+        surface, it is UNPINNED.  Any output_type but 'aa' raises, as in decode."""
+        if not self.differentiable:
+            raise NotImplementedError("VPoser.forward (encode -> sample -> decode) is not used by the reference's fitting path; "
+                                      "it is provided by VPoser(weights, differentiable=True)")
+        if output_type != "aa":
+            raise ValueError("output_type=%r: only 'aa' (axis-angle) is provided" % (output_type,))
+        q = self.encode(Pin)
+        return {"mean": q.mean, "std": q.scale, "pose_aa": self.decode(q.rsample(), output_type="aa")}
 
     def close(self):
-        for d in self._decoders.values():
+        for d in list(self._decoders.values()) + list(self._encoders.values()):
             d.close()
         self._decoders = {}
+        self._encoders = {}
 
 
-def load_vposer_model(vposer_ckpt, vp_model="snapshot"):
+def load_vposer_model(vposer_ckpt, vp_model="snapshot", differentiable=False):
     """`load_vposer(expr_dir, vp_model='snapshot')` of human_body_prior as the reference unpacks it
-    (fit_single_frame.py:241): (VPoser, None) -- the second element is the training configuration, which nothing reads."""
+    (fit_single_frame.py:241): (VPoser, None) -- the second element is the training configuration, which nothing reads.
+    `differentiable`: see VPoser."""
     if vp_model != "snapshot":
         raise ValueError("vp_model=%r: only 'snapshot' is provided" % (vp_model,))
-    return VPoser(load_vposer(vposer_ckpt)), None
+    return VPoser(load_vposer(vposer_ckpt), differentiable=differentiable), None
