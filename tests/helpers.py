@@ -171,6 +171,118 @@ def check_bound(label, what, err, bound):
     assert err <= bound, (label, what, float(err), bound)
     return err
 
+# ---------------------------------------------------------------------------------------------------------
+# Per-block gradient parity.  check_closure bounds the error of the WHOLE variable vector, and one block (the jaw prior far from
+# the solution, the pose near it) carries almost all of that vector's norm: a block with share s of the norm could be wrong by a
+# relative CLOSURE_GRAD_TOL / s and pass.  check_closure_blocks holds every parameter block to a bound of its own:
+#     yardstick(block) = || go32_b - go_b || / || go_b ||      the float32 oracle's own error in that block against the float64
+#                                                              oracle at the same points, largest over the frames of the set
+#     bound(block)     = max(floor, 10 x yardstick x unit_ratio)
+# floor is the whole-vector bound (a block is not asked to be tighter than the vector it is part of); 10 x the float32 reference
+# is the margin of CLOSURE_*_TOL; unit_ratio scales the float32 yardstick to the arithmetic under test (2**-53 / 2**-24 for the
+# float64 batch).  A block whose reference gradient is exactly zero (the dead body_pose parameter) must be exactly zero on the
+# device: the only case in which no ratio is formed.
+F64_UNIT_RATIO = 2.0 ** -53 / 2.0 ** -24
+BLOCK_LOG = {}
+
+
+def gradient_blocks(ff, stage):
+    """[(name, start, stop)] of the oracle's flat gradient of `stage` (oracle.fit_frame.FrameFit `ff`), in the reference's
+    variable order: the body model's own parameter list, then pose_embedding; the camera stage is cam_translation,
+    global_orient.  The caller asserts that the blocks tile 0 .. FrameBatch.num_vars(stage)."""
+    if stage < 0:
+        ps = [("cam_translation", ff.cam_t), ("global_orient", ff.bm.global_orient)]
+    else:
+        ps = [(n, p) for n, p in ff.bm.named_parameters() if p.requires_grad] + [("pose_embedding", ff.pose_embedding)]
+    blocks, o = [], 0
+    for name, p in ps:
+        blocks.append((name, o, o + p.numel()))
+        o += p.numel()
+    return blocks
+
+
+def assert_blocks_tile(blocks, n):
+    """The blocks cover 0 .. n exactly once, in order, none empty."""
+    o = 0
+    for name, a, b in blocks:
+        assert a == o and b > a, ("gradient blocks do not tile", name, a, b, o)
+        o = b
+    assert o == n, ("gradient blocks do not tile", o, n)
+    assert len({name for name, _, _ in blocks}) == len(blocks), blocks
+
+
+def without_block(blocks, name):
+    """(blocks re-tiled without `name`, index array of the kept variables): for a device vector that leaves a dead block out."""
+    keep, out, o = [], [], 0
+    for n, a, b in blocks:
+        if n == name:
+            continue
+        keep.extend(range(a, b))
+        out.append((n, o, o + b - a))
+        o += b - a
+    assert len(out) == len(blocks) - 1, (name, blocks)
+    return out, np.asarray(keep, np.int64)
+
+
+def block_errors(grad, go, blocks):
+    """[(name, || g_b - go_b || / || go_b ||, || go_b || / || go ||)] of one frame.  The error is None for a block whose
+    reference norm is exactly zero (no ratio can be formed; check_closure_blocks asks the device for exact zeros there)."""
+    g, r = np.asarray(grad, np.float64).reshape(-1), np.asarray(go, np.float64).reshape(-1)
+    assert g.shape == r.shape, (g.shape, r.shape)
+    tot = np.linalg.norm(r)
+    out = []
+    for name, a, b in blocks:
+        nb = np.linalg.norm(r[a:b])
+        out.append((name, None if nb == 0.0 else float(np.linalg.norm(g[a:b] - r[a:b]) / nb), float(nb / tot) if tot > 0 else 0.0))
+    return out
+
+
+def block_yardstick(go, go32, blocks):
+    """{block: the float32 oracle's relative error in that block against `go`, largest over the frames} (rows of [B, N]
+    arrays); a block dead in every frame has no entry."""
+    go, go32 = np.atleast_2d(np.asarray(go, np.float64)), np.atleast_2d(np.asarray(go32, np.float64))
+    y = {}
+    for i in range(go.shape[0]):
+        for name, err, _ in block_errors(go32[i], go[i], blocks):
+            if err is not None:
+                y[name] = max(y.get(name, 0.0), err)
+    return y
+
+
+def check_closure_blocks(label, stage, grad, go, go32, blocks, floor=CLOSURE_GRAD_TOL, unit_ratio=1.0, yardstick=None):
+    """Record and assert the per-block gradient comparison of one (cfg, point set, stage): `grad` (device), `go` (float64
+    oracle) and `go32` (float32 oracle) are [N] or [B, N], one row per frame of the set.  Every block of every frame must stay
+    within max(floor, 10 x yardstick x unit_ratio); a block whose reference is exactly zero must be exactly zero.  `yardstick`
+    ({block: value}, from block_yardstick) replaces the one formed from go32 -- for comparisons whose `go` is not the float64
+    oracle (rows against dense).  Returns {block: (largest error or None, smallest share, bound or None)}."""
+    grad, go = np.atleast_2d(np.asarray(grad, np.float64)), np.atleast_2d(np.asarray(go, np.float64))
+    assert grad.shape == go.shape, (grad.shape, go.shape)
+    assert_blocks_tile(blocks, go.shape[1])
+    if yardstick is None:
+        yardstick = block_yardstick(go, go32, blocks)
+    out, bad = {}, []
+    for i in range(go.shape[0]):
+        for (name, err, share), (_, a, b) in zip(block_errors(grad[i], go[i], blocks), blocks):
+            e = BLOCK_LOG.setdefault((label, int(stage), name), [None, np.inf, None, 0])
+            e[3] += 1
+            if err is None:
+                if np.any(grad[i, a:b] != 0):
+                    bad.append(("dead block is not exactly zero", name, i, float(np.abs(grad[i, a:b]).max())))
+                e[1] = 0.0
+            else:
+                if name not in yardstick:
+                    bad.append(("no yardstick", name, i))
+                    continue
+                bound = max(floor, 10.0 * yardstick[name] * unit_ratio)
+                e[0] = err if e[0] is None else max(e[0], err)
+                e[1] = min(e[1], share)
+                e[2] = bound if e[2] is None else max(e[2], bound)
+                if not err <= bound:
+                    bad.append(("closure gradient block", name, i, err, bound, share))
+            out[name] = tuple(e[:3])
+    assert not bad, (label, stage, bad)
+    return out
+
 
 def parity_log_lines():
     out = []
@@ -179,4 +291,10 @@ def parity_log_lines():
     for (label, stage), (le, ge, n, lt, gt) in sorted(PARITY_LOG.items()):
         out.append("closure parity %-28s stage %2d: loss rel err max %.2e (bound %.0e)  gradient rel err max %.2e (bound %.0e)  [%d frames]"
                    % (label, stage, le, lt, ge, gt, n))
+    for (label, stage, name), (err, share, bound, n) in sorted(BLOCK_LOG.items()):
+        if bound is None:
+            out.append("closure block  %-28s stage %2d %-16s reference exactly zero: device exactly zero  [%d frames]" % (label, stage, name, n))
+        else:
+            out.append("closure block  %-28s stage %2d %-16s rel err max %.2e (bound %.1e)  share min %.1e  [%d frames]"
+                       % (label, stage, name, err, bound, share, n))
     return out

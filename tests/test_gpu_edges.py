@@ -221,9 +221,13 @@ def test_halpe_closure_matches_oracle(synth_model):
     assert fb.n_stages == 3
     for stage in (-1, 0, 2):
         loss, grad = fb.closure(stage)
+        ref = []
         for i in range(B):
-            lo, go = T._oracle_closure(synth_model, cfg, frames, i, P, stage)
+            lo, go, go32, blocks = T._oracle_closure_blocks(synth_model, cfg, frames, i, P, stage)
+            ref.append((go, go32))
             H.check_closure("halpe-full-rows", stage, loss[i], lo, grad[i], go)
+        H.assert_blocks_tile(blocks, fb.num_vars(stage))
+        H.check_closure_blocks("halpe-full-rows", stage, grad, np.stack([r[0] for r in ref]), np.stack([r[1] for r in ref]), blocks)
 
 
 @pytest.mark.parametrize("n,extra", [(2, ["--lbs", "rows"]), (2, ["--workload", "pen"]), (4, [])], ids=["body-rows-2", "pen-dense-2", "body-dense-4"])
@@ -442,12 +446,20 @@ def test_use_pca_false_closure_matches_oracle(synth_model, mode):
     try:
         for stage in (-1, 0, 2):
             loss, grad = fb.closure(stage)
+            ref = []
             for i in range(B):
-                lo, go = T._oracle_closure(synth_model, cfg, frames, i, P, stage)
+                lo, go, go32, blocks = T._oracle_closure_blocks(synth_model, cfg, frames, i, P, stage,
+                                                                key=(("pca-off",) + T._cfg_key(cfg), "far", B, 21))
                 if stage >= 0:
                     assert go.size == 248 and np.all(go[13:76] == 0)
-                    go = np.concatenate([go[:13], go[76:]])          # (the dead body_pose parameter is not a device variable here)
+                    # (the dead body_pose parameter is not a device variable here)
+                    blocks, keep = H.without_block(blocks, "body_pose")
+                    assert np.array_equal(keep, np.r_[0:13, 76:248]) and np.all(go32[13:76] == 0)
+                    go, go32 = go[keep], go32[keep]
+                ref.append((go, go32))
                 H.check_closure("pca-off-full-%s" % mode, stage, loss[i], lo, grad[i], go)
+            H.assert_blocks_tile(blocks, fb.num_vars(stage))
+            H.check_closure_blocks("pca-off-full-%s" % mode, stage, grad, np.stack([r[0] for r in ref]), np.stack([r[1] for r in ref]), blocks)
     finally:
         H.oracle_model = orig
 

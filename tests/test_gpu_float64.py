@@ -72,11 +72,17 @@ def _probe(model, dm, cfg, frames, label, seed):
         loss, grad = fb.closure(stage)
         assert loss.dtype == np.float64 and grad.dtype == np.float64
         np.testing.assert_array_equal(fb.last_grad(stage), grad)
+        ref = []
         for i in range(B):
-            lo, go = T._oracle_closure(model, cfg, frames, i, P, stage, dtype=torch.float64)
+            lo, go, go32, blocks = T._oracle_closure_blocks(model, cfg, frames, i, P, stage)
+            ref.append((go, go32))
             H.check_closure(label, stage, loss[i], lo, grad[i], go, loss_tol=LOSS_TOL, grad_tol=GRAD_TOL)
             if stage >= 0:
                 assert np.all(grad[i][13:13 + 63] == 0)      # the dead body_pose parameter
+        # every parameter block: the float32 oracle's own error in the block, scaled to float64's unit roundoff
+        H.assert_blocks_tile(blocks, fb.num_vars(stage))
+        H.check_closure_blocks(label, stage, grad, np.stack([r[0] for r in ref]), np.stack([r[1] for r in ref]), blocks,
+                               floor=GRAD_TOL, unit_ratio=H.F64_UNIT_RATIO)
     fb.close()
 
 

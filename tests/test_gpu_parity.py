@@ -3,8 +3,12 @@ C ABI (ctypes), against the CPU oracle on identical seeded inputs.
 
 Tolerances (fp32 path; north_star asks 1e-4 relative):
   LBS vertices / joints     abs 5e-6 m on ~1 m geometry (vs oracle fp32), 1e-5 vs oracle fp64
-  closure loss              rel 1e-5  (helpers.CLOSURE_LOSS_TOL; observed maxima are printed at session end)
-  closure gradient          ||g - g_ref|| / ||g_ref|| < 1e-4 (helpers.CLOSURE_GRAD_TOL; vs oracle fp64 autograd)
+  closure loss              rel 4e-6  (helpers.CLOSURE_LOSS_TOL; SURVEY 8d asks 1e-5; observed maxima are printed at session end)
+  closure gradient          ||g - g_ref|| / ||g_ref|| <= 6e-6 over the whole variable vector (helpers.CLOSURE_GRAD_TOL; vs oracle
+                            fp64 autograd), and per parameter block b (helpers.check_closure_blocks):
+                            ||g_b - g_ref_b|| / ||g_ref_b|| <= max(6e-6, 10 x the float32 oracle's own error in that block
+                            against the float64 oracle at the same points); a block whose reference is exactly zero (the dead
+                            body_pose) is exactly zero on the device
   end-to-end stage losses   rel 2e-3 on well-posed synthetic frames (the reference's own
                             fp32-vs-fp64 spread on such frames is 6e-5 .. 1e-3)
 """
@@ -76,6 +80,11 @@ def test_lbs_forward_dense_matches_oracle(gpu, synth_model, cfg_full):
 
 def _oracle_closure(model, cfg, frames, i, params, stage, dtype=torch.float64):
     """loss + flat gradient (reference variable order) of the oracle objective at `params`."""
+    return _oracle_closure_ff(model, cfg, frames, i, params, stage, dtype)[:2]
+
+
+def _oracle_closure_ff(model, cfg, frames, i, params, stage, dtype):
+    """_oracle_closure's pair and the oracle.fit_frame.FrameFit it was evaluated on."""
     ff = H.oracle_frame_fit(model, cfg, frames, i, dtype=dtype)
     bm = ff.bm
     with torch.no_grad():
@@ -106,26 +115,91 @@ def _oracle_closure(model, cfg, frames, i, params, stage, dtype=torch.float64):
     loss = fn()
     loss.backward()
     g = torch.cat([(p.grad.reshape(-1) if p.grad is not None else torch.zeros(p.numel(), dtype=dtype)) for p in ps])
-    return loss.item(), g.numpy()
+    return loss.item(), g.numpy(), ff
 
 
-def closure_probe(model, cfg, mode, label, B=3, seed=11, stages=None, vposer=None, check=True):
-    """HIP closure (through the C ABI) against fp64 autograd of the oracle at B seeded random points of B synthetic
-    frames, camera stage + body stages.  Returns {stage: (max loss rel err, max gradient rel err)}; with check=True every
-    comparison also goes through helpers.check_closure (bounds 1e-5 / 1e-4).  Used by the tests below,
-    __graft_entry__.smoke() and bench.py's closure_parity object."""
-    dm = _dm(model, cfg, **({"vposer": vposer} if vposer is not None else {}))
-    frames = synth_frames(model, cfg, B)
-    fb = H.engine_batch_from_frames(dm, cfg, frames, range(B), lbs_mode=mode)
+_ORACLE_CACHE = {}
+
+
+def _point_digest(model, frames, params, i):
+    """What an oracle result depends on beside the cfg: the model's geometry and skinning, the frame's keypoints, the point."""
+    import hashlib
+    h = hashlib.sha1()
+    for a in (model["v_template"], model["weights"], frames["keypoints"][i]):
+        h.update(np.ascontiguousarray(np.asarray(a)).tobytes())
+    for k in sorted(params):
+        h.update(k.encode()); h.update(np.ascontiguousarray(np.asarray(params[k])[i:i + 1]).tobytes())
+    return h.hexdigest()
+
+
+def _oracle_closure_blocks(model, cfg, frames, i, params, stage, key=None):
+    """_oracle_closure in float64 and in float32 at the same point, with the parameter blocks of the flat gradient:
+    (loss64, grad64, grad32, blocks).  `key` = (cfg name, point set name) caches the result per (key, frame, stage, dtype) for
+    the session, so that the rows and the dense test of one cfg share one CPU evaluation (the oracle is the slow part); a cached
+    entry is only handed back for the very same model, frame and parameter values."""
+    out = []
+    for dtype in (torch.float64, torch.float32):
+        k = None if key is None else (tuple(key), int(i), int(stage), dtype)
+        dig = None if k is None else _point_digest(model, frames, params, i)
+        if k is not None and k in _ORACLE_CACHE:
+            assert _ORACLE_CACHE[k][0] == dig, ("oracle cache key reused for another model, frame or point", k)
+            out.append(_ORACLE_CACHE[k][1:])
+            continue
+        lo, go, ff = _oracle_closure_ff(model, cfg, frames, i, params, stage, dtype)
+        go.setflags(write=False)                 # (shared among the tests that ask for it)
+        blocks = tuple(H.gradient_blocks(ff, stage))
+        if k is not None:
+            _ORACLE_CACHE[k] = (dig, lo, go, blocks)
+        out.append((lo, go, blocks))
+    (lo, go, blocks), (_, go32, _) = out
+    return lo, go, go32, blocks
+
+
+def far_points(frames, B, seed, nemb=None, npca=12):
+    """Point set (a) of the closure tests: B seeded random points far from the solution (every block of
+    helpers.random_params at scale 0.5, pose and orientation 0.1 rad off the regression prior, camera 0.3 m off, depth prior
+    1 m off).  nemb: the length of a VPoser latent (N(0, 1)) in place of the 63 pose angles."""
     rng = np.random.RandomState(seed)
-    P = H.random_params(rng, B, scale=0.5)
-    if vposer is not None:
-        P["pose_embedding"] = rng.normal(size=(B, fb.nemb)).astype(np.float32)
+    P = H.random_params(rng, B, scale=0.5, npca=npca)
+    if nemb is not None:
+        P["pose_embedding"] = rng.normal(size=(B, nemb)).astype(np.float32)
     else:
         P["pose_embedding"] = frames["reg_pose"] + 0.1 * rng.normal(size=(B, 63)).astype(np.float32)
     P["global_orient"] = frames["reg_global"] + 0.1 * rng.normal(size=(B, 3)).astype(np.float32)
     P["cam_translation"] = (frames["cam_t"] + 0.3 * rng.normal(size=(B, 3))).astype(np.float32)
     est = (frames["cam_t"][:, 2] + 1.0).astype(np.float32)
+    return P, est
+
+
+def near_points(frames, B, nemb=None, seed=23):
+    """Point set (b): B seeded points near the solution, from the frames' ground truth (no fit is run): betas 0.02, pose,
+    orientation and camera 0.01 off the truth, the depth prior at the true depth, every other block of
+    helpers.random_params at scale 0.02.  nemb: a VPoser latent (whose truth is not known) 0.1 N(0, 1).  The data residual is
+    about the keypoint noise here, and the pose and shape blocks carry the gradient's norm, not the jaw prior."""
+    rng = np.random.RandomState(seed)
+    tr = frames["truth"]
+    P = H.random_params(rng, B, scale=0.02)
+    P["betas"] = (tr["betas"][:B] + 0.02 * rng.normal(size=(B, 10))).astype(np.float32)
+    if nemb is not None:
+        P["pose_embedding"] = (0.1 * rng.normal(size=(B, nemb))).astype(np.float32)
+    else:
+        P["pose_embedding"] = (tr["body_pose"][:B] + 0.01 * rng.normal(size=(B, 63))).astype(np.float32)
+    P["global_orient"] = (tr["global_orient"][:B] + 0.01 * rng.normal(size=(B, 3))).astype(np.float32)
+    P["cam_translation"] = (frames["cam_t"][:B] + 0.01 * rng.normal(size=(B, 3))).astype(np.float32)
+    est = frames["cam_t"][:B, 2].astype(np.float32).copy()
+    return P, est
+
+
+def closure_probe(model, cfg, mode, label, B=3, seed=11, stages=None, vposer=None, check=True):
+    """HIP closure (through the C ABI) against fp64 autograd of the oracle at B seeded random points of B synthetic
+    frames, camera stage + body stages.  Returns {stage: (max loss rel err, max gradient rel err)}; with check=True every
+    comparison also goes through helpers.check_closure (loss 4e-6, whole-vector gradient 6e-6 relative) and every parameter
+    block of the gradient through helpers.check_closure_blocks (max(6e-6, 10 x the float32 oracle's own error in that block);
+    the dead body_pose exactly zero).  Used by the tests below, __graft_entry__.smoke() and bench.py's closure_parity object."""
+    dm = _dm(model, cfg, **({"vposer": vposer} if vposer is not None else {}))
+    frames = synth_frames(model, cfg, B)
+    fb = H.engine_batch_from_frames(dm, cfg, frames, range(B), lbs_mode=mode)
+    P, est = far_points(frames, B, seed, nemb=fb.nemb if vposer is not None else None)
     fb.set_frames(frames["keypoints"], _jw(cfg, frames), _cmask(cfg, frames), frames["focal"],
                   np.tile([frames["W"] * 0.5, frames["H"] * 0.5], (B, 1)), 1000.0 / frames["H"], est_tz=est)
     if vposer is not None:
@@ -137,13 +211,21 @@ def closure_probe(model, cfg, mode, label, B=3, seed=11, stages=None, vposer=Non
     for stage in ([-1] + list(range(fb.n_stages)) if stages is None else stages):
         loss, grad = fb.closure(stage)
         le_max = ge_max = 0.0
+        ref = []
         for i in range(B):
-            lo, go = _oracle_closure(model, cfg, frames, i, P, stage)
+            if check:
+                lo, go, go32, blocks = _oracle_closure_blocks(model, cfg, frames, i, P, stage, key=(_cfg_key(cfg), "far", B, seed))
+                ref.append((go, go32))
+            else:
+                lo, go = _oracle_closure(model, cfg, frames, i, P, stage)
             le, ge = H.check_closure(label, stage, loss[i], lo, grad[i], go) if check else H.closure_errors(loss[i], lo, grad[i], go)
             le_max, ge_max = max(le_max, le), max(ge_max, ge)
             # the dead body_pose parameter receives no gradient (fit_single_frame.py:554-559)
             if stage >= 0 and not cfg["use_vposer"]:
                 assert np.all(grad[i][13:13 + 63] == 0)
+        if check:
+            H.assert_blocks_tile(blocks, fb.num_vars(stage))
+            H.check_closure_blocks(label, stage, grad, np.stack([r[0] for r in ref]), np.stack([r[1] for r in ref]), blocks)
         out[stage] = (le_max, ge_max)
     fb.close(); dm.close()
     return out
@@ -183,6 +265,13 @@ def _cmask(cfg, frames):
 
 
 _FRAME_CACHE = {}
+
+
+def _cfg_key(cfg):
+    """What distinguishes the oracle objective of one cfg of this suite from another's (the key of _ORACLE_CACHE)."""
+    return (cfg["use_hands"], cfg["use_face"], cfg.get("format", "coco25"), bool(cfg.get("use_face_contour")),
+            bool(cfg.get("use_vposer")), bool(cfg.get("use_camera_prior")), str(cfg.get("float_dtype")),
+            bool(cfg.get("interpenetration")), str(cfg.get("body_prior_type")))
 
 
 def synth_frames(model, cfg, n):
@@ -612,9 +701,13 @@ def test_closure_with_vposer_matches_oracle(gpu, synth_model):
         Q = dict(P); Q["est_tz"] = est
         for stage in (-1, 0, 3, 4):
             loss, grad = fb.closure(stage)
+            ref = []
             for i in range(B):
-                lo, go = _oracle_closure(synth_model, cfg, frames, i, Q, stage)
+                lo, go, go32, blocks = _oracle_closure_blocks(synth_model, cfg, frames, i, Q, stage, key=(_cfg_key(cfg), "far", B, 5))
+                ref.append((go, go32))
                 H.check_closure("vposer-full-%s" % mode, stage, loss[i], lo, grad[i], go)
+            H.assert_blocks_tile(blocks, fb.num_vars(stage))
+            H.check_closure_blocks("vposer-full-%s" % mode, stage, grad, np.stack([r[0] for r in ref]), np.stack([r[1] for r in ref]), blocks)
         # decoded body pose of the accepted latent
         bp = fb.get_params()["body_pose"]
         from oracle.vposer import VPoserRef
