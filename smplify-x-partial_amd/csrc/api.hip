@@ -119,7 +119,7 @@ const int* sfx_pen_stats_dev(const sfx_pen* h);
 
 extern "C" void sfx_batch_destroy(sfx_batch* b);
 // Who owns what: a model owns its constants (mem), the batch behind sfx_lbs_forward and the idle collision handle; a batch owns
-// its state (mem), its trace, pinned poll buffers, events, capture stream, graphs, and the collision handle while it lives.  Each
+// its state (mem), its trace, pinned poll buffers, events, capture stream, second stream, graphs, and the collision handle while it lives.  Each
 // handle releases all of it in its destructor and nowhere else: sfx_*_destroy and every failing exit of sfx_*_create end there.
 struct sfx_model {
     DevModel M{};
@@ -127,6 +127,8 @@ struct sfx_model {
     std::vector<int> faces_host, segm_host, parents_host, ign_host;   // interpenetration set-up
     int NB = 0, NE = 0, NPCA = 0;
     std::vector<int> meta_host;   // DevModel.meta
+    const int *tile_key = nullptr, *tile_rest = nullptr;      // the dense GEMM's tiles by consumer (model_tables.h), owned by mem
+    int n_key = 0, n_rest = 0;
     sfx_batch* fwd = nullptr;     // lazily created batch behind sfx_lbs_forward
     int fwd_B = 0;
     // The collision buffers of the interpenetration term (~45 MB per GEMM column: 11.5 GB for 256 columns) outlive the batch that
@@ -152,6 +154,13 @@ struct sfx_model {
 // depth: decisions (retirement, admission, compaction, the end) lag by ahead x 8 rounds; finished frames only ever stay
 // finished, and the surplus rounds at the end run on empty launches (0.1 % of a 256-frame fit at depth 3).
 #define SFX_POLL_BUFS 8
+#define SFX_OV_EVENTS 4      // events per ring of the overlapped dense loop: E_G of rounds i, i - 1, i - 2 are alive at once
+#ifndef SFX_OV_MAX
+#define SFX_OV_MAX 256       // ... and so do rounds at more columns than this: beyond a tick workgroup per CU both kernels fill the chip
+#endif
+#ifndef SFX_OV_SERIAL
+#define SFX_OV_SERIAL 160    // rounds at this many active GEMM columns or fewer stay serial on one stream
+#endif
 struct sfx_batch {
     sfx_model* m = nullptr;
     BatchDev D{};
@@ -165,6 +174,12 @@ struct sfx_batch {
     int* act_new_dev = nullptr;   // [B] frames admitted at the latest poll (export-only launch)
     int slots = 0;                // GEMM columns of the fused dense loop (0: one per frame)
     hipEvent_t poll_ev[SFX_POLL_BUFS] = {};
+    // the overlapped dense loop (run_ticks): the second and third set of GEMM operand buffers (owned by mem; D.featR / D.AT
+    // name the set of the most recent evaluation, whichever that is), the stream of the rest-tile GEMMs and the two rings of events that
+    // order them against the tick kernels; stream and events are made by the first fit that overlaps
+    float *featR_o[2] = {nullptr, nullptr}, *AT_o[2] = {nullptr, nullptr};      // [0] the next export's target, [1] the one after
+    hipStream_t s2 = nullptr;
+    hipEvent_t ov_ev[2][SFX_OV_EVENTS] = {};
     std::vector<int> slot_host;
     int K = 0;
     sfx_pen* pen = nullptr;       // interpenetration operator (cfg.interpenetration)
@@ -189,6 +204,8 @@ struct sfx_batch {
     ~sfx_batch() {
         for (auto& kv : pen_graphs) hipGraphExecDestroy(kv.second);
         if (cap_stream) hipStreamDestroy(cap_stream);
+        if (s2) { (void)hipStreamSynchronize(s2); hipStreamDestroy(s2); }      // (run_ticks drains it on every way out: nothing is pending)
+        for (auto& ring : ov_ev) for (hipEvent_t e : ring) if (e) hipEventDestroy(e);
         if (pen) {             // the collision buffers go back to the model's idle slot (see sfx_model)
             (void)hipDeviceSynchronize();
             std::lock_guard<std::mutex> lk(m->pen_mu);
@@ -263,6 +280,8 @@ extern "C" int sfx_model_create(const sfx_model_desc* d, sfx_model** out) {
     M.dynp_us = T.dynp_us.empty() ? nullptr : mem.up(T.dynp_us);
     M.vslot = mem.up(T.vslot); M.item_uslot = mem.up(T.item_uslot);
     M.meta = mem.up(T.meta);
+    m->tile_key = mem.up(T.tile_key); m->tile_rest = mem.up(T.tile_rest);
+    m->n_key = (int)T.tile_key.size(); m->n_rest = (int)T.tile_rest.size();
     m->meta_host = std::move(T.meta); m->faces_host = std::move(T.faces);
     if (mem.failed) { (void)hipGetLastError(); sfx_set_error("out of device memory (model constants)"); return -2; }
     if (hipDeviceSynchronize() != hipSuccess) { sfx_set_error("model upload failed"); return -2; }
@@ -440,6 +459,13 @@ extern "C" int sfx_batch_create(sfx_model* m, const sfx_batch_cfg* c, const sfx_
     D.bodypose = b->mem.zeros<float>((size_t)B * 63);
     D.featR = b->mem.zeros<float>((size_t)SFX_KD_PAD * D.Bpad);
     D.AT = b->mem.zeros<float>((size_t)12 * SFX_JPAD * D.Bpad);
+    D.featR_w = D.featR; D.AT_w = D.AT;
+    if (c->lbs_mode == 1 && !D.cfg.pen) {
+        for (int i = 0; i < 2; ++i) {
+            b->featR_o[i] = b->mem.zeros<float>((size_t)SFX_KD_PAD * D.Bpad);
+            b->AT_o[i] = b->mem.zeros<float>((size_t)12 * SFX_JPAD * D.Bpad);
+        }
+    }
     D.verts = b->mem.zeros<float>((size_t)B * m->M.V * 3);
     D.fwd = b->mem.zeros<float>((size_t)B * SFX_FWD_N);
     D.uvp = b->mem.zeros<float>((size_t)B * std::max(1, m->M.n_uniq) * 3);
@@ -1017,6 +1043,51 @@ static int run_ticks(sfx_batch* b, int first_stage, int last_stage, int init, in
         constexpr bool dbg_nact = false, dbg_host = false;
         constexpr int rpb_env = 0, ahead_env = 0;
 #endif
+        // GEMM beside tick (no interpenetration term, whose step needs every vertex before the tick).  Of the GEMM of evaluation i
+        // the tick kernel reads D.uvp only -- the blend offsets of the keypoint vertices: the key tiles, a twentieth of the mesh
+        // body-only.  Round i is therefore
+        //     stream s :  Gk(i) key tiles, reads cur | record E_K(i) | wait E_G(i-2) | T(i) reads uvp, exports evaluation i + 1 to nxt
+        //     stream s2:  wait E_K(i) | Gr(i) every other tile, reads cur | record E_G(i)
+        // over THREE sets of operand buffers: cur = D.featR / D.AT, nxt = b->featR_o[0] / AT_o[0], and the set Gr(i-1) may still
+        // be reading, b->featR_o[1] / AT_o[1]; the host rotates them after every tick launch (the kernels take BatchDev by value
+        // and know no parity).  T(i) overwrites what Gr(i-2) read, hence its wait, which never blocks in practice: with two
+        // sets T(i) had to wait for Gr(i-1) and then raced Gr(i) for the CUs -- a tick workgroup needs 300 to 512 registers per
+        // SIMD free and starves behind the GEMM's small workgroups (measured: 99 instead of 46 us per tick launch at 256
+        // frames, no gain).  With three, T(i) is queued while Gr(i-1) drains and takes the CUs as they empty; Gr(i) fills what
+        // is left.  Gr(i) waits for Gk(i), not only for T(i-1): beside Gk it would slow the round's critical path.
+        // A finished frame's workgroup copies its column of cur to nxt for as long as it is listed (fused.hip).  Admission and compaction
+        // exports write cur IN PLACE once s has waited for the latest Gr -- the columns of the frames that keep running hold
+        // their pending evaluation in cur only.  Two records and two waits per round; no other cross-stream traffic.
+        // Rule kept (LAB_NOTES "GEMM beside tick"): rounds at <= ov_serial active columns stay serial on s -- a short rest GEMM
+        // saves less than it costs the tick kernel it runs beside (frames/s by threshold: 32: 581, 96: 597, 160: 605, 192: 603;
+        // serial loop 563) -- and so do rounds at more than SFX_OV_MAX columns (1 024 frames through the
+        // 512-column pool lost 6 % overlapped: two tick workgroups per CU and a GEMM that fills the chip leave nothing to
+        // share); the eight-wavefront tick kernel at every size (the four-wavefront one shares
+        // its CU with GEMM workgroups and then takes 101 instead of 58 us per launch).
+#ifdef SFX_LAB
+        static const bool ov_on = [] { const char* e = getenv("SFX_DENSE_OVERLAP"); return !(e && *e && atoi(e) == 0); }();
+        static const int ov_serial = [] { const char* e = getenv("SFX_OVERLAP_SERIAL"); return e && *e ? atoi(e) : SFX_OV_SERIAL; }();
+#else
+        constexpr bool ov_on = true;
+        constexpr int ov_serial = SFX_OV_SERIAL;
+#endif
+        const bool overlap = ov_on && !b->pen && b->featR_o[0] && b->featR_o[1] && b->AT_o[0] && b->AT_o[1];
+        if (overlap && !b->s2) {
+            int lo = 0, hi = 0;
+            SFX_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));         // (lowest priority: the key tiles and the tick are the round's critical path)
+            SFX_CHECK(hipStreamCreateWithPriority(&b->s2, hipStreamNonBlocking, lo));
+            for (auto& ring : b->ov_ev) for (hipEvent_t& e : ring) SFX_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        }
+        // every way out of this block leaves both streams drained and the export pointed back at D.featR / D.AT
+        struct OvDrain { sfx_batch* b; hipStream_t s;
+                         ~OvDrain() { if (b->s2) (void)hipStreamSynchronize(b->s2); (void)hipStreamSynchronize(s); b->D.featR_w = b->D.featR; b->D.AT_w = b->D.AT; } } ov_drain{b, s};
+        hipEvent_t last_G = nullptr, prev_G = nullptr;     // E_G of the latest overlapped round and of the one before (NULL: s has waited for it)
+        long ov_i = 0;
+        auto join_s2 = [&]() -> int {                       // before s writes operands in place: every Gr has read them
+            if (last_G) SFX_CHECK(hipStreamWaitEvent(s, last_G, 0));
+            last_G = prev_G = nullptr;
+            return 0;
+        };
         static long nact_hist[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};      // rounds by active GEMM columns: <=32, <=64, ..., <=256, more
         const int pool = b->slots > 0 ? std::min(b->slots, B) : B;
         std::vector<int>& col = b->slot_host;                          // frame -> column, -1 = queued or retired
@@ -1051,6 +1122,24 @@ static int run_ticks(sfx_batch* b, int first_stage, int last_stage, int init, in
             struct HostClock { const std::chrono::steady_clock::time_point t0; double& acc; long& n; bool on;
                                ~HostClock() { if (on) { acc += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); ++n; } } } hc{h0, host_enq_s, host_batches, true};
             for (int q = 0; q < rpb; ++q, ++tick) {
+                if (overlap && D.nact > ov_serial && D.nact <= SFX_OV_MAX) {
+                    const int k = (int)(ov_i++ % SFX_OV_EVENTS);
+                    if (b->m->n_key) { ProfScope p("lbs_dense_key", s, D.nact); launch_lbs_dense_list(M, D, b->m->tile_key, b->m->n_key, s); }
+                    SFX_CHECK(hipEventRecord(b->ov_ev[0][k], s));
+                    SFX_CHECK(hipStreamWaitEvent(b->s2, b->ov_ev[0][k], 0));
+                    { ProfScope p("lbs_dense", b->s2, D.nact); launch_lbs_dense_list(M, D, b->m->tile_rest, b->m->n_rest, b->s2); }
+                    SFX_CHECK(hipEventRecord(b->ov_ev[1][k], b->s2));
+                    if (prev_G) SFX_CHECK(hipStreamWaitEvent(s, prev_G, 0));
+                    prev_G = last_G; last_G = b->ov_ev[1][k];
+                    BatchDev Dt = D; Dt.featR_w = b->featR_o[0]; Dt.AT_w = b->AT_o[0];
+                    { ProfScope p("tick", s, D.nrun);
+                      launch_tick_dense(M, Dt, b->vl_dev, b->sw_dev, first_stage, last_stage, 1, s); }
+                    float* const f = D.featR; D.featR = b->featR_o[0]; b->featR_o[0] = b->featR_o[1]; b->featR_o[1] = f;
+                    float* const a = D.AT; D.AT = b->AT_o[0]; b->AT_o[0] = b->AT_o[1]; b->AT_o[1] = a;
+                    D.featR_w = D.featR; D.AT_w = D.AT;
+                    continue;
+                }
+                if (int rc = join_s2()) return rc;
                 { ProfScope p("lbs_dense", s, D.nact); launch_lbs_dense(M, D, s); }
                 if (int rc = eval_penetration(b, -2, s, true)) return rc;
                 ProfScope p("tick", s, D.nrun);
@@ -1091,6 +1180,7 @@ static int run_ticks(sfx_batch* b, int first_stage, int last_stage, int init, in
             if (!done && changed) {
                 if (!fresh.empty()) {
                     // admission: the new frames inherit the freed columns; only they need an export pass
+                    if (int rc = join_s2()) return rc;
                     if (int rc = upload(&fresh)) return rc;
                     BatchDev Dn = D; Dn.act = b->act_new_dev; Dn.nrun = (int)fresh.size();
                     ProfScope p("tick_admit", s, Dn.nrun);
@@ -1102,6 +1192,7 @@ static int run_ticks(sfx_batch* b, int first_stage, int last_stage, int init, in
                     int q = 0;
                     for (int f : run) col[f] = q++;
                     D.nact = q;
+                    if (int rc = join_s2()) return rc;
                     if (int rc = upload(nullptr)) return rc;
                     ProfScope p("tick", s, D.nrun);
                     launch_tick_dense(M, D, b->vl_dev, b->sw_dev, first_stage, last_stage, 0, s);   // re-export only
@@ -1110,6 +1201,7 @@ static int run_ticks(sfx_batch* b, int first_stage, int last_stage, int init, in
                 }
             }
         }
+        if (b->s2) SFX_CHECK(hipStreamSynchronize(b->s2));
         SFX_CHECK(hipStreamSynchronize(s));
         D.act = nullptr; D.nrun = 0;
         const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - wall0;

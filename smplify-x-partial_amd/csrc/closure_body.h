@@ -584,11 +584,11 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
         // coefficients of this frame: one contiguous 2-KiB row (entries >= KD are zero).  (As a COLUMN of a [K][frames]
         // matrix -- what the GEMM's A operand looks like in LDS -- these were 506 scattered 4-byte writes per frame into
         // lines shared by 32 frames: 10 k cycles of the launch; the GEMM transposes while staging instead.)
-        if (t < SFX_KD_PAD / 4) reinterpret_cast<float4*>(D.featR + (size_t)slot * SFX_KD_PAD)[t] = reinterpret_cast<const float4*>(S.feat)[t];
+        if (t < SFX_KD_PAD / 4) reinterpret_cast<float4*>(D.featR_w + (size_t)slot * SFX_KD_PAD)[t] = reinterpret_cast<const float4*>(S.feat)[t];
         MARK(17);
         for (int i = t; i < SFX_J * 12; i += CT) {
             const int j = i / 12, e = i % 12;
-            D.AT[((size_t)e * SFX_JPAD + j) * D.Bpad + slot] = S.A[i];
+            D.AT_w[((size_t)e * SFX_JPAD + j) * D.Bpad + slot] = S.A[i];
         }
         MARK(18);
         if (args.forward_only == 2) {           // export pass only: keep the forward state for the adjoint pass

@@ -45,6 +45,21 @@ void k_fit_rows(DevModel M, BatchDev D, const VarList* __restrict__ vls, const S
 // (small variant, OCC = 2: two workgroups per CU -- batches of more than 256 frames then run two latency-bound frames per
 //  CU; OCC = 1 is the same code with the whole register file, launched when every frame has a CU of its own: no spills,
 //  73.8 instead of 76.2 us per launch)
+// The overlapped loop (api.hip run_ticks) rotates three sets of GEMM operand buffers: the export pass writes featR_w / AT_w while
+// GEMMs in flight read featR / AT (the operands of the latest evaluation) and the third set.  A frame that has finished exports
+// no more, so its column would go on cycling through the operands of its last three evaluations and D.verts would end on any
+// of their meshes.  Its workgroup therefore copies the column from the set of the latest evaluation into the one that is
+// written now -- in the launch it finishes in and in every later one that still lists it (the host retires a frame at least
+// one polled batch of rounds after it finished): after two launches all three sets hold the operands of its last evaluation.
+// Only the set nobody reads is written: the loop has waited for the GEMM that read it.  Elsewhere featR_w == featR: nothing to do.
+__device__ __forceinline__ void copy_operand_column(const BatchDev& D, int slot, int nthreads) {
+    if (D.featR_w == D.featR) return;
+    const int t = threadIdx.x;
+    if (t < SFX_KD_PAD / 4)
+        reinterpret_cast<float4*>(D.featR_w + (size_t)slot * SFX_KD_PAD)[t] = reinterpret_cast<const float4*>(D.featR + (size_t)slot * SFX_KD_PAD)[t];
+    for (int i = t; i < 12 * SFX_JPAD; i += nthreads) D.AT_w[(size_t)i * D.Bpad + slot] = D.AT[(size_t)i * D.Bpad + slot];
+}
+
 template <class LDS, int OCC>
 __global__ __launch_bounds__(LDS::kThreads, OCC)
 void k_tick_dense(DevModel M, BatchDev D, const VarList* __restrict__ vls, const StageW* __restrict__ sws,
@@ -66,7 +81,10 @@ void k_tick_dense(DevModel M, BatchDev D, const VarList* __restrict__ vls, const
     __shared__ int s_stage;
     static_assert(sizeof(VarList) % 4 == 0 && sizeof(OptScal) % 4 == 0 && (NVEC * SFX_NVAR_MAX) % 4 == 0, "dword / 16-byte LDS-DMA");
     const int b = D.act ? D.act[blockIdx.x] : blockIdx.x;      // (frames that finished or still wait in the queue are not launched)
-    if (D.stage[b] > last_stage) return;
+    if (D.stage[b] > last_stage) {      // finished, and the host has not retired it yet: see copy_operand_column
+        if (has_eval) copy_operand_column(D, D.slot[b], CTK);
+        return;
+    }
     const long long wc0 = D.dbg ? wall_clock64() : 0;      // debug: per-workgroup duration statistics (100 MHz clock)
     // debug clocks: stamps freeze after launch number dbg[61] of this kernel, so a mid-fit launch is what is read back
     if (D.dbg && blockIdx.x == 0 && threadIdx.x == 0) { D.dbg[62] += 1; if (D.dbg[62] <= D.dbg[61]) D.dbg[24] = clock64(); }
@@ -100,6 +118,7 @@ void k_tick_dense(DevModel M, BatchDev D, const VarList* __restrict__ vls, const
         if (D.dbg && b == 0 && threadIdx.x == 0 && D.dbg[62] <= D.dbg[61]) { D.dbg[25] = clock64(); for (int i = 0; i < 17; ++i) D.dbg[40 + i] = D.dbg[i]; }
         if ((PF ? s_stage : D.stage[b]) > last_stage) {          // finished in this launch: its column carries no collision weight any more
             if (D.pen_want && threadIdx.x == 0) D.pen_want[D.slot[b]] = 0;
+            copy_operand_column(D, D.slot[b], CTK);
             return;
         }
     }

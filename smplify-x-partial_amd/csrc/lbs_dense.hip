@@ -10,13 +10,14 @@
 //                                >= 506 are zero); transposed to [k-chunk][frame] order while staged into LDS
 //   B operand  dirs[k][3*v + c] (the .npz posedirs layout [486, 3V]: 3 coords interleaved; rows
 //                                padded to 3*Vpad floats and to 512 rows)
-// Work unit = one wavefront = 16 vertices x 32 frames (two 16x16 MFMA tiles): 6 accumulators
-// (x,y,z) x 4 registers for v_posed, then per output row 4 x 2 accumulators of T fused with the
-// skinning epilogue, so v_posed and T never touch HBM.  Small units (about 17 us of MFMA time)
-// keep the 1024 SIMDs balanced for any number of active frames (the fit loop compacts finished
-// frames away), and 24 + 32 accumulator registers leave room for 3+ wavefronts per SIMD.
-// Workgroup = 4 wavefronts = 16 vertices x 128 frames; K is staged through LDS in 32-row chunks
-// (16 chunks), register-prefetched one chunk ahead; the wavefronts share the dirs chunk.
+// Work unit = one wavefront = 16 vertices x 16 frames (one 16x16 MFMA tile per coordinate): 3 accumulators (x,y,z) x 4
+// registers for v_posed, then per output row 4 accumulators of T fused with the skinning epilogue, so v_posed and T never
+// touch HBM.  Workgroup = W wavefronts (3, 4 or 5, picked by the number of active frames) = 16 vertices x 16 W frames; K is
+// staged through LDS in 32-row chunks (16 chunks), register-prefetched one chunk ahead; the wavefronts share the dirs chunk.
+// At <= 32 active frames the three coordinates of a slice go to three wavefronts instead (k_lbs_dense16c).
+// A launch covers either every 16-vertex tile or the tiles of a list (launch_lbs_dense_list): the fitting loop runs the few
+// tiles whose vertices the per-frame kernel reads back (model_tables.h tile_key) in front of that kernel and all the others
+// beside it.  Which launch a tile belongs to changes nothing in its arithmetic.
 // Algorithmic traffic per launch:
 //     66.0 MB of constants (dirs 61.1+2.5, W 2.3, template 0.1) + B * 125.7 KB of vertices.
 #include "sfx_internal.h"
@@ -75,7 +76,7 @@ struct __align__(16) DenseLDS16 {
 #endif
 template <int W>
 __global__ __launch_bounds__(64 * W, MINW16)
-void k_lbs_dense16(DevModel M, BatchDev D) {
+void k_lbs_dense16(DevModel M, BatchDev D, const int* __restrict__ list, int n_list) {      // list == NULL: all ceil(V / 16) tiles
     constexpr int DTW = 64 * W, FBW = 16 * W;
     static_assert(W >= 3 && W <= 8, "staging: two rounds of DTW threads cover the 384 float4 of a dirs chunk");
     __shared__ DenseLDS16<W> S;
@@ -83,11 +84,12 @@ void k_lbs_dense16(DevModel M, BatchDev D) {
     const int lane = tid & 63, wv = tid >> 6;
     int tile, fblk, fpb;
     {
-        const int ny = (D.nact + FBW - 1) / FBW, ntile = (M.V + VB - 1) / VB;
-        const int tpx = (ntile + 7) / 8;                        // tiles per XCD
+        const int ny = (D.nact + FBW - 1) / FBW, ntile = list ? n_list : (M.V + VB - 1) / VB;
+        const int tpx = (ntile + 7) / 8;                        // tiles (list positions) per XCD
         const int L = blockIdx.x, xcd = L & 7, slot = L >> 3;
-        tile = xcd * tpx + slot / ny; fblk = slot % ny;
-        if (tile >= ntile) return;
+        const int pos = xcd * tpx + slot / ny; fblk = slot % ny;
+        if (pos >= ntile) return;
+        tile = list ? list[pos] : pos;
         fpb = 16 * (((D.nact + 15) / 16 + ny - 1) / ny);        // frames dealt evenly to the frame blocks in 16-frame slices
     }
     const int v0 = tile * VB;
@@ -221,16 +223,17 @@ struct __align__(16) DenseLDS16c {
     float x[2][3][64][4];        // [slice][coordinate][lane][register]: v_posed accumulators on their way to the skinning rows
 };
 __global__ __launch_bounds__(384, 2)
-void k_lbs_dense16c(DevModel M, BatchDev D) {
+void k_lbs_dense16c(DevModel M, BatchDev D, const int* __restrict__ list, int n_list) {
     __shared__ DenseLDS16c S;
     const int tid = threadIdx.x;
     const int lane = tid & 63, wv = tid >> 6, sl = wv / 3, co = wv % 3;
     int tile;
     {
-        const int ntile = (M.V + VB - 1) / VB, tpx = (ntile + 7) / 8;
+        const int ntile = list ? n_list : (M.V + VB - 1) / VB, tpx = (ntile + 7) / 8;
         const int L = blockIdx.x, xcd = L & 7, slot = L >> 3;
-        tile = xcd * tpx + slot;
-        if (tile >= ntile || slot >= tpx) return;
+        const int pos = xcd * tpx + slot;
+        if (pos >= ntile || slot >= tpx) return;
+        tile = list ? list[pos] : pos;
     }
     const int v0 = tile * VB, b0 = sl * 16;
     const int jl = lane & 15, kq = lane >> 4;
@@ -331,6 +334,11 @@ static int g_lbs_dense_w = [] { const char* e = getenv("SFX_LBS_W"); const int v
 constexpr int g_lbs_dense_form = 16, g_lbs_dense_w = 0;
 #endif
 
+static void launch_lbs_dense16(const DevModel& M, const BatchDev& D, const int* list, int n_list, hipStream_t s);
+void launch_lbs_dense_list(const DevModel& M, const BatchDev& D, const int* list_dev, int n_list, hipStream_t s) {
+    if (D.nact <= 0 || n_list <= 0) return;
+    launch_lbs_dense16(M, D, list_dev, n_list, s);
+}
 void launch_lbs_dense(const DevModel& M, const BatchDev& D, hipStream_t s) {
     if (D.nact <= 0) return;
 #ifdef MF32
@@ -350,6 +358,11 @@ void launch_lbs_dense(const DevModel& M, const BatchDev& D, hipStream_t s) {
         return;
     }
 #endif
+    launch_lbs_dense16(M, D, nullptr, 0, s);
+}
+// the product kernels over all tiles (list == NULL) or over the n_list tiles of a device list
+static void launch_lbs_dense16(const DevModel& M, const BatchDev& D, const int* list, int n_list, hipStream_t s) {
+    const int ntile = list ? n_list : (M.V + VB - 1) / VB;
     {
         // frame blocks of at most 4 slices as in round 3, and the workgroup as wide as its busiest block: 6 and 9 slices are
         // blocks of 3 (W = 3: no idle wavefront, six workgroups per CU), 5 slices one block of 5; tools/bench_dense.py with
@@ -357,18 +370,17 @@ void launch_lbs_dense(const DevModel& M, const BatchDev& D, hipStream_t s) {
         // every other count is fastest (or as fast) at W = 4, and W = 6 .. 8 lose everywhere (measured, not instantiated)
         const int ns = (D.nact + 15) / 16, ny4 = (ns + 3) / 4;
         if (ns <= 2 && g_lbs_dense_form != 17 && !g_lbs_dense_w) {       // the tail of a fit: three coordinates on three wavefronts (same bits)
-            const int ntile_ = (M.V + VB - 1) / VB;
-            hipLaunchKernelGGL(k_lbs_dense16c, dim3(8 * ((ntile_ + 7) / 8)), dim3(384), 0, s, M, D);
+            hipLaunchKernelGGL(k_lbs_dense16c, dim3(8 * ((ntile + 7) / 8)), dim3(384), 0, s, M, D, list, n_list);
             return;
         }
         int w = ns <= 4 ? 4 : (ns == 5 ? 5 : std::max(3, (ns + ny4 - 1) / ny4));
         if (g_lbs_dense_w) w = g_lbs_dense_w;
-        const int ny = (ns + w - 1) / w, ntile = (M.V + VB - 1) / VB;
+        const int ny = (ns + w - 1) / w;
         dim3 grid(8 * ((ntile + 7) / 8) * ny);
         switch (w) {
-        case 3: hipLaunchKernelGGL(k_lbs_dense16<3>, grid, dim3(192), 0, s, M, D); break;
-        case 5: hipLaunchKernelGGL(k_lbs_dense16<5>, grid, dim3(320), 0, s, M, D); break;
-        default: hipLaunchKernelGGL(k_lbs_dense16<4>, grid, dim3(256), 0, s, M, D); break;
+        case 3: hipLaunchKernelGGL(k_lbs_dense16<3>, grid, dim3(192), 0, s, M, D, list, n_list); break;
+        case 5: hipLaunchKernelGGL(k_lbs_dense16<5>, grid, dim3(320), 0, s, M, D, list, n_list); break;
+        default: hipLaunchKernelGGL(k_lbs_dense16<4>, grid, dim3(256), 0, s, M, D, list, n_list); break;
         }
     }
 }

@@ -20,6 +20,9 @@ struct ModelTables {      // members named after the DevModel pointers they beco
     std::vector<int> dj_start, dj_item, dynp_vid, dynp_wj, dynp_js, dynp_ji, dynp_us;     // dynp_js empty: the rows do not fit
     std::vector<int> meta;        // [SFX_META_N] the MO_* blocks: tree, mapped joints, item owners
     std::vector<int> faces;       // host copy for the collision handle
+    // the dense GEMM's 16-vertex tiles (ceil(V / 16) of them) in two ascending lists: tile_key holds the tiles with at least
+    // one exported vertex (vslot >= 0: what the per-frame kernel reads back as uvp), tile_rest every other tile
+    std::vector<int> tile_key, tile_rest;
 };
 
 // The nonzero weights of vertex v in ascending joint order, packed into SFX_NW slots (pad: j = 0, w = 0).  A row with more
@@ -157,6 +160,11 @@ static inline int sfx_build_model_tables(const sfx_model_desc* d, ModelTables* o
     auto slot_of = [&](int v) { if (T.vslot[v] < 0) T.vslot[v] = T.n_uniq++; return T.vslot[v]; };
     for (int i = 0; i < ns; ++i) T.item_uslot[i] = slot_of(T.item_vid[i]);
     for (size_t o = 0; o < T.dynp_vid.size(); ++o) T.dynp_us[o] = slot_of(T.dynp_vid[o]);
+    for (int t = 0; t < (V + 15) / 16; ++t) {           // (vslot has Vpad >= 16 ceil(V / 16) entries, -1 beyond V)
+        bool key = false;
+        for (int q = 0; q < 16 && !key; ++q) key = T.vslot[(size_t)t * 16 + q] >= 0;
+        (key ? T.tile_key : T.tile_rest).push_back(t);
+    }
     // blend-shape matrix (shape | pose directions, zero beyond KD), vertex-major [V][3][KD_PAD] and tile-major
     // [Vpad/16][KD_PAD][16 vertices x 3 coordinates] (the lab build: and k-major [KD_PAD][3*Vpad])
     const size_t LD = (size_t)3 * T.Vpad;

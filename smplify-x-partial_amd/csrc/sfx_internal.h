@@ -253,6 +253,11 @@ struct BatchDev {
     double* f64;            // [B]
     double* g64;            // [B][NVAR_MAX]
     double* cam64;          // [B][8]
+    // where the export pass WRITES the GEMM operands.  Everywhere but in the overlapped dense loop (api.hip run_ticks) these are
+    // featR / AT themselves; there the rest-tile GEMM of evaluation i still reads featR / AT while the tick kernel exports
+    // evaluation i + 1, so the export goes to another set of buffers and the host rotates the sets after every tick launch
+    float* featR_w;         // [Bpad][KD_PAD]
+    float* AT_w;            // [12][JPAD][Bpad]
 };
 
 enum { VEC_XINIT = 0, VEC_D, VEC_G, VEC_PREVG, VEC_GPREV, VEC_BG0, VEC_BG1, VEC_LSG0, NVEC };
@@ -334,6 +339,8 @@ void launch_closure_ext(const DevModel& M, const BatchDev& D, const VarList* vl_
 void launch_scatter_gc(const BatchDev& D, const float* gc, const LbsGradOut& o, hipStream_t s);
 int sfx_adj_slices(const DevModel& M);
 void launch_lbs_dense(const DevModel& M, const BatchDev& D, hipStream_t s);
+// the same launch over the n_list tiles of an ascending device list (model_tables.h tile_key / tile_rest) instead of over all
+void launch_lbs_dense_list(const DevModel& M, const BatchDev& D, const int* list_dev, int n_list, hipStream_t s);
 #ifdef SFX_LAB
 extern int g_lbs_dense_form;          // 16 (k_lbs_dense16, default) | 17 (k_lbs_dense16 at every size) | 32 (k_lbs_dense)
 #endif
