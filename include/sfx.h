@@ -342,6 +342,52 @@ int  sfx_batch_get_stats(sfx_batch* b, float* stage_loss, int32_t* stage_evals,
 int  sfx_batch_trace(sfx_batch* b, int32_t capacity);
 int  sfx_batch_get_trace(sfx_batch* b, float* records, int32_t* counts);
 
+/* ---- the optimiser for evaluations the CALLER supplies (csrc/opt_ext.hip) ----------------------------------
+ * B independent problems of N <= 192 float32 variables each, advanced by the state machine of sfx_batch_fit / sfx_batch_step
+ * (one wavefront per problem, one evaluation per launch), in reverse communication: the handle says where it wants each problem
+ * evaluated, the caller evaluates loss and gradient there by any means (a torch loss and autograd, say) and hands them back.
+ * No problem waits for a decision of another one, and nothing but sfx_opt_active synchronises.
+ * Replaces FittingMonitor.run_fitting (smplifyx/fitting.py:147-217) over LBFGS(line_search_fn='strong_Wolfe').step
+ * (smplifyx/optimizers/lbfgs_ls.py:256-445, _strong_Wolfe / _cubic_interpolate :11-167) for an arbitrary closure.          */
+typedef struct sfx_opt sfx_opt;
+typedef struct sfx_opt_cfg {
+    int32_t B, N;
+    int32_t n_groups; int32_t group_len[12];   /* the tensors of `params`: run_fitting's gtol test is per tensor
+                                                  (fitting.py:191, abs(grad.max()) < gtol); 0 groups = one group of N */
+    int32_t maxiters; double ftol, gtol;       /* run_fitting (fitting.py:147-217); maxiters >= 1 */
+    float   lr;
+    double  tolerance_grad, tolerance_change;  /* negative = default 1e-5 / 1e-9; 0 is passed through */
+    int32_t max_iter, max_eval, history_size;  /* 0 = defaults, as in sfx_batch_cfg: maxiters, max_iter * 5 / 4, 100 */
+    int32_t reuse_entry_eval;                  /* as sfx_batch_cfg.reuse_entry_eval (mode 0) */
+} sfx_opt_cfg;
+/* The optimiser object of optim_factory.py:50-52 and the monitor's tolerances, for B problems.  Refused before any device memory
+ * is touched (-1): N outside 1..192, B < 1, more than 12 groups, group lengths that do not sum to N, history_size outside
+ * 0..400.  -3: no HIP device.  -2: out of device memory (nothing stays allocated).                                       */
+int  sfx_opt_create(const sfx_opt_cfg* cfg, sfx_opt** out);
+void sfx_opt_destroy(sfx_opt* h);
+/* Start a run.  mode 0: the whole run_fitting loop (fitting.py:174-217); mode 1: ONE LBFGS.step (lbfgs_ls.py:256-445) --
+ * resume = 1 continues the optimiser of the previous mode-1 run (history and counters kept, as sfx_batch_step), 0 starts a
+ * fresh one (lbfgs_ls.py:293-300) and empties the trace.  Copies x0_dev [B][N] (DEVICE) in and writes the first point to
+ * evaluate to x_trial_dev [B][N] (DEVICE).  Enqueues only.                                                                */
+int  sfx_opt_begin(sfx_opt* h, int32_t mode, int32_t resume, const float* x0_dev, float* x_trial_dev, void* stream);
+/* closure() of lbfgs_ls.py:279, :67 and :134, turned inside out: consume loss_dev [B] and grad_dev [B][N] (DEVICE, packed),
+ * evaluated at the current trial points, and write the next ones to x_trial_dev.  A problem that has finished is left alone:
+ * its loss and gradient are not read, its row of x_trial_dev -- its accepted point -- is not written.  Enqueues only,
+ * allocates nothing.                                                                                                     */
+int  sfx_opt_tell(sfx_opt* h, const float* loss_dev, const float* grad_dev, float* x_trial_dev, void* stream);
+/* Problems still running (HOST): the `while` of the caller's loop.  One 4-byte readback; synchronises the stream.        */
+int  sfx_opt_active(sfx_opt* h, int32_t* n_active_host, void* stream);
+/* What the reference leaves behind: the accepted point x_dev [B][N] (the parameters after step()) and grad_dev [B][N], the
+ * gradient of each problem's most recent consumed evaluation (var.grad, fitting.py:191) -- DEVICE, may be NULL; per problem
+ * (HOST, may be NULL): result -- mode 0 the value run_fitting returns (fitting.py:217; NaN for None), mode 1 the loss at entry
+ * (lbfgs_ls.py:445) --, evaluations consumed since the last fresh begin, status (0 running, 1 finished).  Synchronises.   */
+int  sfx_opt_get(sfx_opt* h, float* x_dev, float* grad_dev, float* result_host, int32_t* evals_host, int32_t* status_host);
+/* Optimiser trace: records as sfx_batch_trace (types 0, 1, 2; the stage of a type-2 record is 0).  capacity > 0 attaches a
+ * buffer of `capacity` records per problem, 0 detaches it; a fresh sfx_opt_begin empties it.
+ * sfx_opt_get_trace: records [B][capacity][4] and the number written per problem (HOST; counts may exceed capacity).      */
+int  sfx_opt_trace(sfx_opt* h, int32_t capacity);
+int  sfx_opt_get_trace(sfx_opt* h, float* records, int32_t* counts);
+
 /* Gaussian-mixture body pose prior (MaxMixturePrior, smplifyx/prior.py:100-231; body_prior_type 'gmm'):
  * used by the closure when use_vposer is off and the batch has no regression pose (fitting.py:399-401).
  * means [M][D], precisions [M][D][D], nll_weights [M] = the module's buffers; D = 63, M <= 8 (HOST). */

@@ -71,6 +71,16 @@ class BatchCfg(C.Structure):
     ]
 
 
+class OptCfg(C.Structure):
+    """sfx_opt_cfg: B problems of N variables, run_fitting's tolerances and the hyper-parameters of lbfgs_ls.LBFGS."""
+    _fields_ = [
+        ("B", C.c_int32), ("N", C.c_int32), ("n_groups", C.c_int32), ("group_len", C.c_int32 * 12),
+        ("maxiters", C.c_int32), ("ftol", C.c_double), ("gtol", C.c_double), ("lr", C.c_float),
+        ("tolerance_grad", C.c_double), ("tolerance_change", C.c_double),
+        ("max_iter", C.c_int32), ("max_eval", C.c_int32), ("history_size", C.c_int32), ("reuse_entry_eval", C.c_int32),
+    ]
+
+
 # every symbol include/sfx.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "sfx_model_create": (C.c_int, [C.POINTER(ModelDesc), C.POINTER(C.c_void_p)]),
@@ -112,6 +122,16 @@ SYMBOLS = {
     "sfx_batch_trace": (C.c_int, [C.c_void_p, C.c_int32]),
     "sfx_batch_get_trace": (C.c_int, [C.c_void_p, f32p, i32p]),
     "sfx_batch_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sfx_opt_create": (C.c_int, [C.POINTER(OptCfg), C.POINTER(C.c_void_p)]),
+    "sfx_opt_destroy": (None, [C.c_void_p]),
+    # handle, mode, resume, x0, x_trial, stream
+    "sfx_opt_begin": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # handle, loss, grad, x_trial, stream
+    "sfx_opt_tell": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sfx_opt_active": (C.c_int, [C.c_void_p, i32p, C.c_void_p]),
+    "sfx_opt_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, f32p, i32p, i32p]),
+    "sfx_opt_trace": (C.c_int, [C.c_void_p, C.c_int32]),
+    "sfx_opt_get_trace": (C.c_int, [C.c_void_p, f32p, i32p]),
     "sfx_pen_create": (C.c_int, [C.c_int32, C.c_int32, i32p, i32p, i32p, i32p, C.c_int32, C.c_int32, C.c_int32,
                                  C.POINTER(C.c_void_p)]),
     "sfx_pen_destroy": (None, [C.c_void_p]),

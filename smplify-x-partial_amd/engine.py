@@ -737,6 +737,146 @@ class FrameBatch(object):
             pass
 
 
+class BatchOptimizer(object):
+    """The engine's optimiser for losses the CALLER evaluates (sfx_opt_*, csrc/opt_ext.hip): B independent problems of N <= 192
+    float32 variables, each with its own run_fitting / LBFGS.step / strong-Wolfe state on the device (one wavefront per problem,
+    one evaluation of every running problem per launch).  Reverse communication over torch CUDA tensors:
+
+        opt.begin(x0)                        # [B][N]; opt.x_trial [B][N] now holds the first points to evaluate
+        while opt.active():                  # the loop's only host synchronisation (4 bytes)
+            loss, grad = evaluate(opt.x_trial)      # [B], [B][N], by any means: the device never sees the objective
+            opt.tell(loss, grad)             # opt.x_trial holds the next points; rows of finished problems stay put
+        r = opt.result()
+
+    groups: lengths of the tensors the N variables are made of (run_fitting's gtol test looks at each tensor's gradient,
+    fitting.py:191); None = one tensor.  Hyper-parameters: maxiters, ftol, gtol (FittingMonitor), lr, max_iter, max_eval,
+    history_size, tolerance_grad, tolerance_change (lbfgs_ls.LBFGS; defaults of oracle/lbfgs_machine.StageMachine, whose
+    spellings history / tol_grad / tol_change are accepted too), reuse_entry_eval.  There is no CPU fallback."""
+
+    _ALIASES = dict(history="history_size", tol_grad="tolerance_grad", tol_change="tolerance_change")
+
+    def __init__(self, B, N, groups=None, **hyper):
+        h = dict(maxiters=30, ftol=1e-9, gtol=1e-9, lr=1.0, max_iter=None, max_eval=None, history_size=100,
+                 tolerance_grad=1e-5, tolerance_change=1e-9, reuse_entry_eval=False)
+        for k, v in hyper.items():
+            k = self._ALIASES.get(k, k)
+            if k not in h:
+                raise TypeError("BatchOptimizer: unknown hyper-parameter %r (known: %s)" % (k, ", ".join(sorted(h))))
+            h[k] = v
+        lib = capi.load()
+        groups = [int(n) for n in groups] if groups is not None else []
+        c = capi.OptCfg()
+        c.B, c.N, c.n_groups = int(B), int(N), len(groups)
+        for i, n in enumerate(groups[:12]):      # (a longer list is refused by the library through n_groups)
+            c.group_len[i] = n
+        c.maxiters, c.ftol, c.gtol, c.lr = int(h["maxiters"]), float(h["ftol"]), float(h["gtol"]), float(h["lr"])
+        c.tolerance_grad, c.tolerance_change = float(h["tolerance_grad"]), float(h["tolerance_change"])
+        c.max_iter = int(h["max_iter"]) if h["max_iter"] is not None else 0
+        c.max_eval = int(h["max_eval"]) if h["max_eval"] is not None else 0
+        if c.max_iter < 0 or c.max_eval < 0 or (h["max_iter"] is not None and c.max_iter == 0) or (h["max_eval"] is not None and c.max_eval == 0):
+            raise ValueError("BatchOptimizer: max_iter / max_eval must be positive (None = the reference's defaults)")
+        c.history_size = int(h["history_size"]) if int(h["history_size"]) >= 1 else -1      # (0 is the C structure's "default": not offered here)
+        c.reuse_entry_eval = int(bool(h["reuse_entry_eval"]))
+        hnd = C.c_void_p()
+        capi.check(lib.sfx_opt_create(C.byref(c), C.byref(hnd)))
+        import torch
+        self._h, self._lib = hnd, lib
+        self.B, self.N, self.hyper = int(B), int(N), h
+        self.device = torch.device("cuda", torch.cuda.current_device())      # where the state lives: every tensor of a call must be there
+        self.x_trial = None
+        self._trace_cap = 0
+
+    def _tensor(self, name, t, shape):
+        import torch
+        if not torch.is_tensor(t):
+            raise TypeError("%s: a torch tensor is needed, got %s" % (name, type(t).__name__))
+        if t.device.type != "cuda":
+            raise ValueError("%s: a CUDA tensor is needed (no CPU fallback), got device %s" % (name, t.device))
+        if t.device != self.device:
+            raise ValueError("%s: on %s, the optimiser's state on %s" % (name, t.device, self.device))
+        if t.dtype != torch.float32:
+            raise ValueError("%s: float32 is needed, got %s" % (name, t.dtype))
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError("%s: shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
+        if not t.is_contiguous():
+            raise ValueError("%s: a contiguous tensor is needed (strides %s)" % (name, tuple(t.stride())))
+        return t.detach()
+
+    def _stream(self, stream):
+        import torch
+        return C.c_void_p(stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream)
+
+    def begin(self, x0, mode="fit", resume=False, stream=None):
+        """Start at x0 [B][N].  mode "fit": the whole run_fitting loop; "step": ONE LBFGS.step (resume=True continues the
+        optimiser of the previous "step" run: history and counters kept).  Returns x_trial, the [B][N] tensor every later
+        `tell` rewrites in place: the points to evaluate."""
+        import torch
+        if mode not in ("fit", "step"):
+            raise ValueError("mode: 'fit' or 'step', got %r" % (mode,))
+        x0 = self._tensor("x0", x0, (self.B, self.N))
+        if self.x_trial is None:
+            self.x_trial = torch.empty((self.B, self.N), dtype=torch.float32, device=self.device)
+        capi.check(self._lib.sfx_opt_begin(self._h, 0 if mode == "fit" else 1, int(bool(resume)), C.c_void_p(x0.data_ptr()),
+                                           C.c_void_p(self.x_trial.data_ptr()), self._stream(stream)))
+        return self.x_trial
+
+    def tell(self, loss, grad, stream=None):
+        """loss [B] and grad [B][N] at x_trial -> x_trial holds the next points.  Enqueues only.  Problems that have finished
+        ignore their entries, so calling this more often than needed is harmless."""
+        if self.x_trial is None:
+            raise RuntimeError("BatchOptimizer.tell before begin")
+        loss = self._tensor("loss", loss, (self.B,))
+        grad = self._tensor("grad", grad, (self.B, self.N))
+        capi.check(self._lib.sfx_opt_tell(self._h, C.c_void_p(loss.data_ptr()), C.c_void_p(grad.data_ptr()),
+                                          C.c_void_p(self.x_trial.data_ptr()), self._stream(stream)))
+
+    def active(self, stream=None):
+        """Problems still running.  Waits for the stream: the one host synchronisation of a loop."""
+        n = C.c_int32(0)
+        capi.check(self._lib.sfx_opt_active(self._h, C.byref(n), self._stream(stream)))
+        return int(n.value)
+
+    def result(self):
+        """dict: x [B][N] accepted points and grad [B][N] gradients of the last consumed evaluations (CUDA tensors); result [B]
+        (mode "fit": what run_fitting returns, NaN for None; "step": the loss at entry), evals [B], status [B] (1 = finished)."""
+        import torch
+        x = torch.empty((self.B, self.N), dtype=torch.float32, device=self.device)
+        g = torch.empty((self.B, self.N), dtype=torch.float32, device=self.device)
+        res = np.zeros(self.B, np.float32)
+        ev = np.zeros(self.B, np.int32)
+        st = np.zeros(self.B, np.int32)
+        capi.check(self._lib.sfx_opt_get(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(g.data_ptr()), capi.fptr(res), capi.iptr(ev),
+                                         capi.iptr(st)))
+        return dict(x=x, grad=g, result=res, evals=ev, status=st)
+
+    def trace(self, capacity):
+        """Attach (capacity > 0 records per problem) or detach (0) the optimiser trace (sfx_opt_trace); a fresh begin empties it."""
+        capi.check(self._lib.sfx_opt_trace(self._h, int(capacity)))
+        self._trace_cap = int(capacity)
+
+    def get_trace(self):
+        """Per problem: array [n, 4] of the records of the current run
+        ((0, t, loss, ls_evals) | (1, entry loss, func_evals, n_iter) | (2, result, evals, 0))."""
+        cap = self._trace_cap
+        rec = np.zeros((self.B, cap, 4), np.float32)
+        cnt = np.zeros(self.B, np.int32)
+        capi.check(self._lib.sfx_opt_get_trace(self._h, capi.fptr(rec), capi.iptr(cnt)))
+        if (cnt > cap).any():
+            raise RuntimeError("optimiser trace overflowed: %d records, capacity %d" % (cnt.max(), cap))
+        return [rec[i, :cnt[i]].copy() for i in range(self.B)]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.sfx_opt_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def prof_enable(on=True, every=1):
     """HIP-event timing of the named kernel launches; `every` = N times only every N-th launch of
     each name (an event pair costs two queue packets per launch)."""

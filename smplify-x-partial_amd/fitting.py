@@ -372,15 +372,27 @@ class FittingMonitor(object):
         """The whole step loop (fitting.py:174-217) on device for the 'lbfgsls' optimiser; returns the
         step-entry loss of the last step, like the reference.  Any other optimiser (torch.optim objects of
         optim_factory) is driven from the host with the same stopping rules, each closure evaluation on
-        the device."""
+        the device.  A closure the caller wrote (any callable) with this package's LBFGS runs the same host loop
+        over optimizer.step, whose line searches run on the device."""
         if not isinstance(closure, EngineClosure):
-            raise TypeError("run_fitting needs the closure returned by create_fitting_closure")
-        if hasattr(optimizer, "_bind"):
+            # a closure the caller wrote, with this package's LBFGS: the reference's host loop over optimizer.step, each step's
+            # line searches on the device (optimizers/lbfgs_ls.py)
+            if not (hasattr(optimizer, "_bind") and getattr(optimizer, "_closure", None) is None and callable(closure)):
+                raise TypeError("run_fitting needs the closure returned by create_fitting_closure, or -- with optimizers.lbfgs_ls."
+                                "LBFGS -- any callable that zeroes the gradients, calls backward and returns the loss")
+            if optimizer.per_sample:
+                raise NotImplementedError("run_fitting drives ONE problem, like the reference; for a batch of independent problems "
+                                          "run the whole loop on the device: engine.BatchOptimizer(...).begin(x0, mode='fit')")
+            step_closure = closure
+        elif hasattr(optimizer, "_bind"):
             closure._check_params(list(params))
             return closure.run_stage(stage)
+        else:
+            step_closure = lambda: closure(stage=stage)
+        params = list(params)
         prev_loss = None
         for n in range(self.maxiters):
-            loss = optimizer.step(lambda: closure(stage=stage))
+            loss = optimizer.step(step_closure)
             if torch.isnan(loss).sum() > 0 or torch.isinf(loss).sum() > 0:
                 break
             if n > 0 and prev_loss is not None and self.ftol > 0:
