@@ -16,7 +16,11 @@
  *   SFX_PEN_FAST_PAIRS=n     forms 1 / 2: columns with more than n pairs go to the general kernels
  *   SFX_POLL_ROUNDS=n, SFX_POLL_AHEAD=n   rounds per polled batch / batches queued ahead in the dense fitting loop
  *   SFX_DENSE_OVERLAP=0      the serial dense loop: one whole-grid GEMM in front of every tick launch, one stream
- *   SFX_OVERLAP_SERIAL=n     the overlapped dense loop's rule: rounds at <= n active columns stay serial (default 160)
+ *   SFX_OVERLAP_SERIAL=n     the overlapped dense loop's rule: rounds at <= n active columns stay serial, whichever overlapped form
+ *                            is selected (default: 160 for the key / rest form; SFX_OV_SELF_SERIAL for the self-served one)
+ *   SFX_DENSE_SELF=0         no self-served rounds: the key / rest form wherever the loop overlaps
+ *   SFX_DENSE_SELF_MAX=n     self-served rounds at <= n active columns only (default SFX_OV_SELF_MAX); above, the key / rest rule
+ *   SFX_DENSE_SELF_SERIAL=1  serial rounds launch the tick kernel with self-served blend offsets too (its cost per launch, alone)
  *   SFX_DEBUG_NACT, SFX_DEBUG_HOST        loop diagnostics on stderr
  * Deleted in round 6 (result-changing, or measured and closed; the last tree that holds them is commit e8a08e9):
  *   SFX_PEN_REWALK_OFF, SFX_HIST_ZEROPAGE, SFX_PEN_BRANCHES, SFX_PEN_FORM=3 (k_pen_frame), sfx_fit_multi / sfx_debug_overlap_test.

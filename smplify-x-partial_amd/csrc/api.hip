@@ -161,6 +161,18 @@ struct sfx_model {
 #ifndef SFX_OV_SERIAL
 #define SFX_OV_SERIAL 160    // rounds at this many active GEMM columns or fewer stay serial on one stream
 #endif
+// the self-served form of a round (run_ticks; models that export at most SFX_OV_SELF_UNIQ vertices, no interpenetration term):
+// rounds at more than SFX_OV_SELF_SERIAL and at most SFX_OV_SELF_MAX active columns; outside that band the rules above hold.
+// The band is where the form won the sweep of LAB_NOTES 4.9 (frames/s with the form from n + 1 columns up to 160: n = 0: 620.1,
+// 16: 631.6, 32: 635.7, 64: 637.3, 96: 628.5, 128: 616.2, 160 = the key / rest rule alone: 611.8; up to 192 instead of 160:
+// +3.7): below 65 columns the GEMM's small workgroups take the CUs the tick chain needs next and the round turns serial again
+#ifndef SFX_OV_SELF_SERIAL
+#define SFX_OV_SELF_SERIAL 64
+#endif
+#ifndef SFX_OV_SELF_MAX
+#define SFX_OV_SELF_MAX 192
+#endif
+#define SFX_OV_SELF_UNIQ 16  // one tile of exported vertices: three of the tick workgroup's wavefronts carry one MFMA chain each
 struct sfx_batch {
     sfx_model* m = nullptr;
     BatchDev D{};
@@ -278,7 +290,7 @@ extern "C" int sfx_model_create(const sfx_model_desc* d, sfx_model** out) {
     M.item_vid = mem.up(T.item_vid); M.item_w = mem.up(T.item_w);
     M.item_vt = mem.up(T.item_vt); M.item_wj = mem.up(T.item_wj); M.item_ww = mem.up(T.item_ww);
     M.dynp_us = T.dynp_us.empty() ? nullptr : mem.up(T.dynp_us);
-    M.vslot = mem.up(T.vslot); M.item_uslot = mem.up(T.item_uslot);
+    M.vslot = mem.up(T.vslot); M.item_uslot = mem.up(T.item_uslot); M.uniq_dirs = mem.up(T.uniq_dirs);
     M.meta = mem.up(T.meta);
     m->tile_key = mem.up(T.tile_key); m->tile_rest = mem.up(T.tile_rest);
     m->n_key = (int)T.tile_key.size(); m->n_rest = (int)T.tile_rest.size();
@@ -738,7 +750,9 @@ extern "C" int sfx_debug_phase_clocks(sfx_batch* b, int32_t stage, int64_t* out 
 // debug / tests: copy one of the dense path's device buffers of the most recent evaluation to the host.
 // name -> floats per frame (rows are GEMM columns = frames while no compaction is in force):
 //   "verts" V*3, "vposed" V*3, "pen_dverts" V*3, "pen_dfeat" 512, "pen_dA" 55*12, "pen_loss" 1,
-//   "A" 12*55 (skinning transforms, [row*4+col][joint] gathered from the GEMM operand), "feat" 512
+//   "A" 12*55 (skinning transforms, [row*4+col][joint] gathered from the GEMM operand), "feat" 512,
+//   "uvp" n_uniq*3 (blend offsets of the exported vertices as the dense GEMM wrote them), "uvp_self" n_uniq*3 (the same from
+//   closure_body.h self_blend_offsets on the current "feat": one launch of k_uvp_self into a scratch buffer)
 extern "C" int sfx_batch_debug_read(sfx_batch* b, const char* name, float* out, int64_t n_out) {
     if (!b || !name || !out) { sfx_set_error("null argument"); return -1; }
     const BatchDev& D = b->D; const int B = D.cfg.B, V = b->m->M.V;
@@ -756,6 +770,20 @@ extern "C" int sfx_batch_debug_read(sfx_batch* b, const char* name, float* out, 
     if (k == "pen_dfeat") return plain(D.pen_dfeat, SFX_KD_PAD);
     if (k == "pen_dA") return plain(D.pen_dA, (size_t)SFX_J * 12);
     if (k == "pen_loss") return plain(D.pen_loss, 1);
+    if (k == "uvp") return plain(D.uvp, (size_t)b->m->M.n_uniq * 3);
+    if (k == "uvp_self") {
+        const size_t n = (size_t)B * b->m->M.n_uniq * 3;
+        if ((int64_t)n != n_out) { sfx_set_error("'%s' holds %zu floats, caller asked for %lld", name, n, (long long)n_out); return -1; }
+        if (!n) return 0;
+        if (!D.featR) { sfx_set_error("buffer '%s' is not allocated in this batch", name); return -1; }
+        DevAlloc scratch;
+        float* d = scratch.zeros<float>(n);
+        if (!d) { (void)hipGetLastError(); sfx_set_error("out of device memory"); return -2; }
+        launch_uvp_self(b->m->M, D, d, nullptr);
+        SFX_CHECK(hipDeviceSynchronize());
+        SFX_CHECK(hipMemcpy(out, d, n * sizeof(float), hipMemcpyDeviceToHost));
+        return 0;
+    }
     if (k == "A" || k == "feat") {
         const size_t rows = k == "A" ? (size_t)12 * SFX_JPAD : SFX_KD_PAD, per = k == "A" ? (size_t)12 * SFX_J : SFX_KD_PAD;
         if ((int64_t)(per * B) != n_out) { sfx_set_error("'%s' holds %zu floats, caller asked for %lld", name, per * B, (long long)n_out); return -1; }
@@ -1064,12 +1092,27 @@ static int run_ticks(sfx_batch* b, int first_stage, int last_stage, int init, in
         // 512-column pool lost 6 % overlapped: two tick workgroups per CU and a GEMM that fills the chip leave nothing to
         // share); the eight-wavefront tick kernel at every size (the four-wavefront one shares
         // its CU with GEMM workgroups and then takes 101 instead of 58 us per launch).
+        // Self-served form (models that export at most SFX_OV_SELF_UNIQ vertices: body-only keypoints).  There the tick workgroup
+        // forms the blend offsets of its keypoint vertices itself, from its column of cur with the GEMM's own chain of operations
+        // (closure_body.h self_blend_offsets: has_eval = 2), so the tick of evaluation i waits for no GEMM launch at all and the WHOLE
+        // GEMM of every evaluation runs beside the tick chain:
+        //     stream s :  wait E_G(i-2) | T(i) reads cur, exports evaluation i + 1 to nxt | record E_T(i)
+        //     stream s2:  wait E_T(i-1) | G(i) all tiles, reads cur | record E_G(i)
+        // Same three operand sets, same rotation, same joins; every evaluation still gets exactly one whole-mesh GEMM (it goes on
+        // writing D.uvp, which nobody reads in these rounds).  The first such round after anything else on s records its own E_T at
+        // its start; between the two overlapped forms the loop joins, because Gk(i) on s and G(i-1) on s2 both write the key tiles
+        // of D.verts.  The band of column counts it is used in: SFX_OV_SELF_SERIAL / SFX_OV_SELF_MAX (LAB_NOTES 4.9).
 #ifdef SFX_LAB
         static const bool ov_on = [] { const char* e = getenv("SFX_DENSE_OVERLAP"); return !(e && *e && atoi(e) == 0); }();
+        static const bool ov_serial_set = [] { const char* e = getenv("SFX_OVERLAP_SERIAL"); return e && *e; }();
         static const int ov_serial = [] { const char* e = getenv("SFX_OVERLAP_SERIAL"); return e && *e ? atoi(e) : SFX_OV_SERIAL; }();
+        static const bool self_on = [] { const char* e = getenv("SFX_DENSE_SELF"); return !(e && *e && atoi(e) == 0); }();
+        static const int self_serial = ov_serial_set ? ov_serial : SFX_OV_SELF_SERIAL;       // (SFX_OVERLAP_SERIAL: whichever form is selected)
+        static const int self_max = [] { const char* e = getenv("SFX_DENSE_SELF_MAX"); return e && *e ? atoi(e) : SFX_OV_SELF_MAX; }();
+        static const bool self_in_serial = [] { const char* e = getenv("SFX_DENSE_SELF_SERIAL"); return e && *e && atoi(e) != 0; }();
 #else
-        constexpr bool ov_on = true;
-        constexpr int ov_serial = SFX_OV_SERIAL;
+        constexpr bool ov_on = true, self_on = true, self_in_serial = false;
+        constexpr int ov_serial = SFX_OV_SERIAL, self_serial = SFX_OV_SELF_SERIAL, self_max = SFX_OV_SELF_MAX;
 #endif
         const bool overlap = ov_on && !b->pen && b->featR_o[0] && b->featR_o[1] && b->AT_o[0] && b->AT_o[1];
         if (overlap && !b->s2) {
@@ -1082,6 +1125,8 @@ static int run_ticks(sfx_batch* b, int first_stage, int last_stage, int init, in
         struct OvDrain { sfx_batch* b; hipStream_t s;
                          ~OvDrain() { if (b->s2) (void)hipStreamSynchronize(b->s2); (void)hipStreamSynchronize(s); b->D.featR_w = b->D.featR; b->D.AT_w = b->D.AT; } } ov_drain{b, s};
         hipEvent_t last_G = nullptr, prev_G = nullptr;     // E_G of the latest overlapped round and of the one before (NULL: s has waited for it)
+        hipEvent_t last_T = nullptr;                       // E_T of the latest self-served round (NULL: the latest round was of another form)
+        const bool self_form = overlap && self_on && M.n_uniq <= SFX_OV_SELF_UNIQ;
         long ov_i = 0;
         auto join_s2 = [&]() -> int {                       // before s writes operands in place: every Gr has read them
             if (last_G) SFX_CHECK(hipStreamWaitEvent(s, last_G, 0));
@@ -1122,7 +1167,28 @@ static int run_ticks(sfx_batch* b, int first_stage, int last_stage, int init, in
             struct HostClock { const std::chrono::steady_clock::time_point t0; double& acc; long& n; bool on;
                                ~HostClock() { if (on) { acc += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); ++n; } } } hc{h0, host_enq_s, host_batches, true};
             for (int q = 0; q < rpb; ++q, ++tick) {
+                if (self_form && D.nact > self_serial && D.nact <= self_max) {
+                    const int k = (int)(ov_i++ % SFX_OV_EVENTS);
+                    // (E_T lives in ring 0, whose events the key / rest form records and waits for at once: a wait holds the record
+                    //  it was enqueued behind, so slot k + 1 of this round is free again when round i + 4 records it)
+                    if (!last_G || !last_T) { SFX_CHECK(hipEventRecord(b->ov_ev[0][k], s)); last_T = b->ov_ev[0][k]; }
+                    SFX_CHECK(hipStreamWaitEvent(b->s2, last_T, 0));
+                    { ProfScope p("lbs_dense", b->s2, D.nact); launch_lbs_dense(M, D, b->s2); }
+                    SFX_CHECK(hipEventRecord(b->ov_ev[1][k], b->s2));
+                    if (prev_G) SFX_CHECK(hipStreamWaitEvent(s, prev_G, 0));
+                    prev_G = last_G; last_G = b->ov_ev[1][k];
+                    BatchDev Dt = D; Dt.featR_w = b->featR_o[0]; Dt.AT_w = b->AT_o[0];
+                    { ProfScope p("tick", s, D.nrun);
+                      launch_tick_dense(M, Dt, b->vl_dev, b->sw_dev, first_stage, last_stage, 2, s); }
+                    last_T = b->ov_ev[0][(k + 1) % SFX_OV_EVENTS];
+                    SFX_CHECK(hipEventRecord(last_T, s));
+                    float* const f = D.featR; D.featR = b->featR_o[0]; b->featR_o[0] = b->featR_o[1]; b->featR_o[1] = f;
+                    float* const a = D.AT; D.AT = b->AT_o[0]; b->AT_o[0] = b->AT_o[1]; b->AT_o[1] = a;
+                    D.featR_w = D.featR; D.AT_w = D.AT;
+                    continue;
+                }
                 if (overlap && D.nact > ov_serial && D.nact <= SFX_OV_MAX) {
+                    if (last_T) { if (int rc = join_s2()) return rc; last_T = nullptr; }      // (the latest round was self-served: its G writes the key tiles too)
                     const int k = (int)(ov_i++ % SFX_OV_EVENTS);
                     if (b->m->n_key) { ProfScope p("lbs_dense_key", s, D.nact); launch_lbs_dense_list(M, D, b->m->tile_key, b->m->n_key, s); }
                     SFX_CHECK(hipEventRecord(b->ov_ev[0][k], s));
@@ -1140,10 +1206,11 @@ static int run_ticks(sfx_batch* b, int first_stage, int last_stage, int init, in
                     continue;
                 }
                 if (int rc = join_s2()) return rc;
+                last_T = nullptr;
                 { ProfScope p("lbs_dense", s, D.nact); launch_lbs_dense(M, D, s); }
                 if (int rc = eval_penetration(b, -2, s, true)) return rc;
                 ProfScope p("tick", s, D.nrun);
-                launch_tick_dense(M, D, b->vl_dev, b->sw_dev, first_stage, last_stage, 1, s);
+                launch_tick_dense(M, D, b->vl_dev, b->sw_dev, first_stage, last_stage, (self_in_serial && !b->pen && M.n_uniq <= SFX_OV_SELF_UNIQ) ? 2 : 1, s);
             }
             SFX_CHECK(hipMemcpyAsync(b->stage_host + (size_t)buf * B, D.stage, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
             SFX_CHECK(hipEventRecord(b->poll_ev[buf], s));

@@ -130,6 +130,55 @@ __device__ __forceinline__ void lds_fill_async16(void* lds_dst, const void* gsrc
     }
 }
 
+// Self-served blend offsets: what the dense GEMM (lbs_dense.hip) exports as BatchDev.uvp -- sum_k featR[column][k] dirs[k][vertex,
+// coordinate] for the n_uniq exported vertices -- formed by the frame's own workgroup from its operand row `arow`, bit for bit:
+// the GEMM's instruction (v_mfma_f32_16x16x4_f32), accumulator from zero, its K order (SFX_DENSE_KCHUNK, rows ascending inside
+// a chunk, k = 4 ks + kq in lane group kq), no template added.  The rows of an MFMA tile are independent, so all 16 A rows carry
+// this frame's operand and row 0 (lanes 0-15, register 0) is read; the B columns are the exported vertices, whose rows of dirsT
+// the model keeps a second time in the order this chain consumes them (DevModel.uniq_dirs: one 16-byte load per lane and four
+// steps; gathered from dirsT itself -- 4-byte loads at stride 16 over 16 rows -- the phase cost 9.4 us per launch, LAB_NOTES 4.9).
+// One accumulator chain per (tile of 16 vertices, coordinate), dealt to the `nw` wavefronts that call (wavefront wv of them): 128
+// dependent MFMAs, B operands fetched four chunks (32 steps) ahead.  out[u * 3 + c], LDS or global; any n_uniq (0: nothing).
+typedef float sfx_f32x4 __attribute__((ext_vector_type(4)));
+[[maybe_unused]] static __device__ __forceinline__ void self_blend_offsets(const float* __restrict__ uniq_dirs, const int n_uniq, const float* __restrict__ arow,
+                                                                           float* out, const int wv, const int nw, const int lane) {
+    constexpr int NCH = SFX_KD_PAD / SFX_DENSE_KC, KS = SFX_DENSE_KC / 4;      // 16 chunks of 8 MFMA steps
+    constexpr int NG = 4, GS = NG * KS;                                         // chunks / steps per operand group
+    static_assert(NCH % NG == 0 && KS % 4 == 0 && NCH * KS == 128, "operand groups; DevModel.uniq_dirs holds 128 steps per unit");
+    const int jl = lane & 15, kq = lane >> 4;
+    const int nunit = ((n_uniq + 15) / 16) * 3;
+    for (int unit = wv; unit < nunit; unit += nw) {
+        const int tile = unit / 3, co = unit - tile * 3;
+        const int u = tile * 16 + jl;
+        const float4* pb = reinterpret_cast<const float4*>(uniq_dirs) + (size_t)unit * (NCH * KS / 4) * 64 + lane;
+        const float* pa = arow + kq;
+        float a[NCH * KS];
+        float4 bv[2][GS / 4];
+#pragma unroll
+        for (int c = 0; c < NCH; ++c)
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) a[c * KS + ks] = pa[SFX_DENSE_KCHUNK(c) * SFX_DENSE_KC + ks * 4];
+#define SELF_LOAD(g, buf) _Pragma("unroll") for (int q = 0; q < GS / 4; ++q) bv[buf][q] = pb[((g) * (GS / 4) + q) * 64];
+        sfx_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        SELF_LOAD(0, 0)
+#pragma unroll
+        for (int g = 0; g < NCH / NG; ++g) {
+            if (g + 1 < NCH / NG) { SELF_LOAD(g + 1, (g + 1) & 1) }
+            __builtin_amdgcn_sched_barrier(0);      // (keep the next group's loads in front of this group's chain: left alone, the scheduler sinks them to 8 steps ahead)
+#pragma unroll
+            for (int q = 0; q < GS / 4; ++q) {
+                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[g * GS + 4 * q + 0], bv[g & 1][q].x, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[g * GS + 4 * q + 1], bv[g & 1][q].y, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[g * GS + 4 * q + 2], bv[g & 1][q].z, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[g * GS + 4 * q + 3], bv[g & 1][q].w, acc, 0, 0, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#undef SELF_LOAD
+        if (kq == 0 && u < n_uniq) out[u * 3 + co] = acc[0];
+    }
+}
+
 // Per-frame working set of the closure workgroup.  MAXI = item capacity, VP = VPoser activations
 // present.  Two variants are instantiated: <240, true> (any model / configuration, 86 KB) and
 // <32, false> (body-only keypoints without VPoser, 47 KB -> three workgroups per CU, or one next
@@ -360,6 +409,7 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
     const ParLayout& L = D.L;
     const BatchCfgDev& C = D.cfg;
 
+    const bool self_uvp = !F64 && args.use_dense_verts == 2 && M.n_uniq > 0 && M.n_uniq <= LDS::kMaxItems;      // (the offsets wait in S.dvert)
     const int stage = __builtin_amdgcn_readfirstlane((args.stage_override != -2) ? args.stage_override : D.stage[b]);
     if constexpr (!kExt) { if (stage >= C.n_stages && !args.forward_only) return; }     // frame finished (a forward batch has no stages)
     const bool cam_stage = (stage < 0);
@@ -426,6 +476,12 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
     for (int i = t; i < SFX_KD_PAD; i += CT) { if (!reuse) S.feat[i] = 0.f; S.dfeat[i] = 0.f; }
     for (int i = t; i < SFX_NPAR_MAX; i += CT) S.gc[i] = 0.f;
     for (int i = t; i < 168; i += CT) S.dpose[i] = 0.f;
+    // dense mode without the GEMM's export (use_dense_verts = 2): the blend offsets of the exported vertices from this frame's
+    // operand row, behind the entry's requests and in front of their wait -- into S.dvert, which nobody touches before the
+    // reverse sweep ("needed vertices" below picks them up)
+    if constexpr (!F64) {
+        if (self_uvp) self_blend_offsets(M.uniq_dirs, M.n_uniq, D.featR + (size_t)args.self_col * SFX_KD_PAD, S.dvert, wv, CT / 64, lane);
+    }
     lds_dma_wait();
     __syncthreads();
     const Real* bodypose = S.x + L.emb;
@@ -740,7 +796,9 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
         const size_t ub = (size_t)D.slot[b] * M.n_uniq;
         const int nst = (M.dynp_us || NI < M.n_static_items) ? NI : M.n_static_items;
         for (int w = t; w < nst * 3; w += CT) {
-            const float o = D.uvp[(ub + S.uslot[w / 3]) * 3 + w % 3];
+            float o;
+            if constexpr (F64) o = D.uvp[(ub + S.uslot[w / 3]) * 3 + w % 3];
+            else o = self_uvp ? S.dvert[S.uslot[w / 3] * 3 + w % 3] : D.uvp[(ub + S.uslot[w / 3]) * 3 + w % 3];
             S.vpo[w] = o; S.vp[w] = S.vt[w] + o;
         }
         if (NI > nst) items_forward(nst, NI - nst);

@@ -81,6 +81,9 @@ void k_tick_dense(DevModel M, BatchDev D, const VarList* __restrict__ vls, const
     __shared__ int s_stage;
     static_assert(sizeof(VarList) % 4 == 0 && sizeof(OptScal) % 4 == 0 && (NVEC * SFX_NVAR_MAX) % 4 == 0, "dword / 16-byte LDS-DMA");
     const int b = D.act ? D.act[blockIdx.x] : blockIdx.x;      // (frames that finished or still wait in the queue are not launched)
+    // self-served blend offsets (has_eval = 2): the frame's column addresses the A operand of closure_body's self_blend_offsets --
+    // requested here, with the stage
+    const int self_col = (has_eval == 2 && M.n_uniq > 0) ? D.slot[b] : 0;
     if (D.stage[b] > last_stage) {      // finished, and the host has not retired it yet: see copy_operand_column
         if (has_eval) copy_operand_column(D, D.slot[b], CTK);
         return;
@@ -90,7 +93,8 @@ void k_tick_dense(DevModel M, BatchDev D, const VarList* __restrict__ vls, const
     if (D.dbg && blockIdx.x == 0 && threadIdx.x == 0) { D.dbg[62] += 1; if (D.dbg[62] <= D.dbg[61]) D.dbg[24] = clock64(); }
     if (has_eval) {
         ClosureArgs a{};
-        a.stage_override = -2; a.use_dense_verts = 1; a.reuse_fwd = 1;
+        a.stage_override = -2; a.use_dense_verts = has_eval == 2 ? 2 : 1; a.reuse_fwd = 1;      // (2: self-served blend offsets, sfx_internal.h)
+        a.self_col = __builtin_amdgcn_readfirstlane(self_col);
         if constexpr (PF) {
             lds_fill_async16<CTK>(s_pf, D.vec + (size_t)b * NVEC * SFX_NVAR_MAX, NVEC * SFX_NVAR_MAX / 4);
             lds_fill_async16<CTK>(s_pf + NVEC * SFX_NVAR_MAX, D.X + (size_t)b * SFX_NPAR_MAX, SFX_NPAR_MAX / 4);
@@ -140,6 +144,19 @@ void k_tick_dense(DevModel M, BatchDev D, const VarList* __restrict__ vls, const
         atomicAdd((unsigned long long*)&D.dbg[59], (unsigned long long)dt);
         atomicAdd((unsigned long long*)&D.dbg[60], 1ull);
     }
+}
+
+// debug / tests (sfx_batch_debug_read "uvp_self"): self_blend_offsets for every column of the current D.featR, one workgroup of four
+// wavefronts per column -- what a tick workgroup launched with has_eval = 2 would use in place of that column's row of D.uvp
+__global__ __launch_bounds__(256)
+void k_uvp_self(DevModel M, BatchDev D, float* __restrict__ out) {
+    const int col = blockIdx.x;
+    self_blend_offsets(M.uniq_dirs, M.n_uniq, D.featR + (size_t)col * SFX_KD_PAD, out + (size_t)col * M.n_uniq * 3,
+                       threadIdx.x >> 6, 4, threadIdx.x & 63);
+}
+void launch_uvp_self(const DevModel& M, const BatchDev& D, float* out, hipStream_t s) {
+    if (D.cfg.B <= 0 || M.n_uniq <= 0) return;
+    hipLaunchKernelGGL(k_uvp_self, dim3(D.cfg.B), dim3(256), 0, s, M, D, out);
 }
 
 void launch_fit_rows(const DevModel& M, const BatchDev& D, const VarList* vl_dev, const StageW* sw_dev,

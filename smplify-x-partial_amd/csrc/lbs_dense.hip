@@ -46,6 +46,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // shape / expression terms (centimetres, rows 0-19 of chunk 0) last: added to a centimetre-sized partial sum, every one of the
 // small terms would round at 2e-9 m (2.5e-8 m over the chain, measured on the keypoints)
 #define KCHUNK(c) (((c) + 1) % NCHUNK)
+static_assert(KC == SFX_DENSE_KC, "closure_body.h self_blend_offsets repeats this K order (SFX_DENSE_KCHUNK)");
 
 #ifdef SFX_LAB
 #include "lbs_dense_lab.h"

@@ -13,10 +13,10 @@ struct ModelTables {      // members named after the DevModel pointers they beco
 #ifdef SFX_LAB
     std::vector<float> dirs;
 #endif
-    std::vector<float> dirs_tiled, dirsT, tj_w, jv_w, Wsp_w, J_template, J_dirs, item_w, item_vt, item_ww, sj_w, dj_w;
+    std::vector<float> dirs_tiled, dirsT, uniq_dirs, tj_w, jv_w, Wsp_w, J_template, J_dirs, item_w, item_vt, item_ww, sj_w, dj_w;
     std::vector<float> dynp_w, dynp_vt, dynp_ww, dynp_jw;
     std::vector<double> J_template64, J_dirs64;
-    std::vector<int> tj_n, tj_list, jv_start, jv_vid, Wsp_j, vslot, item_uslot, item_vid, item_wj, sj_start, sj_item;
+    std::vector<int> tj_n, tj_list, jv_start, jv_vid, Wsp_j, vslot, uniq_vid, item_uslot, item_vid, item_wj, sj_start, sj_item;
     std::vector<int> dj_start, dj_item, dynp_vid, dynp_wj, dynp_js, dynp_ji, dynp_us;     // dynp_js empty: the rows do not fit
     std::vector<int> meta;        // [SFX_META_N] the MO_* blocks: tree, mapped joints, item owners
     std::vector<int> faces;       // host copy for the collision handle
@@ -157,7 +157,7 @@ static inline int sfx_build_model_tables(const sfx_model_desc* d, ModelTables* o
     // export slots: distinct vertices of the static items and of every vertex a dynamic item can land on (all LUT rows) -- the
     // dense GEMM hands their blend offsets to the per-frame kernel, which then streams no blend-shape row forward
     T.vslot.assign(T.Vpad, -1); T.item_uslot.assign(ni, -1); T.dynp_us.resize(T.dynp_vid.size());
-    auto slot_of = [&](int v) { if (T.vslot[v] < 0) T.vslot[v] = T.n_uniq++; return T.vslot[v]; };
+    auto slot_of = [&](int v) { if (T.vslot[v] < 0) { T.vslot[v] = T.n_uniq++; T.uniq_vid.push_back(v); } return T.vslot[v]; };
     for (int i = 0; i < ns; ++i) T.item_uslot[i] = slot_of(T.item_vid[i]);
     for (size_t o = 0; o < T.dynp_vid.size(); ++o) T.dynp_us[o] = slot_of(T.dynp_vid[o]);
     for (int t = 0; t < (V + 15) / 16; ++t) {           // (vslot has Vpad >= 16 ceil(V / 16) entries, -1 beyond V)
@@ -182,6 +182,19 @@ static inline int sfx_build_model_tables(const sfx_model_desc* d, ModelTables* o
 #endif
         }
     }
+    // the rows of the exported vertices once more, as the B operands of the per-frame kernel's own copy of the GEMM's chain
+    // (closure_body.h self_blend_offsets): per unit = (tile of 16 export indices, coordinate) the 128 MFMA steps in the GEMM's K
+    // order -- step s = 8 c + ks reads k = 32 SFX_DENSE_KCHUNK(c) + 4 ks + kq in lane kq * 16 + jl, column jl = export index
+    // 16 tile + jl (the spare columns of a partial tile repeat the last vertex) -- laid out [unit][s / 4][lane][s % 4]
+    T.uniq_dirs.assign((size_t)((T.n_uniq + 15) / 16) * 3 * 128 * 64, 0.f);
+    for (int unit = 0; unit < ((T.n_uniq + 15) / 16) * 3; ++unit)
+        for (int s = 0; s < 128; ++s)
+            for (int lane = 0; lane < 64; ++lane) {
+                const int tile = unit / 3, co = unit % 3, jl = lane & 15, kq = lane >> 4;
+                const int v = T.uniq_vid[std::min(tile * 16 + jl, T.n_uniq - 1)];
+                const int k = SFX_DENSE_KC * SFX_DENSE_KCHUNK(s / 8) + 4 * (s % 8) + kq;
+                T.uniq_dirs[(((size_t)unit * 32 + s / 4) * 64 + lane) * 4 + s % 4] = T.dirsT[((size_t)v * 3 + co) * SFX_KD_PAD + k];
+            }
     // skinning weights: packed per vertex, transposed CSR, and per 16-vertex tile
     T.Wsp_j.assign((size_t)V * SFX_NW, 0); T.Wsp_w.assign((size_t)V * SFX_NW, 0.f);
     for (int v = 0; v < V; ++v) sfx_pack_weights(W, v, &T.Wsp_j[(size_t)v * SFX_NW], &T.Wsp_w[(size_t)v * SFX_NW]);

@@ -23,6 +23,10 @@
 #endif
 #define SFX_KD_PAD 512      // padded blend-shape depth (20 + 486 = 506)
 #define SFX_JPAD 56         // joints padded to an even MFMA depth
+// K order of the dense blend-shape GEMM (lbs_dense.hip), shared with whoever must reproduce its sums bit for bit: chunks of
+// SFX_DENSE_KC rows taken as 1, 2, ..., 15, 0, rows ascending inside a chunk
+#define SFX_DENSE_KC 32
+#define SFX_DENSE_KCHUNK(c) (((c) + 1) % (SFX_KD_PAD / SFX_DENSE_KC))
 #define SFX_MAX_LEVELS 16
 #define SFX_HIST 100        // L-BFGS history (optim_factory 'lbfgsls' default): slots of the ring unless history_size asks for more
 #ifndef SFX_HIST_MAX
@@ -134,7 +138,10 @@ struct DevModel {
     const float* item_vt;      // [n_items][3] v_template row of the item's vertex     } gathered copies for the static items:
     const int*   item_wj;      // [n_items][SFX_NW] = Wsp_j[item_vid]                  } one round trip at kernel entry
     const float* item_ww;      // [n_items][SFX_NW] = Wsp_w[item_vid]                  }
-    const void*  gap9_[4];
+    const float* uniq_dirs;    // [ceil(n_uniq / 16) * 3][32][64][4] the blend-shape rows of the exported vertices as the B operands of
+                               // closure_body.h self_blend_offsets: per (tile of 16 export indices, coordinate) the 128 MFMA steps of
+                               // the dense GEMM's K order, four steps per lane and 16-byte load (model_tables.h)
+    const void*  gap9_[3];
     int Vpad;
     // per-joint lists of (item, skinning weight): static items, and dynamic items per LUT row
     const int *sj_start, *sj_item; const float* sj_w;      // [J+1], [..]
@@ -300,13 +307,15 @@ struct DevAlloc {
 struct ClosureArgs {
     int stage_override;     // -2: use per-frame stage[]; otherwise stage for all frames
     int forward_only;       // 1: export joints / full_pose / featR / AT only
-    int use_dense_verts;    // 1: item vertices come from BatchDev.verts
+    int use_dense_verts;    // 1: the blend offsets of the item vertices come from the dense GEMM (BatchDev.uvp); 2: dense mode, but the
+                            //    workgroup forms them itself from its column of BatchDev.featR (closure_body.h self_blend_offsets: same bits)
     int export_dense;       // 1: write featR / AT for the dense kernel
     int from_X;             // 1: evaluate at X instead of Xt
     int from_scratch_items; // 1: dense mode, but evaluate the item rows here (the GEMM export belongs to another call)
     int keep_tables;        // 1: S.meta / S.fd are still valid from the previous evaluation of this workgroup
     int reuse_fwd;          // 1: forward state of this trial point was saved by the export pass
     const float* x_lds;     // the trial point in the workgroup's LDS (k_tick_dense: left there by the optimiser tick); NULL: read X / Xt
+    int self_col;           // use_dense_verts = 2: the frame's GEMM column (BatchDev.slot), read by the caller next to the stage
 };
 // the 47-KB closure variant serves models whose keypoints need at most SFX_SMALL_ITEMS vertex rows
 // when the VPoser decoder is not in the loop
@@ -350,5 +359,9 @@ size_t sfx_optstate_size();
 int debug_two_loop(const float* S, const float* Y, int cnt, int hist_cap, const float* g, float* d_out);   // lbfgs.hip (host pointers)
 void launch_fit_rows(const DevModel& M, const BatchDev& D, const VarList* vl_dev, const StageW* sw_dev,
                      int first_stage, int last_stage, int max_ticks, hipStream_t s);
+// has_eval: 0 export only | 1 loss + adjoint of the pending evaluation (blend offsets from D.uvp), tick, export | 2 the same with
+// self-served blend offsets (nothing of the GEMM of the pending evaluation is read)
 void launch_tick_dense(const DevModel& M, const BatchDev& D, const VarList* vl_dev, const StageW* sw_dev,
                        int first_stage, int last_stage, int has_eval, hipStream_t s);
+// debug / tests: the self-served blend offsets of every column from the current D.featR, out [B][n_uniq][3] (device)
+void launch_uvp_self(const DevModel& M, const BatchDev& D, float* out, hipStream_t s);

@@ -99,6 +99,18 @@ class DeviceModel(object):
             joint_map = np.arange(n_all)
         self.joint_map = np.asarray(joint_map).astype(np.int64)
         self.V, self.F, self.K = V, int(faces.shape[0]), int(len(self.joint_map))
+        # distinct vertices the keypoints read (extra vertices, landmark corners, every corner a dynamic landmark can land on):
+        # the columns of debug_read("uvp") -- csrc/model_tables.h n_uniq
+        fa, e0, l0 = np.asarray(model["f"]).astype(np.int64), 55, 55 + len(extra_vertex_ids)
+        uniq = set()
+        for s_ in self.joint_map:
+            if e0 <= s_ < l0:
+                uniq.add(int(np.asarray(extra_vertex_ids)[s_ - e0]))
+            elif l0 <= s_ < l0 + n_lmk:
+                uniq.update(int(v) for v in fa[int(np.asarray(model["lmk_faces_idx"])[s_ - l0])])
+            elif l0 + n_lmk <= s_ < n_all:      # (an entry out of range is refused by sfx_model_create below)
+                uniq.update(int(v) for v in fa[dyn_f[:, s_ - l0 - n_lmk].astype(np.int64)].ravel())
+        self.n_uniq = len(uniq)
         self.num_betas, self.num_expr, self.num_pca = num_betas, num_expression_coeffs, num_pca_comps
         self.faces = np.asarray(model["f"]).astype(np.int64)
         keep = dict(
@@ -644,14 +656,16 @@ class FrameBatch(object):
                                                     capi.fptr(cc) if cc is not None else None))
 
     _DEBUG_PER_FRAME = dict(verts="V3", vposed="V3", pen_dverts="V3", pen_dfeat=512, feat=512, pen_dA=55 * 12, A=12 * 55,
-                            pen_loss=1)
+                            pen_loss=1, uvp="U3", uvp_self="U3")
 
     def debug_read(self, name):
         """Tests: one of the dense path's device buffers of the most recent evaluation as [B, per-frame]
         (sfx_batch_debug_read)."""
         per = self._DEBUG_PER_FRAME[name]
-        per = self.model.V * 3 if per == "V3" else per
+        per = self.model.V * 3 if per == "V3" else (self.model.n_uniq * 3 if per == "U3" else per)
         out = np.zeros((self.B, per), np.float32)
+        if per == 0:            # (a model whose keypoints are all kinematic joints exports no vertex: nothing to copy or launch)
+            return out
         capi.check(self._lib.sfx_batch_debug_read(self._h, name.encode(), capi.fptr(out), out.size))
         return out
 
