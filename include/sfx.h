@@ -388,6 +388,84 @@ int  sfx_opt_get(sfx_opt* h, float* x_dev, float* grad_dev, float* result_host, 
 int  sfx_opt_trace(sfx_opt* h, int32_t capacity);
 int  sfx_opt_get_trace(sfx_opt* h, float* records, int32_t* counts);
 
+/* ---- the objective on tensors the CALLER supplies (csrc/objective_ext.hip) -----------------------------------
+ * Replaces `loss(body_model_output, camera=..., gt_joints=..., ...)` of the reference's closure (fitting.py:251-259) and what
+ * `total_loss.backward()` walks behind it down to the loss's inputs, for B frames at once and for joints that came from
+ * anywhere: SMPLifyLoss.forward (fitting.py:375-461 without the interpenetration lines :437-455, which the stand-alone
+ * sfx_pen_* operators cover), with camera.py:93-117, utils.py:84-95 (GMoF) and prior.py:53-97, :100-231 inside it.
+ * Stateless: no handle, no allocation, no synchronisation -- one launch that writes the loss of every frame AND the gradient of
+ * that frame's loss with respect to every differentiable input.  All pointers are DEVICE pointers to contiguous fp32;
+ * arithmetic is fp32.  One wavefront per frame, fixed-order reductions, no atomics: a frame's bits depend on its own inputs
+ * only (not on B or its position in the batch).  A keypoint whose weight (joint_weights x confidence) is 0 contributes
+ * exactly 0 to the loss and to every gradient, whatever its coordinates hold.
+ * Refused (-1) before anything is launched: B < 1, K outside 1..512, an unknown prior form, the mixture form with D != 63 (or
+ * an operand that is not 63 long) or M outside 1..32, a NULL required input.                                          */
+enum {                              /* sfx_objective_cfg.prior_form: the pose prior of fitting.py:390-401                   */
+    SFX_PRIOR_L2_EMBEDDING = 0,     /* |operand|^2: use_vposer, operand = pose_embedding (:395)                           */
+    SFX_PRIOR_L2_TARGET = 1,        /* |operand - target|^2: the regression prior (:393, :397)                            */
+    SFX_PRIOR_L2_BODY_POSE = 2,     /* |operand|^2: body_prior_type 'l2', operand = body_model_output.body_pose (:399-401); the
+                                       same arithmetic as form 0 -- kept apart because the caller's operand differs         */
+    SFX_PRIOR_MIXTURE = 3           /* MaxMixturePrior on operand = body_model_output.body_pose (:399-401, prior.py:100-231) */
+};
+typedef struct sfx_objective_cfg {
+    float   rho;                    /* GMoF rho (cfg: 100)                                                                 */
+    float   data_weight, body_pose_weight, shape_weight, bending_prior_weight, hand_prior_weight, expr_prior_weight;
+    float   jaw_prior_weight[3];    /* the stage's weights as SMPLifyLoss holds them (fitting.py:341-359)                  */
+    int32_t use_joints_conf;        /* weights = joint_weights * joints_conf (:380)                                        */
+    int32_t use_hands, use_face;    /* off: the hand / expression + jaw terms are 0 and their gradients are zeros          */
+    int32_t prior_form;             /* SFX_PRIOR_*                                                                          */
+    /* SFX_PRIOR_MIXTURE: the module's buffers as prior.mixture_tables makes them (DEVICE): means [M][D], precisions [M][D][D]
+     * (not symmetrised), nll_weights [M]; comp_const [M] or NULL with the semantics of sfx_batch_set_gmm_form (NULL = the
+     * merged form).  D must be 63.                                                                                        */
+    int32_t gmm_M, gmm_D;
+    const float* gmm_means_dev; const float* gmm_precisions_dev; const float* gmm_nll_weights_dev; const float* gmm_comp_const_dev;
+} sfx_objective_cfg;
+typedef struct sfx_objective_in {
+    int32_t B, K;                   /* frames, keypoints per frame                                                         */
+    int32_t n_prior;                /* length of the pose-prior operand (latent size, or 63)                               */
+    int32_t num_betas, num_expr;
+    const float* joints_dev;        /* [B][K][3]   body_model_output.joints                                                */
+    const float* cam_rot_dev;       /* [B][3][3]   camera.rotation                                                         */
+    const float* cam_t_dev;         /* [B][3]      camera.translation                                                      */
+    const float* focal_x_dev; const float* focal_y_dev;   /* [B]                                                           */
+    const float* center_dev;        /* [B][2]                                                                              */
+    const float* gt_joints_dev;     /* [B][K][2]                                                                           */
+    const float* joints_conf_dev;   /* [B][K]      (NULL allowed without use_joints_conf)                                  */
+    const float* joint_weights_dev; /* [B][K]                                                                              */
+    const float* body_pose_dev;     /* [B][63]     full_pose[:, 3:66]: the angle prior's operand (:407-408)                 */
+    const float* prior_dev;         /* [B][n_prior] the pose prior's operand, see SFX_PRIOR_*                              */
+    const float* prior_target_dev;  /* [B][n_prior] regression_pose (SFX_PRIOR_L2_TARGET only, else NULL)                  */
+    const float* betas_dev;         /* [B][num_betas]                                                                      */
+    const float* expression_dev;    /* [B][num_expr]                      (use_face)                                       */
+    const float* jaw_dev;           /* [B][3]                             (use_face)                                       */
+    const float* lhand_dev; const float* rhand_dev;       /* [B][45] as ModelOutput carries them (use_hands)               */
+} sfx_objective_in;
+typedef struct sfx_objective_grads {  /* d loss[b] / d input, shaped like the input; any may be NULL (not wanted)            */
+    float* d_joints_dev; float* d_cam_rot_dev; float* d_cam_t_dev; float* d_body_pose_dev; float* d_prior_dev;
+    float* d_betas_dev; float* d_expression_dev; float* d_jaw_dev; float* d_lhand_dev; float* d_rhand_dev;
+} sfx_objective_grads;
+/* cfg, in and grads are HOST structures (read during the call) holding DEVICE pointers; grads may be NULL (loss only).
+ * loss_dev [B].  The total is summed in the term order of fitting.py:457-460.                                             */
+int  sfx_objective_eval(const sfx_objective_cfg* cfg, const sfx_objective_in* in, const sfx_objective_grads* grads,
+                        float* loss_dev, void* stream);
+
+/* SMPLifyCameraInitLoss.forward (fitting.py:499-520) in the same way: squared pixel residuals of the keypoints of
+ * init_joints_idxs plus the depth term, with gradients to joints, rotation and translation.  init_count_dev [K]: how often
+ * keypoint k appears in init_joints_idxs (index_select repeats a repeated index; 0 = not selected: contributes exactly 0).
+ * use_conf reproduces the broadcast of :509-511 (oracle/objective.py:camera_init_loss): every residual is weighted by the SUM
+ * of the selected keypoints' squared confidences (joints_conf_dev [B][K]).  est_tz_dev [B] = trans_estimation[:, 2]; NULL, or
+ * depth_loss_weight <= 0: no depth term.  Refusals as sfx_objective_eval.                                                */
+typedef struct sfx_camera_init_cfg {
+    float   data_weight, depth_loss_weight;
+    int32_t use_conf;
+} sfx_camera_init_cfg;
+int  sfx_camera_init_eval(const sfx_camera_init_cfg* cfg, int32_t B, int32_t K,
+                          const float* joints_dev, const float* cam_rot_dev, const float* cam_t_dev,
+                          const float* focal_x_dev, const float* focal_y_dev, const float* center_dev,
+                          const float* gt_joints_dev, const float* init_count_dev, const float* joints_conf_dev /* or NULL */,
+                          const float* est_tz_dev /* or NULL */, float* loss_dev, float* d_joints_dev /* [B][K][3] or NULL */,
+                          float* d_cam_rot_dev /* [B][3][3] or NULL */, float* d_cam_t_dev /* [B][3] or NULL */, void* stream);
+
 /* Gaussian-mixture body pose prior (MaxMixturePrior, smplifyx/prior.py:100-231; body_prior_type 'gmm'):
  * used by the closure when use_vposer is off and the batch has no regression pose (fitting.py:399-401).
  * means [M][D], precisions [M][D][D], nll_weights [M] = the module's buffers; D = 63, M <= 8 (HOST). */

@@ -81,6 +81,38 @@ class OptCfg(C.Structure):
     ]
 
 
+class ObjectiveCfg(C.Structure):
+    """sfx_objective_cfg: weights, flags and pose-prior form of SMPLifyLoss for sfx_objective_eval (pointers: DEVICE)."""
+    _fields_ = [
+        ("rho", C.c_float), ("data_weight", C.c_float), ("body_pose_weight", C.c_float), ("shape_weight", C.c_float),
+        ("bending_prior_weight", C.c_float), ("hand_prior_weight", C.c_float), ("expr_prior_weight", C.c_float),
+        ("jaw_prior_weight", C.c_float * 3),
+        ("use_joints_conf", C.c_int32), ("use_hands", C.c_int32), ("use_face", C.c_int32), ("prior_form", C.c_int32),
+        ("gmm_M", C.c_int32), ("gmm_D", C.c_int32),
+        ("gmm_means_dev", C.c_void_p), ("gmm_precisions_dev", C.c_void_p), ("gmm_nll_weights_dev", C.c_void_p),
+        ("gmm_comp_const_dev", C.c_void_p),
+    ]
+
+
+# the tensors of sfx_objective_in / sfx_objective_grads, in the structures' order
+OBJECTIVE_INPUTS = ("joints", "cam_rot", "cam_t", "focal_x", "focal_y", "center", "gt_joints", "joints_conf", "joint_weights",
+                    "body_pose", "prior", "prior_target", "betas", "expression", "jaw", "lhand", "rhand")
+OBJECTIVE_GRADS = ("joints", "cam_rot", "cam_t", "body_pose", "prior", "betas", "expression", "jaw", "lhand", "rhand")
+
+
+class ObjectiveIn(C.Structure):
+    _fields_ = ([("B", C.c_int32), ("K", C.c_int32), ("n_prior", C.c_int32), ("num_betas", C.c_int32), ("num_expr", C.c_int32)]
+                + [(n + "_dev", C.c_void_p) for n in OBJECTIVE_INPUTS])
+
+
+class ObjectiveGrads(C.Structure):
+    _fields_ = [("d_" + n + "_dev", C.c_void_p) for n in OBJECTIVE_GRADS]
+
+
+class CameraInitCfg(C.Structure):
+    _fields_ = [("data_weight", C.c_float), ("depth_loss_weight", C.c_float), ("use_conf", C.c_int32)]
+
+
 # every symbol include/sfx.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "sfx_model_create": (C.c_int, [C.POINTER(ModelDesc), C.POINTER(C.c_void_p)]),
@@ -132,6 +164,10 @@ SYMBOLS = {
     "sfx_opt_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, f32p, i32p, i32p]),
     "sfx_opt_trace": (C.c_int, [C.c_void_p, C.c_int32]),
     "sfx_opt_get_trace": (C.c_int, [C.c_void_p, f32p, i32p]),
+    # cfg, in, grads (or NULL), loss, stream
+    "sfx_objective_eval": (C.c_int, [C.POINTER(ObjectiveCfg), C.POINTER(ObjectiveIn), C.POINTER(ObjectiveGrads), C.c_void_p, C.c_void_p]),
+    # cfg, B, K, joints, rotation, translation, focal x / y, center, gt, init_count, conf, est_tz, loss, three gradients, stream
+    "sfx_camera_init_eval": (C.c_int, [C.POINTER(CameraInitCfg), C.c_int32, C.c_int32] + [C.c_void_p] * 14 + [C.c_void_p]),
     "sfx_pen_create": (C.c_int, [C.c_int32, C.c_int32, i32p, i32p, i32p, i32p, C.c_int32, C.c_int32, C.c_int32,
                                  C.POINTER(C.c_void_p)]),
     "sfx_pen_destroy": (None, [C.c_void_p]),

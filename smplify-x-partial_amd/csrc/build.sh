@@ -22,8 +22,9 @@ $HIPCC $FLAGS -c "$HERE/lbs_backward.hip" -o "$OBJ/lbs_backward.o" & pids+=($!)
 $HIPCC $FLAGS -c "$HERE/vposer_batch.hip" -o "$OBJ/vposer_batch.o" & pids+=($!)
 $HIPCC $FLAGS -c "$HERE/vposer_encode.hip" -o "$OBJ/vposer_encode.o" & pids+=($!)
 $HIPCC $FLAGS -ffp-contract=off -c "$HERE/opt_ext.hip" -o "$OBJ/opt_ext.o" & pids+=($!)
+$HIPCC $FLAGS -c "$HERE/objective_ext.hip" -o "$OBJ/objective_ext.o" & pids+=($!)
 for p in "${pids[@]}"; do wait $p; done
 $HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/$NAME" "$OBJ/api.o" "$OBJ/closure.o" \
     "$OBJ/lbs_dense.o" "$OBJ/lbfgs.o" "$OBJ/fused.o" "$OBJ/collide.o" "$OBJ/lbs_adjoint.o" "$OBJ/lbs_backward.o" \
-    "$OBJ/vposer_batch.o" "$OBJ/vposer_encode.o" "$OBJ/opt_ext.o"
+    "$OBJ/vposer_batch.o" "$OBJ/vposer_encode.o" "$OBJ/opt_ext.o" "$OBJ/objective_ext.o"
 echo "built $OUT/$NAME"

@@ -646,12 +646,10 @@ class FrameBatch(object):
         mu = np.ascontiguousarray(prior.means.detach().cpu().numpy(), np.float32)
         P = np.ascontiguousarray(prior.precisions.detach().cpu().numpy(), np.float32)
         nw = np.ascontiguousarray(prior.nll_weights.detach().cpu().numpy().reshape(-1), np.float32)
-        cc = None
-        if not getattr(prior, "use_merged", True):
-            # MaxMixturePrior.log_likelihood (prior.py:203-225): d^T P d + 0.5 (log(det cov + eps) + D log 2 pi) per component
-            import torch
-            cov_term = torch.log(torch.det(prior.covs) + prior.epsilon)
-            cc = np.ascontiguousarray((0.5 * (cov_term + prior.random_var_dim * prior.pi_term)).detach().cpu().numpy().reshape(-1), np.float32)
+        # MaxMixturePrior.log_likelihood (prior.py:203-225): d^T P d + 0.5 (log(det cov + eps) + D log 2 pi) per component
+        cc = prior.component_constants() if hasattr(prior, "component_constants") else None
+        if cc is not None:
+            cc = np.ascontiguousarray(cc.detach().cpu().numpy().reshape(-1), np.float32)
         capi.check(self._lib.sfx_batch_set_gmm_form(self._h, mu.shape[0], mu.shape[1], capi.fptr(mu), capi.fptr(P), capi.fptr(nw),
                                                     capi.fptr(cc) if cc is not None else None))
 
@@ -889,6 +887,173 @@ class BatchOptimizer(object):
             self.close()
         except Exception:
             pass
+
+
+# ---- the objective on tensors the caller supplies (sfx_objective_eval / sfx_camera_init_eval, csrc/objective_ext.hip) --------
+PRIOR_FORMS = dict(embedding=0, target=1, body_pose=2, mixture=3)      # SFX_PRIOR_*
+OBJECTIVE_MAX_K = 512                                                   # keypoints per frame (OBJ_MAX_K)
+OBJECTIVE_WEIGHTS = ("data_weight", "body_pose_weight", "shape_weight", "bending_prior_weight", "hand_prior_weight",
+                     "expr_prior_weight")
+# gradient names of objective_eval, in the order of sfx_objective_grads
+OBJECTIVE_GRADS = ("joints", "rotation", "translation", "body_pose", "prior", "betas", "expression", "jaw_pose",
+                   "left_hand_pose", "right_hand_pose")
+
+
+def _obj_in(name, t, shape, dev):
+    """One input of the stand-alone objective: a float32 contiguous CUDA tensor of `shape` on `dev` (None passes through)."""
+    import torch
+    if t is None:
+        return None
+    if not torch.is_tensor(t):
+        raise TypeError("%s: a torch tensor is needed, got %s" % (name, type(t).__name__))
+    if t.device.type != "cuda":
+        raise ValueError("%s: a CUDA tensor is needed (no CPU fallback), got device %s" % (name, t.device))
+    if dev is not None and t.device != dev:
+        raise ValueError("%s: on %s, joints on %s" % (name, t.device, dev))
+    if t.dtype != torch.float32:
+        raise ValueError("%s: float32 is needed, got %s" % (name, t.dtype))
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError("%s: shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
+    if not t.is_contiguous():
+        raise ValueError("%s: a contiguous tensor is needed (strides %s)" % (name, tuple(t.stride())))
+    return t.detach()
+
+
+def _obj_joints(joints):
+    import torch
+    if not torch.is_tensor(joints) or joints.dim() != 3 or joints.shape[2] != 3:
+        raise ValueError("joints: shape %s, expected (B, K, 3)" % (tuple(getattr(joints, "shape", ())),))
+    B, K = int(joints.shape[0]), int(joints.shape[1])
+    if B < 1:
+        raise ValueError("joints: at least one frame is needed, got B = %d" % B)
+    if K < 1 or K > OBJECTIVE_MAX_K:
+        raise ValueError("joints: K = %d keypoints, supported 1..%d" % (K, OBJECTIVE_MAX_K))
+    return B, K, _obj_in("joints", joints, (B, K, 3), None)
+
+
+def _obj_ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def objective_eval(joints, rotation, translation, focal_x, focal_y, center, gt_joints, joint_weights, body_pose, prior, betas,
+                   joints_conf=None, prior_target=None, expression=None, jaw_pose=None, left_hand_pose=None,
+                   right_hand_pose=None, weights=None, jaw_prior_weight=(0.0, 0.0, 0.0), rho=100.0, use_joints_conf=True,
+                   use_hands=True, use_face=True, prior_form="embedding", mixture=None, want_grads=True, stream=None):
+    """SMPLifyLoss.forward (fitting.py:375-461, no interpenetration) and its gradient for B frames in one launch
+    (sfx_objective_eval).  Every tensor is a float32 contiguous CUDA tensor: joints [B, K, 3], rotation [B, 3, 3],
+    translation [B, 3], focal_x / focal_y [B], center [B, 2], gt_joints [B, K, 2], joints_conf / joint_weights [B, K],
+    body_pose [B, 63] (the angle prior's operand), prior [B, n] (the pose prior's operand; prior_form 'embedding' | 'target' --
+    with prior_target [B, n] -- | 'body_pose' | 'mixture' -- with mixture = dict(means [M, 63], precisions [M, 63, 63],
+    nll_weights [M], comp_const [M] or None: CUDA tensors as prior.mixture_tables makes them)), betas, expression, jaw_pose
+    [B, 3], left_hand_pose / right_hand_pose [B, 45].  weights: {name: float} over OBJECTIVE_WEIGHTS (missing = 0).
+    Returns (loss [B], {name: gradient of loss[b] with respect to that input} over OBJECTIVE_GRADS) -- ({} when
+    want_grads is off).  Only enqueues on the current (or the given) stream."""
+    import torch
+    B, K, joints = _obj_joints(joints)
+    dev = joints.device
+    if prior_form not in PRIOR_FORMS:
+        raise ValueError("prior_form: one of %s, got %r" % (sorted(PRIOR_FORMS), prior_form))
+    if not torch.is_tensor(prior) or prior.dim() != 2:
+        raise ValueError("prior: shape %s, expected (B, n)" % (tuple(getattr(prior, "shape", ())),))
+    n = int(prior.shape[1])
+    nb = int(betas.shape[1]) if torch.is_tensor(betas) and betas.dim() == 2 else -1
+    ne = int(expression.shape[1]) if torch.is_tensor(expression) and expression.dim() == 2 else 0
+    if use_joints_conf and joints_conf is None:
+        raise ValueError("use_joints_conf needs joints_conf")
+    if prior_form == "target" and prior_target is None:
+        raise ValueError("prior_form 'target' needs prior_target")
+    if use_hands and (left_hand_pose is None or right_hand_pose is None):
+        raise ValueError("use_hands needs left_hand_pose and right_hand_pose")
+    if use_face and (expression is None or jaw_pose is None):
+        raise ValueError("use_face needs expression and jaw_pose")
+    ins = dict(joints=joints,
+               cam_rot=_obj_in("rotation", rotation, (B, 3, 3), dev), cam_t=_obj_in("translation", translation, (B, 3), dev),
+               focal_x=_obj_in("focal_x", focal_x, (B,), dev), focal_y=_obj_in("focal_y", focal_y, (B,), dev),
+               center=_obj_in("center", center, (B, 2), dev), gt_joints=_obj_in("gt_joints", gt_joints, (B, K, 2), dev),
+               joints_conf=_obj_in("joints_conf", joints_conf, (B, K), dev),
+               joint_weights=_obj_in("joint_weights", joint_weights, (B, K), dev),
+               body_pose=_obj_in("body_pose", body_pose, (B, 63), dev), prior=_obj_in("prior", prior, (B, n), dev),
+               prior_target=_obj_in("prior_target", prior_target, (B, n), dev) if prior_form == "target" else None,
+               betas=_obj_in("betas", betas, (B, nb), dev),
+               expression=_obj_in("expression", expression, (B, ne), dev) if use_face else None,
+               jaw=_obj_in("jaw_pose", jaw_pose, (B, 3), dev) if use_face else None,
+               lhand=_obj_in("left_hand_pose", left_hand_pose, (B, 45), dev) if use_hands else None,
+               rhand=_obj_in("right_hand_pose", right_hand_pose, (B, 45), dev) if use_hands else None)
+    c = capi.ObjectiveCfg()
+    c.rho = float(rho)
+    weights = weights or {}
+    unknown = set(weights) - set(OBJECTIVE_WEIGHTS)
+    if unknown:
+        raise TypeError("objective_eval: unknown weights %s (known: %s)" % (sorted(unknown), ", ".join(OBJECTIVE_WEIGHTS)))
+    for name in OBJECTIVE_WEIGHTS:
+        setattr(c, name, float(weights.get(name, 0.0)))
+    for q in range(3):
+        c.jaw_prior_weight[q] = float(jaw_prior_weight[q])
+    c.use_joints_conf, c.use_hands, c.use_face = int(bool(use_joints_conf)), int(bool(use_hands)), int(bool(use_face))
+    c.prior_form = PRIOR_FORMS[prior_form]
+    keep = []
+    if prior_form == "mixture":
+        if mixture is None:
+            raise ValueError("prior_form 'mixture' needs the mixture's tables")
+        mu = mixture["means"]
+        if not torch.is_tensor(mu) or mu.dim() != 2:
+            raise ValueError("mixture['means']: a [M, D] tensor is needed")
+        M, D = int(mu.shape[0]), int(mu.shape[1])
+        if D != 63 or n != 63:
+            raise ValueError("the mixture prior acts on the 63 body-pose values: means [M, %d], operand [B, %d]" % (D, n))
+        keep = [_obj_in("mixture['means']", mu, (M, D), dev), _obj_in("mixture['precisions']", mixture["precisions"], (M, D, D), dev),
+                _obj_in("mixture['nll_weights']", mixture["nll_weights"], (M,), dev),
+                _obj_in("mixture['comp_const']", mixture.get("comp_const"), (M,), dev)]
+        c.gmm_M, c.gmm_D = M, D
+        c.gmm_means_dev, c.gmm_precisions_dev, c.gmm_nll_weights_dev, c.gmm_comp_const_dev = [t.data_ptr() if t is not None else None for t in keep]
+    a = capi.ObjectiveIn()
+    a.B, a.K, a.n_prior, a.num_betas, a.num_expr = B, K, n, nb, ne
+    for name in capi.OBJECTIVE_INPUTS:
+        setattr(a, name + "_dev", ins[name].data_ptr() if ins[name] is not None else None)
+    loss = torch.empty([B], dtype=torch.float32, device=dev)
+    grads, g = {}, None
+    if want_grads:
+        like = dict(joints=ins["joints"], rotation=ins["cam_rot"], translation=ins["cam_t"], body_pose=ins["body_pose"],
+                    prior=ins["prior"], betas=ins["betas"], expression=ins["expression"], jaw_pose=ins["jaw"],
+                    left_hand_pose=ins["lhand"], right_hand_pose=ins["rhand"])
+        g = capi.ObjectiveGrads()
+        for name, field in zip(OBJECTIVE_GRADS, capi.OBJECTIVE_GRADS):
+            if like[name] is not None:
+                grads[name] = torch.empty_like(like[name])
+                setattr(g, "d_" + field + "_dev", grads[name].data_ptr())
+    s = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
+    with torch.cuda.device(dev):
+        capi.check(capi.load().sfx_objective_eval(C.byref(c), C.byref(a), C.byref(g) if g is not None else None, _obj_ptr(loss), s))
+    return loss, grads
+
+
+def camera_init_eval(joints, rotation, translation, focal_x, focal_y, center, gt_joints, init_count, joints_conf=None,
+                     est_tz=None, data_weight=1.0, depth_loss_weight=0.0, use_conf=False, want_grads=True, stream=None):
+    """SMPLifyCameraInitLoss.forward (fitting.py:499-520) and its gradient for B frames in one launch (sfx_camera_init_eval).
+    Tensors as objective_eval; init_count [K]: how often keypoint k appears in init_joints_idxs; joints_conf [B, K] (use_conf:
+    the broadcast of :509-511); est_tz [B] = trans_estimation[:, 2] or None (no depth term).
+    Returns (loss [B], dict(joints=, rotation=, translation=))."""
+    import torch
+    B, K, joints = _obj_joints(joints)
+    dev = joints.device
+    if use_conf and joints_conf is None:
+        raise ValueError("use_conf needs joints_conf")
+    ins = [joints, _obj_in("rotation", rotation, (B, 3, 3), dev), _obj_in("translation", translation, (B, 3), dev),
+           _obj_in("focal_x", focal_x, (B,), dev), _obj_in("focal_y", focal_y, (B,), dev), _obj_in("center", center, (B, 2), dev),
+           _obj_in("gt_joints", gt_joints, (B, K, 2), dev), _obj_in("init_count", init_count, (K,), dev),
+           _obj_in("joints_conf", joints_conf, (B, K), dev) if use_conf else None, _obj_in("est_tz", est_tz, (B,), dev)]
+    c = capi.CameraInitCfg()
+    c.data_weight, c.depth_loss_weight, c.use_conf = float(data_weight), float(depth_loss_weight), int(bool(use_conf))
+    loss = torch.empty([B], dtype=torch.float32, device=dev)
+    grads = {}
+    if want_grads:
+        grads = dict(joints=torch.empty_like(ins[0]), rotation=torch.empty_like(ins[1]), translation=torch.empty_like(ins[2]))
+    s = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
+    with torch.cuda.device(dev):
+        capi.check(capi.load().sfx_camera_init_eval(C.byref(c), B, K, *[_obj_ptr(t) for t in ins], _obj_ptr(loss),
+                                                    _obj_ptr(grads.get("joints")), _obj_ptr(grads.get("rotation")),
+                                                    _obj_ptr(grads.get("translation")), s))
+    return loss, grads
 
 
 def prof_enable(on=True, every=1):

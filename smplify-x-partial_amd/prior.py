@@ -114,6 +114,13 @@ class MaxMixturePrior(nn.Module):
     def merged_log_likelihood(self, pose, betas=None):
         return (0.5 * self._quadratic_forms(pose) - torch.log(self.nll_weights)).min(dim=1)[0]
 
+    def component_constants(self):
+        """[M] 0.5 (log(det cov_m + eps) + D log 2 pi): the constant of a component in the per-component form (prior.py:203-225),
+        the `comp_const` table of sfx_batch_set_gmm_form and sfx_objective_cfg; None for the merged form, which has none."""
+        if self.use_merged:
+            return None
+        return (0.5 * (torch.log(torch.det(self.covs) + self.epsilon) + self.random_var_dim * self.pi_term)).reshape(-1)
+
     def log_likelihood(self, pose, betas=None, *args, **kwargs):
         """The per-component form (prior.py:203-231; written for batch 1 there, and here)."""
         const = 0.5 * (torch.log(torch.det(self.covs) + self.epsilon) + self.random_var_dim * self.pi_term)      # [M]

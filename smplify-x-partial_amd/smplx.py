@@ -27,7 +27,9 @@ _ModelOutput.__new__.__defaults__ = (None,) * len(_ModelOutput._fields)
 
 class ModelOutput(_ModelOutput):
     """smplx.ModelOutput (a namedtuple).  Outputs of SMPLX.forward below also remember the model and the exact parameter
-    tensors they were made from (`_model`, `_inputs`): the stand-alone SMPLifyLoss.forward evaluates the device objective there."""
+    tensors they were made from (`_model`, `_inputs`): the stand-alone SMPLifyLoss.forward evaluates the device objective there.
+    Outputs of a differentiable model also carry `_graph`: the picked prior operands with their autograd graphs (the echoed fields
+    are detached), which a loss made with create_loss(differentiable=True) reads."""
 
 
 SMPLXOutput = ModelOutput
@@ -203,6 +205,9 @@ class SMPLX(nn.Module):
         lh = pick(left_hand_pose, "left_hand_pose", self.num_pca_comps)
         rh = pick(right_hand_pose, "right_hand_pose", self.num_pca_comps)
         verts, joints, full_pose = _LBS.apply(dm, return_verts, go, bp, be, ex, jw, le, re, lh, rh)
+        # the picked tensors WITH their graphs (the echoed fields below stay detached): where a differentiable loss
+        # (fitting.create_loss(differentiable=True)) takes its prior operands from
+        graph = dict(body_pose=bp, betas=be, expression=ex, jaw_pose=jw, left_hand_pose=lh, right_hand_pose=rh)
         cast = lambda x: x.to(self.dtype) if x is not None else None
         verts, joints, full_pose = cast(verts), cast(joints), cast(full_pose)
         be, go, bp, ex, jw = (cast(x.detach()) for x in (be, go, bp, ex, jw))
@@ -213,8 +218,22 @@ class SMPLX(nn.Module):
         out = ModelOutput(vertices=verts, joints=joints, full_pose=full_pose if return_full_pose else None, betas=be,
                           global_orient=go, body_pose=bp, expression=ex, left_hand_pose=full_pose[:, 75:120] - pm(75),
                           right_hand_pose=full_pose[:, 120:165] - pm(120), jaw_pose=jw)
-        out._model, out._inputs = self, inputs
+        out._model, out._inputs, out._graph = self, inputs, graph
         return out
+
+    def hand_pose_45(self, coeffs, side):
+        """The 45 axis-angle values of a hand WITHOUT the mean (what ModelOutput.left_hand_pose / right_hand_pose carry) from the
+        module's hand parameters: pca @ components in torch, so that a graph on the coefficients is kept (use_pca=False: the
+        values themselves)."""
+        if not self.use_pca:
+            return coeffs
+        comps = getattr(self, "_hand_comps", None)
+        if comps is None or comps[0].device != coeffs.device:
+            d = self._model_data
+            comps = tuple(torch.as_tensor(np.asarray(d[k], np.float32)[:self.num_pca_comps], device=coeffs.device)
+                          for k in ("hands_componentsl", "hands_componentsr"))
+            self._hand_comps = comps
+        return coeffs.to(torch.float32) @ comps[0 if side == "left" else 1]
 
 
 def dm_pose_mean(model, start):
