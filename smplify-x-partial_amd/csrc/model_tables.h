@@ -132,14 +132,15 @@ static inline int sfx_build_model_tables(const sfx_model_desc* d, ModelTables* o
     T.dynp_vid.assign((size_t)rows * nd, 0); T.dynp_w.assign((size_t)rows * nd, 0.f); T.dynp_vt.assign((size_t)rows * nd * 3, 0.f);
     T.dynp_wj.assign(rows * RB, 0); T.dynp_ww.assign(rows * RB, 0.f);
     T.dynp_js.assign((size_t)rows * (SFX_J + 1), 0); T.dynp_ji.assign(rows * RB, 0); T.dynp_jw.assign(rows * RB, 0.f);
-    // (kept as it was: once a row overflows, the blocks of the rows after it stay zero although closure_body reads them with
-    // dynp_js absent -- no model reaches this; the fix belongs in a change of its own, with a GPU parity test of that path)
+    // Row overflow: a row whose vertices carry more than nd * SFX_NW weights in all does not fit the per-joint part of its
+    // block.  Then no row's dynp_js / dynp_ji / dynp_jw is used (dynp_js is dropped, closure_body walks dj_* instead); the
+    // forward part of EVERY row's block (dynp_vid / w / vt / wj / ww / us) is filled regardless: closure_body reads it for
+    // whatever row the head pose selects.
     bool fit = true;
     std::vector<int> vids(nd);
     for (int row = 0; row < rows; ++row) {
         for (int q = 0; q < nd; ++q) vids[q] = sfx_dyn_vertex(d, row, idyn[ns + q] / 3, idyn[ns + q] % 3);
         by_joint(vids.data(), ns, nd, T.dj_start, T.dj_item, T.dj_w);
-        if (!fit) continue;
         for (int q = 0; q < nd; ++q) {
             const int l = idyn[ns + q] / 3, c = idyn[ns + q] % 3, v = vids[q];
             const size_t o = (size_t)row * nd + q;
@@ -147,13 +148,14 @@ static inline int sfx_build_model_tables(const sfx_model_desc* d, ModelTables* o
             std::memcpy(&T.dynp_vt[o * 3], d->v_template + (size_t)v * 3, 3 * sizeof(float));
             sfx_pack_weights(W, v, &T.dynp_wj[o * SFX_NW], &T.dynp_ww[o * SFX_NW]);
         }
+        if (!fit) continue;
         const int* st = &T.dj_start[(size_t)row * (SFX_J + 1)];
         const size_t n_row = st[SFX_J] - st[0];
         if (n_row > RB) { fit = false; continue; }      // (> SFX_NW weights per vertex on average: the closure reads dj_*)
         for (int j = 0; j <= SFX_J; ++j) T.dynp_js[(size_t)row * (SFX_J + 1) + j] = st[j] - st[0];
         std::copy_n(&T.dj_item[st[0]], n_row, &T.dynp_ji[row * RB]); std::copy_n(&T.dj_w[st[0]], n_row, &T.dynp_jw[row * RB]);
     }
-    if (!fit) T.dynp_js.clear();
+    if (!fit) { T.dynp_js.clear(); T.dynp_ji.assign(rows * RB, 0); T.dynp_jw.assign(rows * RB, 0.f); }
     // export slots: distinct vertices of the static items and of every vertex a dynamic item can land on (all LUT rows) -- the
     // dense GEMM hands their blend offsets to the per-frame kernel, which then streams no blend-shape row forward
     T.vslot.assign(T.Vpad, -1); T.item_uslot.assign(ni, -1); T.dynp_us.resize(T.dynp_vid.size());

@@ -243,8 +243,13 @@ TOPOLOGY_FILE = "smplx_topology.npz"
 def _topology_path(path=None):
     import os
     if path is None:
-        path = os.environ.get("SFX_SMPLX_TOPOLOGY") or os.path.join(
-            os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
+        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        path = os.environ.get("SFX_SMPLX_TOPOLOGY") or os.path.join(root, "tests", "golden")
+        # tools/make_topology.py keeps a second copy beside the other products built from the reference tree: a tests/
+        # directory that was checked out afresh (another revision's tests on this build) has lost the first one
+        spare = os.path.join(root, "oracle", "_ref", TOPOLOGY_FILE)
+        if os.path.isdir(path) and not os.path.isfile(os.path.join(path, TOPOLOGY_FILE)) and os.path.isfile(spare):
+            return spare
     if os.path.isdir(path):
         path = os.path.join(path, TOPOLOGY_FILE)
     return path

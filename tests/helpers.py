@@ -132,6 +132,88 @@ def engine_batch_from_frames(dm, cfg, frames, idx, lbs_mode="rows", reuse=False)
 
 
 # ---------------------------------------------------------------------------------------------------------
+# A model with dense skinning weights.  synthetic.make_synthetic_model gives a vertex at most 3 nonzero weights and a 16-vertex
+# tile at most 6 joints; a licensed SMPL-X model is not that sparse, and the library has a path of its own wherever a vertex
+# has more than SFX_NW = 8 weights (the full-row fallbacks of csrc/) or a tile many joints (the skinning epilogue's joint groups).
+SFX_NW, SFX_JPAD, DENSE_TILE = 8, 56, 16
+DENSE_TILE_CLASSES = 6                                  # class of tile t: t % 6; the last, partial tile: class 4
+DENSE_CLASS_COUNT = {1: 8, 2: 9, 3: 12, 4: 55}          # nonzero weights per vertex; classes 0 and 5: the model's own rows
+DENSE_KEYPOINT_COUNT = 12                               # every vertex a keypoint can read, whatever its tile
+_DENSE_MODELS = {}
+
+
+def dense_tile_classes(V):
+    """[ceil(V / 16)] class of every 16-vertex tile of dense_weights_model."""
+    nt = (V + DENSE_TILE - 1) // DENSE_TILE
+    cls = np.arange(nt) % DENSE_TILE_CLASSES
+    cls[-1] = 4
+    return cls
+
+
+def keypoint_vertices(model):
+    """Sorted ids of every vertex a keypoint can read: the extra vertices, the corners of the static landmarks' faces and of
+    every LUT row's dynamic-contour faces."""
+    f = np.asarray(model["f"]).astype(np.int64)
+    return np.unique(np.concatenate([np.asarray(model["extra_vertex_ids"]).astype(np.int64).ravel(),
+                                     f[np.asarray(model["lmk_faces_idx"]).astype(np.int64)].ravel(),
+                                     f[np.asarray(model["dynamic_lmk_faces_idx"]).astype(np.int64)].ravel()]))
+
+
+def dense_weights_model(model, eps=0.1, seed=4):
+    """A copy of `model` with only `weights` changed: W' = (1 - eps) W + eps R, R a random row on joints the vertex does not
+    use yet, normalised to sum 1 -- the rows still sum to 1 and the mesh stays near the original.  Tiles of class 1 .. 4
+    (dense_tile_classes) have every vertex topped up to exactly 8 (the last count that packs), 9 (the first that falls back
+    to the full row), 12 and 55 nonzeros; every vertex a keypoint can read gets 12 whatever its tile.  Cached per (model,
+    eps, seed); the result is shared and must not be written to."""
+    key = (id(model), float(eps), int(seed))
+    if key in _DENSE_MODELS:
+        return _DENSE_MODELS[key][1]
+    W = np.asarray(model["weights"], np.float64)
+    V, J = W.shape
+    assert J == SFX_JPAD - 1
+    cls = dense_tile_classes(V)
+    want = np.zeros(V, np.int64)
+    for c, n in DENSE_CLASS_COUNT.items():
+        want[np.repeat(cls == c, DENSE_TILE)[:V]] = n
+    kv = keypoint_vertices(model)
+    want[kv] = DENSE_KEYPOINT_COUNT
+    have = (W != 0).sum(1)
+    add = np.where(want > 0, want - have, 0)
+    assert add.min() >= 0 and have.max() <= 3, (add.min(), have.max())
+    rng = np.random.RandomState(seed)
+    order = rng.uniform(size=(V, J))
+    order[W != 0] = 2.0                                             # joints in use sort last
+    rank = np.argsort(np.argsort(order, axis=1), axis=1)
+    R = np.where(rank < add[:, None], rng.uniform(0.2, 1.0, size=(V, J)), 0.0)
+    assert np.all(R[W != 0] == 0)
+    top = add > 0
+    R[top] /= R[top].sum(1, keepdims=True)
+    Wd = W.copy()
+    Wd[top] = (1.0 - eps) * W[top] + eps * R[top]
+    Wd = Wd.astype(np.asarray(model["weights"]).dtype)
+    # ---- preconditions the tests rely on
+    nz = (Wd != 0).sum(1)
+    assert np.abs(Wd.astype(np.float64).sum(1) - 1.0).max() <= 1e-6
+    assert set(np.unique(nz)) == {1, 2, 3, 8, 9, 12, 55}, np.unique(nz)
+    assert np.all(nz[top] == want[top]) and np.array_equal(Wd[~top], np.asarray(model["weights"])[~top])
+    assert np.all(nz[kv] == DENSE_KEYPOINT_COUNT) and np.all(nz[V - V % DENSE_TILE:] >= DENSE_KEYPOINT_COUNT)
+    pad = np.zeros((len(cls) * DENSE_TILE, J), bool)
+    pad[:V] = Wd != 0
+    union = pad.reshape(len(cls), DENSE_TILE, J).any(1).sum(1)      # joints per tile: tj_n before its padding to 4
+    assert union.min() == 1 and union.max() == SFX_JPAD - 1 and union[-1] == SFX_JPAD - 1, (union.min(), union.max())
+    assert np.any(union % 4 == 0) and np.any(union % 4 != 0)
+    # the row-overflow condition of csrc/model_tables.h for LUT row 0, from the model: its dynamic vertices carry more than
+    # nd * SFX_NW weights together, so the per-joint lists of the rows do not fit their blocks
+    f = np.asarray(model["f"]).astype(np.int64)
+    dv0 = f[np.asarray(model["dynamic_lmk_faces_idx"]).astype(np.int64)[0]].ravel()
+    assert nz[dv0].sum() > dv0.size * SFX_NW, (nz[dv0].sum(), dv0.size * SFX_NW)
+    out = dict(model)
+    out["weights"] = Wd
+    _DENSE_MODELS[key] = (model, out)                               # (the base model is kept alive: its id is the key)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------
 # Closure-level parity bounds (SURVEY.md 8d: loss 1e-5; north_star: 1e-4 on the gradient), shared by every
 # closure-vs-oracle comparison of the GPU suite, __graft_entry__.smoke() and bench.py's closure_parity object.
 # Every comparison is recorded in PARITY_LOG; conftest prints the observed maxima per (label, stage) at the end

@@ -219,18 +219,14 @@ static void check_tables(Desc& D, const ModelTables& T, bool expect_blocks) {
     CHECK(T.dynp_wj.size() == (size_t)ROWS * nd * SFX_NW && T.dynp_ww.size() == T.dynp_wj.size() && T.dynp_ji.size() == T.dynp_wj.size() && T.dynp_jw.size() == T.dynp_wj.size());
     CHECK(T.dj_start.size() == (size_t)ROWS * (SFX_J + 1) && T.dj_item.size() == T.dj_w.size() && T.dynp_us.size() == T.dynp_vid.size());
     CHECK(T.dynp_js.size() == (expect_blocks ? T.dj_start.size() : 0));
-    int dyn_over = 0, rows_over = 0;
+    int dyn_over = 0, rows_over = 0, rows_after_over = 0;
     for (int row = 0; row < ROWS; ++row) {
         std::vector<int> vids;
         for (int q = 0; q < nd; ++q) {
             const int l = idyn[ns + q] / 3, c = idyn[ns + q] % 3, v = D.faces[D.df[row * NDYN + l] * 3 + c];
             const size_t o = (size_t)row * nd + q;
             vids.push_back(v);
-            if (rows_over) {        // as it always was: the blocks of the rows after an overflowing one are left zero
-                CHECK(T.dynp_vid[o] == 0 && T.dynp_w[o] == 0.f && T.dynp_vt[o * 3] == 0.f && T.dynp_vt[o * 3 + 1] == 0.f && T.dynp_vt[o * 3 + 2] == 0.f);
-                for (int e = 0; e < SFX_NW; ++e) CHECK(T.dynp_wj[o * SFX_NW + e] == 0 && T.dynp_ww[o * SFX_NW + e] == 0.f);
-                continue;
-            }
+            // the forward part of every row's block is filled, the rows of and after an overflowing one included
             CHECK(T.dynp_vid[o] == v && T.dynp_w[o] == D.db[(row * NDYN + l) * 3 + c]);
             for (int e = 0; e < 3; ++e) CHECK(T.dynp_vt[o * 3 + e] == D.vt[v * 3 + e]);
             check_packed(D, v, &T.dynp_wj[o * SFX_NW], &T.dynp_ww[o * SFX_NW]); dyn_over += T.dynp_wj[o * SFX_NW] == -1;
@@ -238,14 +234,19 @@ static void check_tables(Desc& D, const ModelTables& T, bool expect_blocks) {
         const int* st = &T.dj_start[(size_t)row * (SFX_J + 1)];
         CHECK(st[0] == (row ? st[-1] : 0) && (row + 1 < ROWS || st[SFX_J] == (int)T.dj_item.size()));
         check_lists(D, st, 0, T.dj_item.data(), T.dj_w.data(), ns, vids.data(), nd);
+        rows_after_over += rows_over > 0;
         rows_over += st[SFX_J] - st[0] > nd * SFX_NW;
-        if (T.dynp_js.empty()) continue;
+        if (T.dynp_js.empty()) {        // row overflow: the per-joint part of the blocks is dropped (dj_* serve), left zero
+            for (int q = 0; q < nd * SFX_NW; ++q) CHECK(T.dynp_ji[(size_t)row * nd * SFX_NW + q] == 0 && T.dynp_jw[(size_t)row * nd * SFX_NW + q] == 0.f);
+            continue;
+        }
         const int* js = &T.dynp_js[(size_t)row * (SFX_J + 1)];
         for (int j = 0; j <= SFX_J; ++j) CHECK(js[j] == st[j] - st[0]);
         CHECK(js[SFX_J] <= nd * SFX_NW);
         check_lists(D, js, 0, &T.dynp_ji[(size_t)row * nd * SFX_NW], &T.dynp_jw[(size_t)row * nd * SFX_NW], ns, vids.data(), nd);
     }
     CHECK(dyn_over >= 1 && (rows_over == 0) == expect_blocks);
+    CHECK(expect_blocks || rows_after_over >= 1);      // (the overflow descriptor has a row after the overflowing one)
     // export slots
     std::set<int> uniq(ivid.begin(), ivid.begin() + ns), slots; uniq.insert(T.dynp_vid.begin(), T.dynp_vid.end());
     CHECK((int)T.vslot.size() == Vpad && T.n_uniq == (int)uniq.size());

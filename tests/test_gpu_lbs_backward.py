@@ -14,6 +14,8 @@ which asks more of them than leaving them out would.
 
 Observed on MI355X (the session summary prints every comparison next to its bound): the nine together <= 3.5e-7 (yardstick of
 the same run 1.8e-7 .. 4.7e-7), per block <= 2.2e-6 (yardstick 1.5e-7 .. 4.5e-6), every block at 0.1 .. 1.4 x its own yardstick.
+On helpers.dense_weights_model (the "dense-weights" case): the nine together <= 2.8e-7 (yardstick 2.5e-7 .. 5.9e-7), per block
+<= 2.1e-6 (yardstick 1.9e-7 .. 3.1e-6), every block at 0.1 .. 2.1 x its own yardstick.
 """
 
 import numpy as np
@@ -88,10 +90,14 @@ def _cat(g):
 _REF = {}
 
 
-def reference(model, kind, use_pca):
-    """Inputs, upstream gradients, fp64 reference gradients and the fp32 yardstick of one configuration (computed once)."""
-    key = (kind, use_pca)
+def reference(model, kind, use_pca, weights="base"):
+    """Inputs, upstream gradients, fp64 reference gradients and the fp32 yardstick of one configuration (computed once).
+    weights: "base", the model as given, or "dense", helpers.dense_weights_model of it."""
+    key = (kind, use_pca, weights)
     if key not in _REF:
+        if weights != "base":
+            assert weights == "dense"
+            model = H.dense_weights_model(model)
         cfg = _cfg(kind)
         npca = cfg["num_pca_comps"] if use_pca else 45
         P, rng = _inputs(3, 5, npca)
@@ -106,7 +112,7 @@ def reference(model, kind, use_pca):
             y = {n: _rel(g32[c][n], g64[c][n]) for n in NAMES}
             y["whole"] = _rel(_cat(g32[c]), _cat(g64[c]))
             yard[c] = y
-        _REF[key] = dict(cfg=cfg, P=P, dv=dv, dj=dj, g64=g64, yard=yard, K=K, V=V)
+        _REF[key] = dict(cfg=cfg, P=P, dv=dv, dj=dj, g64=g64, yard=yard, K=K, V=V, model=model)
     return _REF[key]
 
 
@@ -121,12 +127,18 @@ def _device_grads(dm, P, dv, dj, gpu):
     return g
 
 
-@pytest.mark.parametrize("kind,use_pca", [("full", True), ("body", True), ("full", False)])
-def test_backward_matches_fp64_autograd_of_the_oracle(gpu, synth_model, kind, use_pca):
-    R = reference(synth_model, kind, use_pca)
-    dm = _dm(synth_model, R["cfg"], use_pca)
+# (the base model's cases keep the ids they had before the model became a parameter)
+@pytest.mark.parametrize("kind,use_pca,weights", [
+    pytest.param("full", True, "base", id="full-True"), pytest.param("body", True, "base", id="body-True"),
+    pytest.param("full", False, "base", id="full-False"), pytest.param("full", True, "dense", id="full-True-dense-weights")])
+def test_backward_matches_fp64_autograd_of_the_oracle(gpu, synth_model, kind, use_pca, weights):
+    """weights = "dense": helpers.dense_weights_model -- 5 437 vertices with more than SFX_NW weights (k_adj_prep's full-row
+    branch, wj[0] == -1), per-joint vertex lists of 2 433 .. 5 019 entries in k_adj_finish's d A (the base model's: 59 .. 3 443),
+    keypoint vertices with 12."""
+    R = reference(synth_model, kind, use_pca, weights)
+    dm = _dm(R["model"], R["cfg"], use_pca)
     assert dm.K == R["K"] and dm.V == R["V"]
-    label = "lbs-backward %s%s" % (kind, "" if use_pca else " no-pca")
+    label = "lbs-backward %s%s%s" % (kind, "" if use_pca else " no-pca", "" if weights == "base" else " dense-weights")
     for case in CASES:
         g = _device_grads(dm, R["P"], R["dv"] if case != "joints" else None, R["dj"] if case != "vertices" else None, gpu)
         g = {n: g[n].cpu().numpy() for n in NAMES}

@@ -190,16 +190,26 @@ def near_points(frames, B, nemb=None, seed=23):
     return P, est
 
 
-def closure_probe(model, cfg, mode, label, B=3, seed=11, stages=None, vposer=None, check=True):
+def closure_probe(model, cfg, mode, label, B=3, seed=11, stages=None, vposer=None, check=True, model_tag="base", frames=None,
+                  points="far", adjust=None):
     """HIP closure (through the C ABI) against fp64 autograd of the oracle at B seeded random points of B synthetic
     frames, camera stage + body stages.  Returns {stage: (max loss rel err, max gradient rel err)}; with check=True every
     comparison also goes through helpers.check_closure (loss 4e-6, whole-vector gradient 6e-6 relative) and every parameter
     block of the gradient through helpers.check_closure_blocks (max(6e-6, 10 x the float32 oracle's own error in that block);
-    the dead body_pose exactly zero).  Used by the tests below, __graft_entry__.smoke() and bench.py's closure_parity object."""
+    the dead body_pose exactly zero).  Used by the tests below, __graft_entry__.smoke() and bench.py's closure_parity object.
+    model_tag names the model in the oracle cache's key (the cache refuses a key that comes back with another model);
+    frames: the keypoint frames when they are not the model's own synthetic set; adjust(P, est): moves the far points in
+    place before they are used, `points` then names the moved set in the cache's key."""
+    assert (adjust is None) == (points == "far"), "a moved point set needs a name of its own"
     dm = _dm(model, cfg, **({"vposer": vposer} if vposer is not None else {}))
-    frames = synth_frames(model, cfg, B)
+    if frames is None:
+        frames = synth_frames(model, cfg, B)
     fb = H.engine_batch_from_frames(dm, cfg, frames, range(B), lbs_mode=mode)
     P, est = far_points(frames, B, seed, nemb=fb.nemb if vposer is not None else None)
+    if adjust is not None:
+        adjust(P, est)
+    # (the base model's key is the one test_gpu_closure_blocks.point_set forms: the two share one oracle evaluation)
+    key = (_cfg_key(cfg), points, B, seed) + (() if model_tag == "base" else (model_tag,))
     fb.set_frames(frames["keypoints"], _jw(cfg, frames), _cmask(cfg, frames), frames["focal"],
                   np.tile([frames["W"] * 0.5, frames["H"] * 0.5], (B, 1)), 1000.0 / frames["H"], est_tz=est)
     if vposer is not None:
@@ -214,7 +224,7 @@ def closure_probe(model, cfg, mode, label, B=3, seed=11, stages=None, vposer=Non
         ref = []
         for i in range(B):
             if check:
-                lo, go, go32, blocks = _oracle_closure_blocks(model, cfg, frames, i, P, stage, key=(_cfg_key(cfg), "far", B, seed))
+                lo, go, go32, blocks = _oracle_closure_blocks(model, cfg, frames, i, P, stage, key=key)
                 ref.append((go, go32))
             else:
                 lo, go = _oracle_closure(model, cfg, frames, i, P, stage)

@@ -383,6 +383,20 @@ def test_interpenetration_at_the_cfg_values(synth_model):
 
 
 def test_dense_skinning_adjoint_matches_torch_reference(synth_model):
+    _dense_skinning_adjoint(synth_model, False)
+
+
+def test_dense_skinning_adjoint_matches_torch_reference_dense_weights(synth_model):
+    """The same on helpers.dense_weights_model (the first test keeps the name it had, and so has no parameter): the vertices
+    with more than SFX_NW weights take the full-row branch of collide_eval.h's adjoint (wj[0] == -1) and k_adj_finish walks
+    per-joint vertex lists several times the base model's.  No partner is dropped and no grid cell overflows at this pose,
+    and at least 1000 vertices with more than 8 weights carry a gradient (observed on MI355X: 129 488 .. 183 118 ordered pairs
+    per frame, 6 060 .. 6 528 vertices with a gradient, 3 181 .. 3 437 of them with more than 8 weights)."""
+    import helpers as H
+    _dense_skinning_adjoint(H.dense_weights_model(synth_model), True)
+
+
+def _dense_skinning_adjoint(synth_model, dense):
     """The adjoint of the dense skinning in isolation (d v_posed = T^T g written by k_pen_gather -> fp32-MFMA split-K GEMM
     k_lbs_dense_adj -> k_adj_finish: partial sums and d A): from the evaluation's own vertex gradient g, skinning transforms A,
     v_posed and the model constants, a plain torch fp64 restatement of
@@ -414,6 +428,13 @@ def test_dense_skinning_adjoint_matches_torch_reference(synth_model):
     dA = fb.debug_read("pen_dA").reshape(B, 55, 3, 4)
     assert np.abs(g).max() > 0
     W = np.asarray(synth_model["weights"], np.float64)                         # [V][55]
+    st = fb.penetration_stats()
+    many = ((W != 0).sum(1) > 8)[None] & np.any(g != 0, axis=2)
+    print("pairs %s dropped %s entry_overflow %s; vertices with a gradient %s, of them with more than 8 weights %s" %
+          (st["pairs"], st["dropped"], st["entry_overflow"], np.any(g != 0, axis=2).sum(1), many.sum(1)))
+    if dense:
+        assert np.all(st["dropped"] == 0) and np.all(st["entry_overflow"] == 0), st
+        assert many.any(0).sum() >= 1000, many.sum(1)
     V = W.shape[0]
     nb, ne = cfg["num_betas"], cfg["num_expression_coeffs"]
     sd = np.asarray(synth_model["shapedirs"], np.float64)

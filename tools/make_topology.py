@@ -24,6 +24,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_ROOT = os.environ.get("SFX_REFERENCE_ROOT", "/root/reference")
 OUT = os.path.join(ROOT, "tests", "golden", "smplx_topology.npz")
+SPARE = os.path.join(ROOT, "oracle", "_ref", "smplx_topology.npz")     # second copy, git-ignored like the first (synthetic._topology_path)
 
 
 def read_ply_mesh(path):
@@ -52,6 +53,7 @@ def build(force=False, out=OUT):
     """Write the fixture; returns its path, or None when the reference tree is not there.  Deterministic: the same bytes of
     array data every time (test_topology_model.py checks the arrays' shapes and invariants)."""
     if os.path.exists(out) and not force:
+        _spare_copy(out)
         return out
     if not available():
         return None
@@ -72,7 +74,17 @@ def build(force=False, out=OUT):
     os.makedirs(os.path.dirname(out), exist_ok=True)
     np.savez_compressed(out, faces=faces.astype(np.int32), segm=segm.astype(np.int8), parents=parents.astype(np.int8),
                         vertices=verts, joints=joints)
+    _spare_copy(out)
     return out
+
+
+def _spare_copy(out):
+    """Keep SPARE equal to the fixture at its default place (a caller's own `out` has no spare)."""
+    if os.path.abspath(out) != OUT:
+        return
+    import shutil
+    os.makedirs(os.path.dirname(SPARE), exist_ok=True)
+    shutil.copyfile(out, SPARE)
 
 
 if __name__ == "__main__":
