@@ -4,6 +4,7 @@
 // device->host poll every POLL ticks.
 #include "../../include/sfx.h"
 #include "sfx_internal.h"
+#include "column_pool.h"
 #include "model_tables.h"
 #include "vposer_pack.h"
 
@@ -161,7 +162,7 @@ struct sfx_model {
 #ifndef SFX_OV_SERIAL
 #define SFX_OV_SERIAL 160    // rounds at this many active GEMM columns or fewer stay serial on one stream
 #endif
-// the self-served form of a round (run_ticks; models that export at most SFX_OV_SELF_UNIQ vertices, no interpenetration term):
+// the self-served form of a round (DenseLoop::round_self; models that export at most SFX_OV_SELF_UNIQ vertices, no interpenetration term):
 // rounds at more than SFX_OV_SELF_SERIAL and at most SFX_OV_SELF_MAX active columns; outside that band the rules above hold.
 // The band is where the form won the sweep of LAB_NOTES 4.9 (frames/s with the form from n + 1 columns up to 160: n = 0: 620.1,
 // 16: 631.6, 32: 635.7, 64: 637.3, 96: 628.5, 128: 616.2, 160 = the key / rest rule alone: 611.8; up to 192 instead of 160:
@@ -186,13 +187,12 @@ struct sfx_batch {
     int* act_new_dev = nullptr;   // [B] frames admitted at the latest poll (export-only launch)
     int slots = 0;                // GEMM columns of the fused dense loop (0: one per frame)
     hipEvent_t poll_ev[SFX_POLL_BUFS] = {};
-    // the overlapped dense loop (run_ticks): the second and third set of GEMM operand buffers (owned by mem; D.featR / D.AT
+    // the overlapped dense loop (DenseLoop): the second and third set of GEMM operand buffers (owned by mem; D.featR / D.AT
     // name the set of the most recent evaluation, whichever that is), the stream of the rest-tile GEMMs and the two rings of events that
     // order them against the tick kernels; stream and events are made by the first fit that overlaps
     float *featR_o[2] = {nullptr, nullptr}, *AT_o[2] = {nullptr, nullptr};      // [0] the next export's target, [1] the one after
     hipStream_t s2 = nullptr;
     hipEvent_t ov_ev[2][SFX_OV_EVENTS] = {};
-    std::vector<int> slot_host;
     int K = 0;
     sfx_pen* pen = nullptr;       // interpenetration operator (cfg.interpenetration)
     float pen_sigma = 0.f; int pen_outside = 1;
@@ -216,7 +216,7 @@ struct sfx_batch {
     ~sfx_batch() {
         for (auto& kv : pen_graphs) hipGraphExecDestroy(kv.second);
         if (cap_stream) hipStreamDestroy(cap_stream);
-        if (s2) { (void)hipStreamSynchronize(s2); hipStreamDestroy(s2); }      // (run_ticks drains it on every way out: nothing is pending)
+        if (s2) { (void)hipStreamSynchronize(s2); hipStreamDestroy(s2); }      // (DenseLoop::run drains it on every way out: nothing is pending)
         for (auto& ring : ov_ev) for (hipEvent_t e : ring) if (e) hipEventDestroy(e);
         if (pen) {             // the collision buffers go back to the model's idle slot (see sfx_model)
             (void)hipDeviceSynchronize();
@@ -1034,309 +1034,286 @@ extern "C" int sfx_batch_guess_init(sfx_batch* b, const int32_t* pairs, int32_t 
     return 0;
 }
 
-// tick loop shared by sfx_batch_fit (whole run_fitting) and sfx_batch_step (one LBFGS.step)
-static int run_ticks(sfx_batch* b, int first_stage, int last_stage, int init, int step_mode, hipStream_t s) {
-    BatchDev& D = b->D; const DevModel& M = b->m->M;
-    const int B = D.cfg.B;
-    const bool dense = D.cfg.lbs_mode == 1;
-    const bool fused = !step_mode && !g_unfused;
-    D.act = nullptr; D.nrun = 0;          // (a previous fit that ended on an error may have left its running list attached)
-    if (init == 1 && D.pen_flag) SFX_CHECK(hipMemsetAsync(D.pen_flag, 0, (size_t)B * sizeof(int), s));
-    launch_lbfgs_tick(M, D, b->vl_dev, first_stage, last_stage, init, step_mode, s);
-    // bound on the rounds of the polled loops: one resident batch needs at most stages x maxiters LBFGS.step calls of
-    // <= ~160 evaluations each; a job of B frames through a pool of `slots` columns needs that once per wave of the queue
-    long max_ticks = sfx_fit_tick_bound(D.cfg, first_stage, last_stage);
-    if (dense && b->slots > 0 && b->slots < B) max_ticks *= (B + b->slots - 1) / b->slots;
-    std::vector<int> hs(B);
-    int* hp = b->stage_host ? b->stage_host : hs.data();
-    long tick = 0;
-    bool done = false;
-    if (fused && dense && !(b->stage_host && b->map_host)) { ProfScope p("tick", s, B); launch_tick_dense(M, D, b->vl_dev, b->sw_dev, first_stage, last_stage, 0, s); }
-    if (fused && dense && b->stage_host && b->map_host) {
-        // dense fused loop, polled one batch of rounds AHEAD: while the host waits for the stage flags
-        // copied after rounds 8i .. 8i+7, rounds 8i+8 .. 8i+15 are already queued, so the GPU never idles
-        // on the host round trip.  A decision (all done / admission / compaction) therefore lags by 8 rounds:
-        // finished frames only ever stay finished, so that is safe; the surplus rounds at the end find nothing to do.
-        //
-        // Column pool (continuous batching, cfg.slots): `pool` GEMM columns; frames beyond the first `pool` wait in
-        // a queue (slot = -1, not in the running list) and take over the column of a frame that has finished -- their
-        // first pose / chain export is one extra launch over the admitted frames only.  Once the queue is dry the
-        // columns are compacted whenever a 32-frame MFMA slice has emptied, as before.  Frames are independent and a
-        // column's arithmetic does not depend on its index: results equal those of a batch with one column per frame.
-#ifdef SFX_LAB       // measurement switches of the lab build (include/sfx_lab.h): diagnostics to stderr, polling cadence
-        static const bool dbg_nact = getenv("SFX_DEBUG_NACT") != nullptr, dbg_host = getenv("SFX_DEBUG_HOST") != nullptr;
-        static const int rpb_env = [] { const char* e = getenv("SFX_POLL_ROUNDS"); return e ? atoi(e) : 0; }();
-        static const int ahead_env = [] { const char* e = getenv("SFX_POLL_AHEAD"); return e ? atoi(e) : 0; }();
-#else
-        constexpr bool dbg_nact = false, dbg_host = false;
-        constexpr int rpb_env = 0, ahead_env = 0;
-#endif
-        // GEMM beside tick (no interpenetration term, whose step needs every vertex before the tick).  Of the GEMM of evaluation i
-        // the tick kernel reads D.uvp only -- the blend offsets of the keypoint vertices: the key tiles, a twentieth of the mesh
-        // body-only.  Round i is therefore
-        //     stream s :  Gk(i) key tiles, reads cur | record E_K(i) | wait E_G(i-2) | T(i) reads uvp, exports evaluation i + 1 to nxt
-        //     stream s2:  wait E_K(i) | Gr(i) every other tile, reads cur | record E_G(i)
-        // over THREE sets of operand buffers: cur = D.featR / D.AT, nxt = b->featR_o[0] / AT_o[0], and the set Gr(i-1) may still
-        // be reading, b->featR_o[1] / AT_o[1]; the host rotates them after every tick launch (the kernels take BatchDev by value
-        // and know no parity).  T(i) overwrites what Gr(i-2) read, hence its wait, which never blocks in practice: with two
-        // sets T(i) had to wait for Gr(i-1) and then raced Gr(i) for the CUs -- a tick workgroup needs 300 to 512 registers per
-        // SIMD free and starves behind the GEMM's small workgroups (measured: 99 instead of 46 us per tick launch at 256
-        // frames, no gain).  With three, T(i) is queued while Gr(i-1) drains and takes the CUs as they empty; Gr(i) fills what
-        // is left.  Gr(i) waits for Gk(i), not only for T(i-1): beside Gk it would slow the round's critical path.
-        // A finished frame's workgroup copies its column of cur to nxt for as long as it is listed (fused.hip).  Admission and compaction
-        // exports write cur IN PLACE once s has waited for the latest Gr -- the columns of the frames that keep running hold
-        // their pending evaluation in cur only.  Two records and two waits per round; no other cross-stream traffic.
-        // Rule kept (LAB_NOTES "GEMM beside tick"): rounds at <= ov_serial active columns stay serial on s -- a short rest GEMM
-        // saves less than it costs the tick kernel it runs beside (frames/s by threshold: 32: 581, 96: 597, 160: 605, 192: 603;
-        // serial loop 563) -- and so do rounds at more than SFX_OV_MAX columns (1 024 frames through the
-        // 512-column pool lost 6 % overlapped: two tick workgroups per CU and a GEMM that fills the chip leave nothing to
-        // share); the eight-wavefront tick kernel at every size (the four-wavefront one shares
-        // its CU with GEMM workgroups and then takes 101 instead of 58 us per launch).
-        // Self-served form (models that export at most SFX_OV_SELF_UNIQ vertices: body-only keypoints).  There the tick workgroup
-        // forms the blend offsets of its keypoint vertices itself, from its column of cur with the GEMM's own chain of operations
-        // (closure_body.h self_blend_offsets: has_eval = 2), so the tick of evaluation i waits for no GEMM launch at all and the WHOLE
-        // GEMM of every evaluation runs beside the tick chain:
-        //     stream s :  wait E_G(i-2) | T(i) reads cur, exports evaluation i + 1 to nxt | record E_T(i)
-        //     stream s2:  wait E_T(i-1) | G(i) all tiles, reads cur | record E_G(i)
-        // Same three operand sets, same rotation, same joins; every evaluation still gets exactly one whole-mesh GEMM (it goes on
-        // writing D.uvp, which nobody reads in these rounds).  The first such round after anything else on s records its own E_T at
-        // its start; between the two overlapped forms the loop joins, because Gk(i) on s and G(i-1) on s2 both write the key tiles
-        // of D.verts.  The band of column counts it is used in: SFX_OV_SELF_SERIAL / SFX_OV_SELF_MAX (LAB_NOTES 4.9).
+// Measurement switches of the lab build (include/sfx_lab.h), read once by the first dense fit: diagnostics to stderr, polling
+// cadence, the form of a dense round.  The product build has the defaults as constants.
+struct DenseSwitches {
+    bool dbg_nact = false, dbg_host = false;
+    int rpb = 0, ahead = 0;                                                 // 0: the loop's own 8 rounds per batch, 3 / 1 batches ahead
+    bool ov_on = true, self_on = true, self_in_serial = false;
+    int ov_serial = SFX_OV_SERIAL, self_serial = SFX_OV_SELF_SERIAL, self_max = SFX_OV_SELF_MAX;
+};
+static const DenseSwitches& dense_switches() {
 #ifdef SFX_LAB
-        static const bool ov_on = [] { const char* e = getenv("SFX_DENSE_OVERLAP"); return !(e && *e && atoi(e) == 0); }();
-        static const bool ov_serial_set = [] { const char* e = getenv("SFX_OVERLAP_SERIAL"); return e && *e; }();
-        static const int ov_serial = [] { const char* e = getenv("SFX_OVERLAP_SERIAL"); return e && *e ? atoi(e) : SFX_OV_SERIAL; }();
-        static const bool self_on = [] { const char* e = getenv("SFX_DENSE_SELF"); return !(e && *e && atoi(e) == 0); }();
-        static const int self_serial = ov_serial_set ? ov_serial : SFX_OV_SELF_SERIAL;       // (SFX_OVERLAP_SERIAL: whichever form is selected)
-        static const int self_max = [] { const char* e = getenv("SFX_DENSE_SELF_MAX"); return e && *e ? atoi(e) : SFX_OV_SELF_MAX; }();
-        static const bool self_in_serial = [] { const char* e = getenv("SFX_DENSE_SELF_SERIAL"); return e && *e && atoi(e) != 0; }();
+    static const DenseSwitches w = [] {
+        const auto num = [](const char* name, int unset) { const char* e = getenv(name); return e && *e ? atoi(e) : unset; };
+        DenseSwitches v;
+        v.dbg_nact = getenv("SFX_DEBUG_NACT") != nullptr; v.dbg_host = getenv("SFX_DEBUG_HOST") != nullptr;
+        v.rpb = num("SFX_POLL_ROUNDS", 0); v.ahead = num("SFX_POLL_AHEAD", 0);
+        v.ov_on = num("SFX_DENSE_OVERLAP", 1) != 0; v.self_on = num("SFX_DENSE_SELF", 1) != 0; v.self_in_serial = num("SFX_DENSE_SELF_SERIAL", 0) != 0;
+        v.ov_serial = num("SFX_OVERLAP_SERIAL", SFX_OV_SERIAL); v.self_max = num("SFX_DENSE_SELF_MAX", SFX_OV_SELF_MAX);
+        v.self_serial = num("SFX_OVERLAP_SERIAL", SFX_OV_SELF_SERIAL);      // (SFX_OVERLAP_SERIAL: whichever form is selected)
+        return v;
+    }();
 #else
-        constexpr bool ov_on = true, self_on = true, self_in_serial = false;
-        constexpr int ov_serial = SFX_OV_SERIAL, self_serial = SFX_OV_SELF_SERIAL, self_max = SFX_OV_SELF_MAX;
+    static constexpr DenseSwitches w{};
 #endif
-        const bool overlap = ov_on && !b->pen && b->featR_o[0] && b->featR_o[1] && b->AT_o[0] && b->AT_o[1];
+    return w;
+}
+
+namespace {
+// Dense fused loop, polled one batch of rounds AHEAD: while the host waits for the stage flags copied after rounds 8i .. 8i+7,
+// rounds 8i+8 .. 8i+15 are already queued, so the GPU never idles on the host round trip.  A decision (all done / admission /
+// compaction) therefore lags by 8 rounds: finished frames only ever stay finished, so that is safe; the surplus rounds at the
+// end find nothing to do.  Frames beyond cfg.slots columns queue for the column of a frame that finishes (column_pool.h).
+//
+// A round is one GEMM and one tick launch, in one of three forms (round_serial, round_key_rest, round_self).  The two overlapped
+// forms run over THREE sets of operand buffers: cur = D.featR / D.AT, nxt = b->featR_o[0] / AT_o[0], and the set the GEMM of the
+// round before may still be reading, b->featR_o[1] / AT_o[1]; the host rotates them after every tick launch (the kernels take
+// BatchDev by value and know no parity).  T(i) overwrites what the GEMM of round i-2 read, hence its wait, which never blocks in
+// practice: with two sets T(i) had to wait for Gr(i-1) and then raced Gr(i) for the CUs -- a tick workgroup needs 300 to 512
+// registers per SIMD free and starves behind the GEMM's small workgroups (measured: 99 instead of 46 us per tick launch at 256
+// frames, no gain).  With three, T(i) is queued while Gr(i-1) drains and takes the CUs as they empty; Gr(i) fills what is left.
+// A finished frame's workgroup copies its column of cur to nxt for as long as it is listed (fused.hip).  Admission and
+// compaction exports write cur IN PLACE once s has waited for the latest Gr -- the columns of the frames that keep running hold
+// their pending evaluation in cur only.  Two records and two waits per round; no other cross-stream traffic.
+struct DenseLoop {
+    sfx_batch* const b; const hipStream_t s; const int first_stage, last_stage;
+    BatchDev& D = b->D; const DevModel& M = b->m->M; const int B = D.cfg.B;
+    bool overlap = false, self_form = false;            // a second stream and operand sets to overlap on; the model may serve itself
+    hipEvent_t last_G = nullptr, prev_G = nullptr;     // E_G of the latest overlapped round and of the one before (NULL: s has waited for it)
+    hipEvent_t last_T = nullptr;                       // E_T of the latest self-served round (NULL: the latest round was of another form)
+    long ov_i = 0, tick = 0;                           // overlapped rounds (their slot in the event rings), rounds
+    ColumnPool pool;
+    int upl = 0, rpb = 8;                              // next upload buffer, rounds per polled batch
+    // how much of the loop's wall time the HOST spends enqueueing (its headroom against a busy box) and waiting for stage flags
+    double host_enq_s = 0.0, host_wait_s = 0.0; long host_batches = 0;
+    static inline long nact_hist[9] = {};              // rounds by active GEMM columns: <=32, <=64, ..., <=256, more (cumulative)
+    void tick_kernel(const char* name, const BatchDev& Dx, int has_eval) {
+        ProfScope p(name, s, Dx.nrun);
+        launch_tick_dense(M, Dx, b->vl_dev, b->sw_dev, first_stage, last_stage, has_eval, s);
+    }
+    int join_s2() {                                     // before s writes operands in place: every Gr has read them
+        if (last_G) SFX_CHECK(hipStreamWaitEvent(s, last_G, 0));
+        last_G = prev_G = nullptr;
+        return 0;
+    }
+    int upload(const std::vector<int>* fresh) {         // slot[], running list (+ admitted list) through pinned memory
+        const std::vector<int>& run = pool.run;
+        int* h = b->map_host + (size_t)upl * 3 * B; upl = (upl + 1) % SFX_POLL_BUFS;      // (at most one upload per processed batch, at most `ahead` + 1 batches in flight)
+        memcpy(h, pool.col.data(), (size_t)B * sizeof(int));
+        memcpy(h + B, run.data(), run.size() * sizeof(int));
+        SFX_CHECK(hipMemcpyAsync(D.slot, h, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
+        if (!run.empty()) SFX_CHECK(hipMemcpyAsync(b->act_dev, h + B, run.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        if (fresh && !fresh->empty()) {
+            memcpy(h + 2 * B, fresh->data(), fresh->size() * sizeof(int));
+            SFX_CHECK(hipMemcpyAsync(b->act_new_dev, h + 2 * B, fresh->size() * sizeof(int), hipMemcpyHostToDevice, s));
+        }
+        D.act = b->act_dev; D.nrun = (int)run.size();
+        return 0;
+    }
+    // the tail of both overlapped forms: s waits for E_G(i-2), T(i) exports evaluation i + 1 to nxt, the operand sets rotate
+    int tick_beside(hipEvent_t e_G, int has_eval) {
+        if (prev_G) SFX_CHECK(hipStreamWaitEvent(s, prev_G, 0));
+        prev_G = last_G; last_G = e_G;
+        BatchDev Dt = D; Dt.featR_w = b->featR_o[0]; Dt.AT_w = b->AT_o[0];
+        tick_kernel("tick", Dt, has_eval);
+        float* const f = D.featR; D.featR = b->featR_o[0]; b->featR_o[0] = b->featR_o[1]; b->featR_o[1] = f;
+        float* const a = D.AT; D.AT = b->AT_o[0]; b->AT_o[0] = b->AT_o[1]; b->AT_o[1] = a;
+        D.featR_w = D.featR; D.AT_w = D.AT;
+        return 0;
+    }
+    // Self-served form (models that export at most SFX_OV_SELF_UNIQ vertices: body-only keypoints).  The tick workgroup forms the
+    // blend offsets of its keypoint vertices itself, from its column of cur with the GEMM's own chain of operations
+    // (closure_body.h self_blend_offsets: has_eval = 2), so the tick of evaluation i waits for no GEMM launch at all and the WHOLE
+    // GEMM of every evaluation runs beside the tick chain:
+    //     stream s :  wait E_G(i-2) | T(i) reads cur, exports evaluation i + 1 to nxt | record E_T(i)
+    //     stream s2:  wait E_T(i-1) | G(i) all tiles, reads cur | record E_G(i)
+    // Every evaluation still gets exactly one whole-mesh GEMM (it goes on writing D.uvp, which nobody reads in these rounds).
+    // The first such round after anything else on s records its own E_T at its start.  E_T lives in ring 0, whose events the
+    // key / rest form records and waits for at once: a wait holds the record it was enqueued behind, so slot k + 1 of this
+    // round is free again when round i + 4 records it.
+    int round_self() {
+        const int k = (int)(ov_i++ % SFX_OV_EVENTS);
+        if (!last_G || !last_T) { SFX_CHECK(hipEventRecord(b->ov_ev[0][k], s)); last_T = b->ov_ev[0][k]; }
+        SFX_CHECK(hipStreamWaitEvent(b->s2, last_T, 0));
+        { ProfScope p("lbs_dense", b->s2, D.nact); launch_lbs_dense(M, D, b->s2); }
+        SFX_CHECK(hipEventRecord(b->ov_ev[1][k], b->s2));
+        if (int rc = tick_beside(b->ov_ev[1][k], 2)) return rc;
+        last_T = b->ov_ev[0][(k + 1) % SFX_OV_EVENTS];
+        SFX_CHECK(hipEventRecord(last_T, s));
+        return 0;
+    }
+    // GEMM beside tick.  Of the GEMM of evaluation i the tick kernel reads D.uvp only -- the blend offsets of the keypoint
+    // vertices: the key tiles, a twentieth of the mesh body-only:
+    //     stream s :  Gk(i) key tiles, reads cur | record E_K(i) | wait E_G(i-2) | T(i) reads uvp, exports evaluation i + 1 to nxt
+    //     stream s2:  wait E_K(i) | Gr(i) every other tile, reads cur | record E_G(i)
+    // Gr(i) waits for Gk(i), not only for T(i-1): beside Gk it would slow the round's critical path.  After a self-served round
+    // the loop joins first: Gk(i) on s and G(i-1) on s2 both write the key tiles of D.verts.
+    int round_key_rest() {
+        if (last_T) { if (int rc = join_s2()) return rc; last_T = nullptr; }
+        const int k = (int)(ov_i++ % SFX_OV_EVENTS);
+        if (b->m->n_key) { ProfScope p("lbs_dense_key", s, D.nact); launch_lbs_dense_list(M, D, b->m->tile_key, b->m->n_key, s); }
+        SFX_CHECK(hipEventRecord(b->ov_ev[0][k], s));
+        SFX_CHECK(hipStreamWaitEvent(b->s2, b->ov_ev[0][k], 0));
+        { ProfScope p("lbs_dense", b->s2, D.nact); launch_lbs_dense_list(M, D, b->m->tile_rest, b->m->n_rest, b->s2); }
+        SFX_CHECK(hipEventRecord(b->ov_ev[1][k], b->s2));
+        return tick_beside(b->ov_ev[1][k], 1);
+    }
+    // Everything on s: whole-grid GEMM, the interpenetration step (which needs every vertex before the tick), tick.
+    int round_serial() {
+        if (int rc = join_s2()) return rc;
+        last_T = nullptr;
+        { ProfScope p("lbs_dense", s, D.nact); launch_lbs_dense(M, D, s); }
+        if (int rc = eval_penetration(b, -2, s, true)) return rc;
+        tick_kernel("tick", D, (dense_switches().self_in_serial && !b->pen && M.n_uniq <= SFX_OV_SELF_UNIQ) ? 2 : 1);
+        return 0;
+    }
+    // One polled batch: rpb rounds, each in the form its count of active columns selects, then the stage flags to poll buffer
+    // `buf`.  Self-served at SFX_OV_SELF_SERIAL < columns <= SFX_OV_SELF_MAX: the band where the form won (LAB_NOTES 4.9).
+    // Key / rest at SFX_OV_SERIAL < columns <= SFX_OV_MAX (LAB_NOTES "GEMM beside tick"): below, a short rest GEMM saves less
+    // than it costs the tick kernel it runs beside (frames/s by threshold: 32: 581, 96: 597, 160: 605, 192: 603; serial loop
+    // 563); above, 1 024 frames through the 512-column pool lost 6 % overlapped: two tick workgroups per CU and a GEMM that fills
+    // the chip leave nothing to share.  The eight-wavefront tick kernel at every size (the four-wavefront one shares its CU with
+    // GEMM workgroups and then takes 101 instead of 58 us per launch).
+    int rounds(int buf) {
+        const DenseSwitches& sw = dense_switches();
+        if (sw.dbg_nact) nact_hist[std::min(8, (D.nact - 1) / 32)] += rpb;
+        const auto h0 = std::chrono::steady_clock::now();
+        for (int q = 0; q < rpb; ++q, ++tick) {
+            const int rc = self_form && D.nact > sw.self_serial && D.nact <= sw.self_max ? round_self()
+                         : overlap && D.nact > sw.ov_serial && D.nact <= SFX_OV_MAX      ? round_key_rest() : round_serial();
+            if (rc) return rc;
+        }
+        SFX_CHECK(hipMemcpyAsync(b->stage_host + (size_t)buf * B, D.stage, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
+        SFX_CHECK(hipEventRecord(b->poll_ev[buf], s));
+        host_enq_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - h0).count(); ++host_batches;
+        return 0;
+    }
+    // Wait for poll buffer `cur`; retire the frames that have finished, admit queued ones to their columns; once the queue is
+    // dry, compact the columns whenever a slice has emptied.
+    int poll(int cur, bool& done) {
+        const auto w0 = std::chrono::steady_clock::now();
+        SFX_CHECK(hipEventSynchronize(b->poll_ev[cur]));
+        host_wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
+        std::vector<int> fresh;
+        const bool changed = pool.retire(b->stage_host + (size_t)cur * B, last_stage, fresh);
+        done = pool.run.empty();
+        if (done || !changed) return 0;
+        if (!fresh.empty()) {
+            // admission: the new frames inherit the freed columns; only they need an export pass (one extra launch)
+            if (int rc = join_s2()) return rc;
+            if (int rc = upload(&fresh)) return rc;
+            BatchDev Dn = D; Dn.act = b->act_new_dev; Dn.nrun = (int)fresh.size();
+            tick_kernel("tick_admit", Dn, 0);
+        } else if (ColumnPool::slice_emptied(D.nact, (int)pool.run.size())) {
+            // The pending evaluation of every running frame lives in column slot[f] of featR / AT, so re-export after
+            // remapping (queued behind the rounds already in flight, which still use the old mapping consistently).
+            D.nact = pool.compact();
+            if (int rc = join_s2()) return rc;
+            if (int rc = upload(nullptr)) return rc;
+            tick_kernel("tick", D, 0);
+        } else if (int rc = upload(nullptr)) return rc;      // shorter running list: fewer workgroups per tick launch
+        return 0;
+    }
+    int run(long max_ticks, bool& done) {
+        const DenseSwitches& sw = dense_switches();
+        overlap = sw.ov_on && !b->pen && b->featR_o[0] && b->featR_o[1] && b->AT_o[0] && b->AT_o[1];
         if (overlap && !b->s2) {
             int lo = 0, hi = 0;
             SFX_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));         // (lowest priority: the key tiles and the tick are the round's critical path)
             SFX_CHECK(hipStreamCreateWithPriority(&b->s2, hipStreamNonBlocking, lo));
             for (auto& ring : b->ov_ev) for (hipEvent_t& e : ring) SFX_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         }
-        // every way out of this block leaves both streams drained and the export pointed back at D.featR / D.AT
-        struct OvDrain { sfx_batch* b; hipStream_t s;
-                         ~OvDrain() { if (b->s2) (void)hipStreamSynchronize(b->s2); (void)hipStreamSynchronize(s); b->D.featR_w = b->D.featR; b->D.AT_w = b->D.AT; } } ov_drain{b, s};
-        hipEvent_t last_G = nullptr, prev_G = nullptr;     // E_G of the latest overlapped round and of the one before (NULL: s has waited for it)
-        hipEvent_t last_T = nullptr;                       // E_T of the latest self-served round (NULL: the latest round was of another form)
-        const bool self_form = overlap && self_on && M.n_uniq <= SFX_OV_SELF_UNIQ;
-        long ov_i = 0;
-        auto join_s2 = [&]() -> int {                       // before s writes operands in place: every Gr has read them
-            if (last_G) SFX_CHECK(hipStreamWaitEvent(s, last_G, 0));
-            last_G = prev_G = nullptr;
-            return 0;
-        };
-        static long nact_hist[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};      // rounds by active GEMM columns: <=32, <=64, ..., <=256, more
-        const int pool = b->slots > 0 ? std::min(b->slots, B) : B;
-        std::vector<int>& col = b->slot_host;                          // frame -> column, -1 = queued or retired
-        col.assign(B, -1);
-        std::vector<int> run;                                          // running frames, ascending admission order
-        run.reserve(B);
-        for (int i = 0; i < pool; ++i) { col[i] = i; run.push_back(i); }
-        int next_q = pool, upl = 0;
-        auto upload = [&](const std::vector<int>* fresh) -> int {      // slot[], running list (+ admitted list) through pinned memory
-            int* h = b->map_host + (size_t)upl * 3 * B; upl = (upl + 1) % SFX_POLL_BUFS;      // (at most one upload per processed batch, at most `ahead` + 1 batches in flight)
-            memcpy(h, col.data(), (size_t)B * sizeof(int));
-            memcpy(h + B, run.data(), run.size() * sizeof(int));
-            SFX_CHECK(hipMemcpyAsync(D.slot, h, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
-            if (!run.empty()) SFX_CHECK(hipMemcpyAsync(b->act_dev, h + B, run.size() * sizeof(int), hipMemcpyHostToDevice, s));
-            if (fresh && !fresh->empty()) {
-                memcpy(h + 2 * B, fresh->data(), fresh->size() * sizeof(int));
-                SFX_CHECK(hipMemcpyAsync(b->act_new_dev, h + 2 * B, fresh->size() * sizeof(int), hipMemcpyHostToDevice, s));
+        self_form = overlap && sw.self_on && M.n_uniq <= SFX_OV_SELF_UNIQ;
+        {
+            // every way out of this block leaves both streams drained and the export pointed back at D.featR / D.AT
+            struct OvDrain { sfx_batch* b; hipStream_t s;
+                             ~OvDrain() { if (b->s2) (void)hipStreamSynchronize(b->s2); (void)hipStreamSynchronize(s); b->D.featR_w = b->D.featR; b->D.AT_w = b->D.AT; } } ov_drain{b, s};
+            const int ncol = b->slots > 0 ? std::min(b->slots, B) : B;
+            pool.reset(B, ncol);
+            D.nact = ncol;
+            if (int rc = upload(nullptr)) return rc;
+            tick_kernel("tick", D, 0);
+            const double wall0 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+            rpb = std::max(1, std::min(64, sw.rpb > 0 ? sw.rpb : 8));
+            const int ahead = std::max(1, std::min(SFX_POLL_BUFS - 1, sw.ahead > 0 ? sw.ahead : (b->pen ? 1 : 3)));
+            long q_head = 0, q_next = 0;       // batches processed / queued
+            for (; q_next < ahead; ++q_next) if (int rc = rounds((int)(q_next % SFX_POLL_BUFS))) return rc;
+            while (!done && tick < max_ticks + (long)rpb * (ahead + 1)) {
+                if (int rc = rounds((int)(q_next++ % SFX_POLL_BUFS))) return rc;
+                if (int rc = poll((int)(q_head++ % SFX_POLL_BUFS), done)) return rc;
             }
-            D.act = b->act_dev; D.nrun = (int)run.size();
-            return 0;
-        };
-        D.nact = pool;
-        if (int rc = upload(nullptr)) return rc;
-        { ProfScope p("tick", s, D.nrun); launch_tick_dense(M, D, b->vl_dev, b->sw_dev, first_stage, last_stage, 0, s); }
-        // SFX_DEBUG_HOST=1: how much of the loop's wall time the HOST spends enqueueing (its headroom against a busy box)
-        double host_enq_s = 0.0, host_wait_s = 0.0; long host_batches = 0;
-        const double wall0 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-        const int rpb = std::max(1, std::min(64, rpb_env > 0 ? rpb_env : 8));          // rounds per polled batch
-        auto rounds = [&](int buf) -> int {
-            if (dbg_nact) nact_hist[std::min(8, (D.nact - 1) / 32)] += rpb;
-            const auto h0 = std::chrono::steady_clock::now();
-            struct HostClock { const std::chrono::steady_clock::time_point t0; double& acc; long& n; bool on;
-                               ~HostClock() { if (on) { acc += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); ++n; } } } hc{h0, host_enq_s, host_batches, true};
-            for (int q = 0; q < rpb; ++q, ++tick) {
-                if (self_form && D.nact > self_serial && D.nact <= self_max) {
-                    const int k = (int)(ov_i++ % SFX_OV_EVENTS);
-                    // (E_T lives in ring 0, whose events the key / rest form records and waits for at once: a wait holds the record
-                    //  it was enqueued behind, so slot k + 1 of this round is free again when round i + 4 records it)
-                    if (!last_G || !last_T) { SFX_CHECK(hipEventRecord(b->ov_ev[0][k], s)); last_T = b->ov_ev[0][k]; }
-                    SFX_CHECK(hipStreamWaitEvent(b->s2, last_T, 0));
-                    { ProfScope p("lbs_dense", b->s2, D.nact); launch_lbs_dense(M, D, b->s2); }
-                    SFX_CHECK(hipEventRecord(b->ov_ev[1][k], b->s2));
-                    if (prev_G) SFX_CHECK(hipStreamWaitEvent(s, prev_G, 0));
-                    prev_G = last_G; last_G = b->ov_ev[1][k];
-                    BatchDev Dt = D; Dt.featR_w = b->featR_o[0]; Dt.AT_w = b->AT_o[0];
-                    { ProfScope p("tick", s, D.nrun);
-                      launch_tick_dense(M, Dt, b->vl_dev, b->sw_dev, first_stage, last_stage, 2, s); }
-                    last_T = b->ov_ev[0][(k + 1) % SFX_OV_EVENTS];
-                    SFX_CHECK(hipEventRecord(last_T, s));
-                    float* const f = D.featR; D.featR = b->featR_o[0]; b->featR_o[0] = b->featR_o[1]; b->featR_o[1] = f;
-                    float* const a = D.AT; D.AT = b->AT_o[0]; b->AT_o[0] = b->AT_o[1]; b->AT_o[1] = a;
-                    D.featR_w = D.featR; D.AT_w = D.AT;
-                    continue;
-                }
-                if (overlap && D.nact > ov_serial && D.nact <= SFX_OV_MAX) {
-                    if (last_T) { if (int rc = join_s2()) return rc; last_T = nullptr; }      // (the latest round was self-served: its G writes the key tiles too)
-                    const int k = (int)(ov_i++ % SFX_OV_EVENTS);
-                    if (b->m->n_key) { ProfScope p("lbs_dense_key", s, D.nact); launch_lbs_dense_list(M, D, b->m->tile_key, b->m->n_key, s); }
-                    SFX_CHECK(hipEventRecord(b->ov_ev[0][k], s));
-                    SFX_CHECK(hipStreamWaitEvent(b->s2, b->ov_ev[0][k], 0));
-                    { ProfScope p("lbs_dense", b->s2, D.nact); launch_lbs_dense_list(M, D, b->m->tile_rest, b->m->n_rest, b->s2); }
-                    SFX_CHECK(hipEventRecord(b->ov_ev[1][k], b->s2));
-                    if (prev_G) SFX_CHECK(hipStreamWaitEvent(s, prev_G, 0));
-                    prev_G = last_G; last_G = b->ov_ev[1][k];
-                    BatchDev Dt = D; Dt.featR_w = b->featR_o[0]; Dt.AT_w = b->AT_o[0];
-                    { ProfScope p("tick", s, D.nrun);
-                      launch_tick_dense(M, Dt, b->vl_dev, b->sw_dev, first_stage, last_stage, 1, s); }
-                    float* const f = D.featR; D.featR = b->featR_o[0]; b->featR_o[0] = b->featR_o[1]; b->featR_o[1] = f;
-                    float* const a = D.AT; D.AT = b->AT_o[0]; b->AT_o[0] = b->AT_o[1]; b->AT_o[1] = a;
-                    D.featR_w = D.featR; D.AT_w = D.AT;
-                    continue;
-                }
-                if (int rc = join_s2()) return rc;
-                last_T = nullptr;
-                { ProfScope p("lbs_dense", s, D.nact); launch_lbs_dense(M, D, s); }
-                if (int rc = eval_penetration(b, -2, s, true)) return rc;
-                ProfScope p("tick", s, D.nrun);
-                launch_tick_dense(M, D, b->vl_dev, b->sw_dev, first_stage, last_stage, (self_in_serial && !b->pen && M.n_uniq <= SFX_OV_SELF_UNIQ) ? 2 : 1, s);
+            if (b->s2) SFX_CHECK(hipStreamSynchronize(b->s2));
+            SFX_CHECK(hipStreamSynchronize(s));
+            D.act = nullptr; D.nrun = 0;
+            const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - wall0;
+            {   // the host's side of this loop, accumulated for sfx_loop_host_stats (bench.py reports it next to the kernels' times)
+                std::lock_guard<std::mutex> lk(g_prof_mu);
+                g_loop_host[0] += host_enq_s; g_loop_host[1] += host_wait_s; g_loop_host[2] += wall; g_loop_host[3] += (double)host_batches * rpb;
             }
-            SFX_CHECK(hipMemcpyAsync(b->stage_host + (size_t)buf * B, D.stage, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
-            SFX_CHECK(hipEventRecord(b->poll_ev[buf], s));
-            return 0;
-        };
-        const int ahead = std::max(1, std::min(SFX_POLL_BUFS - 1, ahead_env > 0 ? ahead_env : (b->pen ? 1 : 3)));
-        long q_head = 0, q_next = 0;       // batches processed / queued
-        for (; q_next < ahead; ++q_next) if (int rc = rounds((int)(q_next % SFX_POLL_BUFS))) return rc;
-        while (!done && tick < max_ticks + (long)rpb * (ahead + 1)) {
-            if (int rc = rounds((int)(q_next % SFX_POLL_BUFS))) return rc;
-            ++q_next;
-            const int cur = (int)(q_head % SFX_POLL_BUFS); ++q_head;
-            {
-                const auto w0 = std::chrono::steady_clock::now();
-                SFX_CHECK(hipEventSynchronize(b->poll_ev[cur]));
-                host_wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
-            }
-            const int* hq = b->stage_host + (size_t)cur * B;
-            // frames of the running list that have finished (frames admitted after this snapshot show their start stage)
-            std::vector<int> fresh;
-            size_t w = 0;
-            bool changed = false;
-            for (size_t r = 0; r < run.size(); ++r) {
-                const int f = run[r];
-                if (hq[f] <= last_stage) { run[w++] = f; continue; }
-                changed = true;
-                const int c = col[f];
-                col[f] = -1;
-                if (next_q < B) { const int nf = next_q++; col[nf] = c; fresh.push_back(nf); }
-            }
-            run.resize(w);
-            for (int nf : fresh) run.push_back(nf);
-            done = run.empty();
-            if (!done && changed) {
-                if (!fresh.empty()) {
-                    // admission: the new frames inherit the freed columns; only they need an export pass
-                    if (int rc = join_s2()) return rc;
-                    if (int rc = upload(&fresh)) return rc;
-                    BatchDev Dn = D; Dn.act = b->act_new_dev; Dn.nrun = (int)fresh.size();
-                    ProfScope p("tick_admit", s, Dn.nrun);
-                    launch_tick_dense(M, Dn, b->vl_dev, b->sw_dev, first_stage, last_stage, 0, s);
-                } else if ((D.nact + 31) / 32 != ((int)run.size() + 31) / 32 || (D.nact > 16 && run.size() <= 16)) {      // (round 5: also down to ONE 16-frame slice -- the few-frames GEMM's floor is 17.5 us there, 23 at two slices)
-                    // queue dry and a 32-frame MFMA slice has emptied: compact.  The pending evaluation of every running
-                    // frame lives in column slot[f] of featR / AT, so re-export after remapping (queued behind the rounds
-                    // already in flight, which still use the old mapping consistently).
-                    int q = 0;
-                    for (int f : run) col[f] = q++;
-                    D.nact = q;
-                    if (int rc = join_s2()) return rc;
-                    if (int rc = upload(nullptr)) return rc;
-                    ProfScope p("tick", s, D.nrun);
-                    launch_tick_dense(M, D, b->vl_dev, b->sw_dev, first_stage, last_stage, 0, s);   // re-export only
-                } else {
-                    if (int rc = upload(nullptr)) return rc;      // shorter running list: fewer workgroups per tick launch
-                }
+            if (sw.dbg_host)
+                fprintf(stderr, "[sfx] host enqueue: %ld batches of rounds, %.1f us of host time per round, %.1f %% of the loop's %.1f ms wall time\n",
+                        host_batches, 1e6 * host_enq_s / std::max(1L, host_batches * rpb), 100.0 * host_enq_s / std::max(wall, 1e-9), 1e3 * wall);
+            if (sw.dbg_nact) {
+                fprintf(stderr, "[sfx] rounds by active columns (<=32, <=64, ..., <=256, more), cumulative:");
+                for (int i = 0; i < 9; ++i) fprintf(stderr, " %ld", nact_hist[i]);
+                fprintf(stderr, "\n");
             }
         }
-        if (b->s2) SFX_CHECK(hipStreamSynchronize(b->s2));
+        SFX_CHECK(hipGetLastError());
+        std::vector<int> id(B);         // restore the identity mapping for stand-alone calls
+        for (int i = 0; i < B; ++i) id[i] = i;
+        SFX_CHECK(hipMemcpyAsync(D.slot, id.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
         SFX_CHECK(hipStreamSynchronize(s));
-        D.act = nullptr; D.nrun = 0;
-        const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - wall0;
-        {   // the host's side of this loop, accumulated for sfx_loop_host_stats (bench.py reports it next to the kernels' times)
-            std::lock_guard<std::mutex> lk(g_prof_mu);
-            g_loop_host[0] += host_enq_s; g_loop_host[1] += host_wait_s; g_loop_host[2] += wall; g_loop_host[3] += (double)host_batches * rpb;
-        }
-        if (dbg_host) {
-            fprintf(stderr, "[sfx] host enqueue: %ld batches of rounds, %.1f us of host time per round, %.1f %% of the loop's %.1f ms wall time\n",
-                    host_batches, 1e6 * host_enq_s / std::max(1L, host_batches * rpb), 100.0 * host_enq_s / std::max(wall, 1e-9), 1e3 * wall);
-        }
-        if (dbg_nact) {
-            fprintf(stderr, "[sfx] rounds by active columns (<=32, <=64, ..., <=256, more), cumulative:");
-            for (int i = 0; i < 9; ++i) fprintf(stderr, " %ld", nact_hist[i]);
-            fprintf(stderr, "\n");
-        }
-    } else
-    while (!done && tick < max_ticks) {
-        if (fused && !dense) {
-            // persistent per-frame workgroups; the host only re-launches frames that need more ticks
-            const int chunk = 512;
-            { ProfScope p("fit_rows", s); launch_fit_rows(M, D, b->vl_dev, b->sw_dev, first_stage, last_stage, chunk, s); }
+        D.nact = B;
+        return 0;
+    }
+};
+}  // namespace
+
+// The loops that wait for every poll: the needed-rows fused path (persistent per-frame workgroups; the host only re-launches
+// frames that need more ticks) and the stand-alone kernels of sfx_batch_step / sfx_prof_enable bit 1
+static int run_synced(sfx_batch* b, int first_stage, int last_stage, int step_mode, bool fused, long max_ticks, bool& done, hipStream_t s) {
+    BatchDev& D = b->D; const DevModel& M = b->m->M;
+    const int B = D.cfg.B, chunk = 512, POLL = D.cfg.lbs_mode == 1 ? 8 : 32;
+    std::vector<int> hs(B);
+    int* hp = b->stage_host ? b->stage_host : hs.data();
+    for (long tick = 0; !done && tick < max_ticks;) {
+        if (fused) {
+            ProfScope p("fit_rows", s);
+            launch_fit_rows(M, D, b->vl_dev, b->sw_dev, first_stage, last_stage, chunk, s);
             tick += chunk;
-        } else if (fused) {
-            for (int q = 0; q < 8; ++q, ++tick) {
-                { ProfScope p("lbs_dense", s, D.nact); launch_lbs_dense(M, D, s); }
-                if (int rc = eval_penetration(b, -2, s, true)) return rc;
-                ProfScope p("tick", s);
-                launch_tick_dense(M, D, b->vl_dev, b->sw_dev, first_stage, last_stage, 1, s);
-            }
-        } else {
-            const int POLL = dense ? 8 : 32;
-            for (int q = 0; q < POLL; ++q, ++tick) {
-                if (int rc = eval_closure(b, -2, 0, s)) return rc;
-                ProfScope p("lbfgs", s);
-                launch_lbfgs_tick(M, D, b->vl_dev, first_stage, last_stage, 0, step_mode, s);
-            }
+        } else for (int q = 0; q < POLL; ++q, ++tick) {
+            if (int rc = eval_closure(b, -2, 0, s)) return rc;
+            ProfScope p("lbfgs", s);
+            launch_lbfgs_tick(M, D, b->vl_dev, first_stage, last_stage, 0, step_mode, s);
         }
         SFX_CHECK(hipMemcpyAsync(hp, D.stage, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
         SFX_CHECK(hipStreamSynchronize(s));
         done = true;
         for (int i = 0; i < B; ++i) if (hp[i] <= last_stage) { done = false; break; }
-        if (fused && dense && !done) {
-            // compaction: finished frames give up their GEMM columns.  The pending evaluation of
-            // every active frame lives in column slot[b] of featR / AT, so re-export after remapping.
-            int n = 0;
-            for (int i = 0; i < B; ++i) if (hp[i] <= last_stage) ++n;
-            if ((b->D.nact + 31) / 32 != (n + 31) / 32) {      // a 32-frame MFMA tile became free
-                std::vector<int>& sl = b->slot_host;
-                sl.assign(B, 0);
-                int q = 0;
-                for (int i = 0; i < B; ++i) sl[i] = (hp[i] <= last_stage) ? q++ : 0;
-                SFX_CHECK(hipMemcpyAsync(D.slot, sl.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
-                b->D.nact = n;
-                ProfScope p("tick", s);
-                launch_tick_dense(M, b->D, b->vl_dev, b->sw_dev, first_stage, last_stage, 0, s);   // re-export only
-            }
-        }
     }
     SFX_CHECK(hipGetLastError());
-    if (fused && dense) {       // restore the identity mapping for stand-alone calls
-        std::vector<int>& sl = b->slot_host;
-        sl.resize(B);
-        for (int i = 0; i < B; ++i) sl[i] = i;
-        SFX_CHECK(hipMemcpyAsync(D.slot, sl.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
-        SFX_CHECK(hipStreamSynchronize(s));
-        b->D.nact = B;
-    }
+    return 0;
+}
+
+// tick loop shared by sfx_batch_fit (whole run_fitting) and sfx_batch_step (one LBFGS.step): the init tick, then the loop of the
+// batch's kind -- the polled dense loop for a fused dense fit, run_synced for everything else
+static int run_ticks(sfx_batch* b, int first_stage, int last_stage, int init, int step_mode, hipStream_t s) {
+    BatchDev& D = b->D;
+    const bool dense = D.cfg.lbs_mode == 1;
+    const bool fused = !step_mode && !g_unfused;
+    D.act = nullptr; D.nrun = 0;          // (a previous fit that ended on an error may have left its running list attached)
+    if (init == 1 && D.pen_flag) SFX_CHECK(hipMemsetAsync(D.pen_flag, 0, (size_t)D.cfg.B * sizeof(int), s));
+    launch_lbfgs_tick(b->m->M, D, b->vl_dev, first_stage, last_stage, init, step_mode, s);
+    // bound on the rounds of the polled loops: one resident batch needs at most stages x maxiters LBFGS.step calls of
+    // <= ~160 evaluations each; a job of B frames through a pool of `slots` columns needs that once per wave of the queue
+    long max_ticks = sfx_fit_tick_bound(D.cfg, first_stage, last_stage);
+    if (dense && b->slots > 0 && b->slots < D.cfg.B) max_ticks *= (D.cfg.B + b->slots - 1) / b->slots;
+    bool done = false;
+    const int rc = fused && dense ? DenseLoop{b, s, first_stage, last_stage}.run(max_ticks, done)
+                                  : run_synced(b, first_stage, last_stage, step_mode, fused, max_ticks, done, s);
+    if (rc) return rc;
     if (!done) { sfx_set_error("fit did not finish within %ld ticks", max_ticks); return -4; }
     return 0;
 }
