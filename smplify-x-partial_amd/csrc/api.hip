@@ -752,7 +752,7 @@ extern "C" int sfx_debug_phase_clocks(sfx_batch* b, int32_t stage, int64_t* out 
 //   "verts" V*3, "vposed" V*3, "pen_dverts" V*3, "pen_dfeat" 512, "pen_dA" 55*12, "pen_loss" 1,
 //   "A" 12*55 (skinning transforms, [row*4+col][joint] gathered from the GEMM operand), "feat" 512,
 //   "uvp" n_uniq*3 (blend offsets of the exported vertices as the dense GEMM wrote them), "uvp_self" n_uniq*3 (the same from
-//   closure_body.h self_blend_offsets on the current "feat": one launch of k_uvp_self into a scratch buffer)
+//   closure_lds.h self_blend_offsets on the current "feat": one launch of k_uvp_self into a scratch buffer)
 extern "C" int sfx_batch_debug_read(sfx_batch* b, const char* name, float* out, int64_t n_out) {
     if (!b || !name || !out) { sfx_set_error("null argument"); return -1; }
     const BatchDev& D = b->D; const int B = D.cfg.B, V = b->m->M.V;
@@ -1124,7 +1124,7 @@ struct DenseLoop {
     }
     // Self-served form (models that export at most SFX_OV_SELF_UNIQ vertices: body-only keypoints).  The tick workgroup forms the
     // blend offsets of its keypoint vertices itself, from its column of cur with the GEMM's own chain of operations
-    // (closure_body.h self_blend_offsets: has_eval = 2), so the tick of evaluation i waits for no GEMM launch at all and the WHOLE
+    // (closure_lds.h self_blend_offsets: has_eval = 2), so the tick of evaluation i waits for no GEMM launch at all and the WHOLE
     // GEMM of every evaluation runs beside the tick chain:
     //     stream s :  wait E_G(i-2) | T(i) reads cur, exports evaluation i + 1 to nxt | record E_T(i)
     //     stream s2:  wait E_T(i-1) | G(i) all tiles, reads cur | record E_G(i)

@@ -16,73 +16,11 @@
 //   loss                                         : one lane per keypoint, fixed-order reduce
 //   reverse sweep                                : gathers only (no atomics) -> deterministic
 #pragma once
-#include "sfx_internal.h"
-#include "wave_ops.h"
-// contraction only inside one source expression (decided by the front end): the stand-alone
-// closure kernel and the fused fit kernels then round identically, so optimizer.step() driven from
-// the host and sfx_batch_fit walk the same trajectory bit for bit
+#include "closure_math.h"
+#include "closure_lds.h"
+// contraction only inside one source expression, as in closure_math.h (the closure and the fused fit kernels round identically)
 #pragma clang fp contract(on)
-#include "vposer.h"
 
-// Precision of the keypoint forward (rotations, rest joints, kinematic chain, keypoint skinning: fwd_t) and of the
-// projection up to the pixel residual (proj_t); see "forward precision" in closure_body.  Measured on the 64 + 64
-// reference fits of the benchmark configuration (LAB_NOTES.md §3.1; evaluations per frame / signed mean final-loss
-// difference to the reference's fp32 run; the reference: 2 362 in fp32, 4 098 and -2.1 % in fp64):
-//   fwd fp64, proj fp64 : 3 221 / -1.7 %   gradient noise 0.13 x torch fp32's: keeps working where the reference stalls
-//   fwd fp64, proj fp32 : 2 482 / -0.4 %   <- built: never noisier than the reference, closest to it in loss and in work
-//   fwd fp32, proj fp32 : 2 233 / +0.6 %   noise ~ torch's (pointer-jumping chain 1.3 x): stops a little early
-#ifdef SFX_FWD_FP32
-typedef float fwd_t;
-#else
-typedef double fwd_t;
-#endif
-#ifdef SFX_PROJ_FP64
-typedef double proj_t;
-#else
-typedef float proj_t;
-#endif
-
-// camera.py:93-117: p_cam = R p + t, pixel = f p_cam.xy / p_cam.z + c; residual gt - pixel, all in T.
-// O: the closure's working precision (float; double in the float64 mode)
-template <class T, class O>
-__device__ __forceinline__ void project_residual(const fwd_t* pj, const float* Rc, const O* ct, O fx, O fy, O cx,
-                                                 O cy, float gtx, float gty, O& pcx, O& pcy, O& pcz, O& rx,
-                                                 O& ry) {
-    const T p[3] = {(T)pj[0], (T)pj[1], (T)pj[2]};
-    const T pxd = (T)Rc[0] * p[0] + (T)Rc[1] * p[1] + (T)Rc[2] * p[2] + (T)ct[0];
-    const T pyd = (T)Rc[3] * p[0] + (T)Rc[4] * p[1] + (T)Rc[5] * p[2] + (T)ct[1];
-    const T pzd = (T)Rc[6] * p[0] + (T)Rc[7] * p[1] + (T)Rc[8] * p[2] + (T)ct[2];
-    pcx = (O)pxd; pcy = (O)pyd; pcz = (O)pzd;
-    rx = (O)((T)gtx - ((T)fx * (pxd / pzd) + (T)cx));
-    ry = (O)((T)gty - ((T)fy * (pyd / pzd) + (T)cy));
-}
-__device__ __forceinline__ void sincos_t(double a, double* s, double* c) { sincos(a, s, c); }
-__device__ __forceinline__ void sincos_t(float a, float* s, float* c) { *s = sinf(a); *c = cosf(a); }
-// the closure's math at its working precision (float: the fp32 library calls of the fp32 closure, unchanged)
-__device__ __forceinline__ float r_sqrt(float a) { return sqrtf(a); }
-__device__ __forceinline__ double r_sqrt(double a) { return sqrt(a); }
-__device__ __forceinline__ float r_sin(float a) { return sinf(a); }
-__device__ __forceinline__ double r_sin(double a) { return sin(a); }
-__device__ __forceinline__ float r_cos(float a) { return cosf(a); }
-__device__ __forceinline__ double r_cos(double a) { return cos(a); }
-__device__ __forceinline__ float r_exp(float a) { return expf(a); }
-__device__ __forceinline__ double r_exp(double a) { return exp(a); }
-// batch_rodrigues' 1e-8 (a Python float: rounded to the tensor's dtype)
-template <class Real> __device__ __forceinline__ Real rodrigues_eps() { return (Real)1e-8; }
-template <> __device__ __forceinline__ float rodrigues_eps<float>() { return 1e-8f; }
-// an integer parked in a slot of the reduction scratch
-__device__ __forceinline__ void red_put_int(float& r, int n) { r = __int_as_float(n); }
-__device__ __forceinline__ void red_put_int(double& r, int n) { r = (double)n; }
-__device__ __forceinline__ int red_get_int(float r) { return __float_as_int(r); }
-__device__ __forceinline__ int red_get_int(double r) { return (int)r; }
-
-// threads per closure workgroup: a property of the LDS variant (FrameLDSx::kThreads) -- 256 for the body-only working set
-// (two or three workgroups share a CU), 512 for the full one (142 KB: the workgroup owns its CU, and what it does there is
-// stream VPoser weights and adjoint rows through that CU's L2 port: 8 wavefronts keep 108 GB/s in flight, 4 keep 93)
-#ifndef SFX_BIG_THREADS
-#define SFX_BIG_THREADS 512
-#endif
-#define SFX_MAX_THREADS 512
 // RIF = 2-KiB blend-shape rows in flight per wavefront (forward dots and dfeat adjoint): 4 for the
 // body-only variant (33 rows: 16 + 16 + 1), SFX_RIF_BIG for the full model (675 rows)
 // debug timing: block 0 / thread 0 stores the shader clock at phase boundaries when D.dbg != NULL
@@ -93,289 +31,6 @@ __device__ __forceinline__ int red_get_int(double r) { return (int)r; }
 // compiler unroll and overlap the (dependent) LDS reads of the iterations
 #define FOR_CT(w, N) _Pragma("unroll") for (int w##_i = 0; w##_i < ((N) + CT - 1) / CT; ++w##_i)             \
                          if (const int w = t + w##_i * CT; w < (N))
-
-struct EmptyLDS {};
-
-// Asynchronous global -> LDS copies by the whole workgroup (LDS-DMA, `global_load_lds_dword[x4]`): no registers, and no wait
-// until the next __syncthreads (which carries the vmcnt(0)).  Every table a closure workgroup needs at entry -- model
-// tables, this frame's record, the forward state of the previous launch -- is requested back to back this way: ONE memory
-// round trip instead of one per copy loop (the entry of k_tick_dense was 7.7 us body-only / 11 us with hands + face).
-// The destination of one wave-instruction is a contiguous run of 64 dwords (or 64 x 16 bytes) starting at a wave-uniform
-// LDS address; sources are per-lane.
-typedef __attribute__((address_space(3))) void* sfx_lds_vp;
-typedef const __attribute__((address_space(1))) void* sfx_glb_vp;
-template <int CT>
-__device__ __forceinline__ void lds_fill_async(void* lds_dst, const void* gsrc, const int n_dwords) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const char* g = reinterpret_cast<const char*>(gsrc);
-    char* l = reinterpret_cast<char*>(lds_dst);
-    for (int base = wv * 64; base < n_dwords; base += CT) {
-        const int i = base + lane;
-        if (i < n_dwords) __builtin_amdgcn_global_load_lds((sfx_glb_vp)(g + 4 * (size_t)i), (sfx_lds_vp)(l + 4 * base), 4, 0, 0);
-    }
-}
-// LDS-DMA completes in vmcnt order: the barrier that publishes DMA-filled LDS to the other wavefronts must be preceded by a
-// wait for this wavefront's own copies.  The compiler emits that s_waitcnt in front of every such s_barrier today; the memory
-// model does not oblige it to (a workgroup-scope release needs lgkmcnt only), so it is spelled out (CK: block_sync_lds_direct_load).
-__device__ __forceinline__ void lds_dma_wait() { __builtin_amdgcn_s_waitcnt(0x0F70); }      // vmcnt(0); expcnt / lgkmcnt untouched
-// the same in 16-byte units (both sides 16-byte aligned)
-template <int CT>
-__device__ __forceinline__ void lds_fill_async16(void* lds_dst, const void* gsrc, const int n16) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const char* g = reinterpret_cast<const char*>(gsrc);
-    char* l = reinterpret_cast<char*>(lds_dst);
-    for (int base = wv * 64; base < n16; base += CT) {
-        const int i = base + lane;
-        if (i < n16) __builtin_amdgcn_global_load_lds((sfx_glb_vp)(g + 16 * (size_t)i), (sfx_lds_vp)(l + 16 * base), 16, 0, 0);
-    }
-}
-
-// Self-served blend offsets: what the dense GEMM (lbs_dense.hip) exports as BatchDev.uvp -- sum_k featR[column][k] dirs[k][vertex,
-// coordinate] for the n_uniq exported vertices -- formed by the frame's own workgroup from its operand row `arow`, bit for bit:
-// the GEMM's instruction (v_mfma_f32_16x16x4_f32), accumulator from zero, its K order (SFX_DENSE_KCHUNK, rows ascending inside
-// a chunk, k = 4 ks + kq in lane group kq), no template added.  The rows of an MFMA tile are independent, so all 16 A rows carry
-// this frame's operand and row 0 (lanes 0-15, register 0) is read; the B columns are the exported vertices, whose rows of dirsT
-// the model keeps a second time in the order this chain consumes them (DevModel.uniq_dirs: one 16-byte load per lane and four
-// steps; gathered from dirsT itself -- 4-byte loads at stride 16 over 16 rows -- the phase cost 9.4 us per launch, LAB_NOTES 4.9).
-// One accumulator chain per (tile of 16 vertices, coordinate), dealt to the `nw` wavefronts that call (wavefront wv of them): 128
-// dependent MFMAs, B operands fetched four chunks (32 steps) ahead.  out[u * 3 + c], LDS or global; any n_uniq (0: nothing).
-typedef float sfx_f32x4 __attribute__((ext_vector_type(4)));
-[[maybe_unused]] static __device__ __forceinline__ void self_blend_offsets(const float* __restrict__ uniq_dirs, const int n_uniq, const float* __restrict__ arow,
-                                                                           float* out, const int wv, const int nw, const int lane) {
-    constexpr int NCH = SFX_KD_PAD / SFX_DENSE_KC, KS = SFX_DENSE_KC / 4;      // 16 chunks of 8 MFMA steps
-    constexpr int NG = 4, GS = NG * KS;                                         // chunks / steps per operand group
-    static_assert(NCH % NG == 0 && KS % 4 == 0 && NCH * KS == 128, "operand groups; DevModel.uniq_dirs holds 128 steps per unit");
-    const int jl = lane & 15, kq = lane >> 4;
-    const int nunit = ((n_uniq + 15) / 16) * 3;
-    for (int unit = wv; unit < nunit; unit += nw) {
-        const int tile = unit / 3, co = unit - tile * 3;
-        const int u = tile * 16 + jl;
-        const float4* pb = reinterpret_cast<const float4*>(uniq_dirs) + (size_t)unit * (NCH * KS / 4) * 64 + lane;
-        const float* pa = arow + kq;
-        float a[NCH * KS];
-        float4 bv[2][GS / 4];
-#pragma unroll
-        for (int c = 0; c < NCH; ++c)
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) a[c * KS + ks] = pa[SFX_DENSE_KCHUNK(c) * SFX_DENSE_KC + ks * 4];
-#define SELF_LOAD(g, buf) _Pragma("unroll") for (int q = 0; q < GS / 4; ++q) bv[buf][q] = pb[((g) * (GS / 4) + q) * 64];
-        sfx_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        SELF_LOAD(0, 0)
-#pragma unroll
-        for (int g = 0; g < NCH / NG; ++g) {
-            if (g + 1 < NCH / NG) { SELF_LOAD(g + 1, (g + 1) & 1) }
-            __builtin_amdgcn_sched_barrier(0);      // (keep the next group's loads in front of this group's chain: left alone, the scheduler sinks them to 8 steps ahead)
-#pragma unroll
-            for (int q = 0; q < GS / 4; ++q) {
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[g * GS + 4 * q + 0], bv[g & 1][q].x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[g * GS + 4 * q + 1], bv[g & 1][q].y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[g * GS + 4 * q + 2], bv[g & 1][q].z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[g * GS + 4 * q + 3], bv[g & 1][q].w, acc, 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#undef SELF_LOAD
-        if (kq == 0 && u < n_uniq) out[u * 3 + co] = acc[0];
-    }
-}
-
-// Per-frame working set of the closure workgroup.  MAXI = item capacity, VP = VPoser activations
-// present.  Two variants are instantiated: <240, true> (any model / configuration, 86 KB) and
-// <32, false> (body-only keypoints without VPoser, 47 KB -> three workgroups per CU, or one next
-// to two 48-KB GEMM workgroups).
-// TH (round 4): threads of the workgroup when not the variant's default -- the body-only set on 512 threads where a workgroup owns
-// its CU (k_tick_dense at <= 256 frames): two wavefronts per SIMD cover each other's LDS round trips in the barrier-separated
-// passes.  The same bits as on 256 threads: every sum across wavefronts either has its terms in the first four wavefronts on
-// both (threads >= 256 hold no keypoint, parameter or item of this variant: they add zeros) or is dealt to kRowWaves = 4
-// wavefronts whatever the thread count (the adjoint's row streams), and the layout -- the forward-state blob two launches
-// hand each other -- does not depend on TH.
-// Real (the float64 mode, sfx_batch_cfg.high_precision = 2: double): the closure's working precision -- parameters,
-// rotations, blend-shape sums, item vertices and transforms, losses and the whole reverse sweep.  The copies of model
-// tables (vt, iw, ww, sjw, djw) stay fp32: the model is fp32 and widening it is exact.
-template <int MAXI, bool VP, int TH, class Real>
-struct __align__(16) FrameLDSBase {
-    using real_t = Real;
-    static constexpr int kMaxItems = MAXI;
-    static constexpr int kBlocksPerCU = (MAXI <= SFX_SMALL_ITEMS && !VP) ? SFX_SMALL_OCC : 1;    // register budget of the fused kernels
-    static constexpr int kThreads = TH ? TH : ((MAXI <= SFX_SMALL_ITEMS && !VP) ? 256 : SFX_BIG_THREADS);
-    static constexpr int kRowWaves = (MAXI <= SFX_SMALL_ITEMS && !VP) ? 4 : kThreads / 64;        // wavefronts that stream adjoint rows
-    // scratch T: the item transforms, and (reverse sweep) one 512-float partial per row-streaming wavefront
-    static constexpr int kScratch = (MAXI * 12 > kRowWaves * 512) ? MAXI * 12 : kRowWaves * 512;
-    Real  feat[SFX_KD_PAD];        // first: read as float4
-    Real  x[SFX_NPAR_MAX];
-    Real  full_pose[168];
-    Real  R[SFX_J * 9];
-    Real  Jr[SFX_J * 3];
-    Real  G[SFX_J * 12];
-    Real  A[SFX_J * 12];
-    // the part of the forward whose ROUNDING NOISE decides when the line search stalls is carried in fp64 (see
-    // "forward precision" below): skinning transforms and posed kinematic joints; saved with the prefix above
-    fwd_t Ad[SFX_J * 12];
-    fwd_t Gt[SFX_J * 3 + 3];      // (+3: keeps the saved prefix a multiple of 16 bytes in either precision)
-    Real  vp[MAXI * 3];            // v_posed of the items (template + blend offsets), for the reverse sweep
-    Real  vpo[MAXI * 3];           // the blend offsets alone (small numbers: fp32 sums of them carry ~1e-10 m)
-    float vt[MAXI * 3];            // v_template rows of the items
-    alignas(16) Real T[kScratch]; // item transforms [MAXI][12]; reused as scratch (>= 2048 floats) by the reverse sweep and, between
-                                   // evaluations, as the working set of the optimiser tick (float4 accesses)
-    fwd_t cd[2 * SFX_J * 12];     // kinematic chain in fp64: the two buffers of the pointer-jumping rounds
-    fwd_t Jd[SFX_J * 3];          // rest joints, fp64
-    fwd_t jd[SFX_MAX_K * 3];      // mapped joints, fp64 (what the projection reads)
-    Real  dvert[MAXI * 3];
-    Real  dvp[MAXI * 3];
-    int   rl[MAXI * 3];            // compacted list of the blend-shape rows the adjoint streams (row = vertex * 3 + coordinate) ...
-    Real  rc[MAXI * 3];            // ... and their coefficients (d v_posed), nonzero entries only
-    int   ivid[MAXI];
-    int   uslot[MAXI];             // static items: index of the item's vertex in the dense GEMM's export (BatchDev.uvp)
-    float iw[MAXI];
-    int   wj[MAXI * SFX_NW];       // sparse skinning weights of the items
-    float ww[MAXI * SFX_NW];
-    int   sjs[SFX_J + 1];          // per-joint lists of the static items (adjoint of the skinning: dA), copied from the
-    int   sji[MAXI * SFX_NW];      //   model's CSR when it fits (M.n_sj <= MAXI * SFX_NW): two dependent global round trips
-    float sjw[MAXI * SFX_NW];      //   per evaluation otherwise
-    static constexpr int kMaxDyn = (MAXI > SFX_SMALL_ITEMS) ? SFX_MAX_DYN : 1;
-    int   djs[SFX_J + 1];          // the same for the dynamic-contour items of this frame's LUT row (DevModel.dynp_*)
-    int   dji[kMaxDyn * SFX_NW];
-    float djw[kMaxDyn * SFX_NW];
-    Real  joints[SFX_MAX_K * 3];
-    Real  dj[SFX_MAX_K * 3];
-    Real  dA[SFX_J * 12];
-    Real  dG[SFX_J * 12];
-    Real  drel[SFX_J * 3];
-    Real  dJ[SFX_J * 3];
-    Real  dR[SFX_J * 9];
-    Real  dfeat[SFX_KD_PAD];
-    Real  dpose[168];
-    Real  gc[SFX_NPAR_MAX];
-    Real  red[SFX_MAX_THREADS];
-    Real  lh45[SFX_NHAND], rh45[SFX_NHAND];    // } contiguous: saved / reloaded as one run of 2 * SFX_NHAND + 1 dwords
-    int   lut_row;                             // }
-    typename std::conditional<VP, VposerLDS, EmptyLDS>::type V;   // VPoser activations (use_vposer only)
-    alignas(16) float fd[FD_N]; // this frame's keypoints / weights / camera / regression pose (image of BatchDev.fd)
-    alignas(16) int meta[SFX_META_N];     // tree / joint-map tables (one coalesced load instead of
-                                // dependent global loads inside every level of the chain)
-};
-template <int MAXI, bool VP, int TH = 0>
-struct FrameLDSx : FrameLDSBase<MAXI, VP, TH, float> {};
-using FrameLDS = FrameLDSx<SFX_MAX_ITEMS, true>;
-using FrameLDSSmall = FrameLDSx<SFX_SMALL_ITEMS, false>;
-using FrameLDSSmall8 = FrameLDSx<SFX_SMALL_ITEMS, false, 512>;      // the same set on eight wavefronts (k_tick_dense, a workgroup per CU)
-// the body-only set in double (float64 mode, needed-rows path): one workgroup per CU
-struct FrameLDSSmall64 : FrameLDSBase<SFX_SMALL_ITEMS, false, 0, double> {};
-static_assert(sizeof(FrameLDSSmall64) + 4096 <= 160 * 1024, "float64 closure working set: LDS of one workgroup");
-
-__device__ __forceinline__ float wave_sum(float v) { return wave_sum_dpp(v); }
-__device__ __forceinline__ double wave_sum(double v) { return wave_sum_dpp(v); }
-template <int CTRL>
-__device__ __forceinline__ float lb_quad(float x) {       // DPP quad permutation of x (all lanes of the quad active)
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, true));
-}
-template <int CTRL>
-__device__ __forceinline__ double lb_quad(double x) {     // the same in fp64: both halves take the same permutation
-    const long long u = __double_as_longlong(x);
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)u, CTRL, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(u >> 32), CTRL, 0xf, 0xf, true);
-    return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
-}
-
-// fixed-order block reduction: DPP sum per wavefront, then the CT/64 partials in order
-// (2 barriers instead of a 9-barrier LDS tree); result in all threads
-template <int CT, class Real>
-__device__ __forceinline__ Real block_sum(Real v, Real* red) {
-    const Real w = wave_sum_dpp(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
-    __syncthreads();
-    Real r = red[0];
-#pragma unroll
-    for (int i = 1; i < CT / 64; ++i) r += red[i];
-    __syncthreads();
-    return r;
-}
-
-// smplx.lbs.batch_rodrigues: angle = ||theta + 1e-8||, R = I + sin K + (1-cos) K K
-__device__ __forceinline__ void rodrigues_fwd(const float* th, float* R) {
-    const float ex = th[0] + 1e-8f, ey = th[1] + 1e-8f, ez = th[2] + 1e-8f;
-    const float a = sqrtf(ex * ex + ey * ey + ez * ez);
-    const float dx = th[0] / a, dy = th[1] / a, dz = th[2] / a;
-    const float s = sinf(a), c = cosf(a);
-    const float K[9] = {0.f, -dz, dy, dz, 0.f, -dx, -dy, dx, 0.f};
-    const float omc = 1.f - c;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            float kk = K[i * 3 + 0] * K[0 * 3 + j] + K[i * 3 + 1] * K[1 * 3 + j] + K[i * 3 + 2] * K[2 * 3 + j];
-            R[i * 3 + j] = ((i == j) ? 1.f : 0.f) + s * K[i * 3 + j] + omc * kk;
-        }
-}
-
-// the same in fp64 (forward precision, see closure_body): R row-major
-template <class Tin>
-__device__ __forceinline__ void rodrigues_fwd_d(const Tin* th, fwd_t* R) {
-    const fwd_t t0 = th[0], t1 = th[1], t2 = th[2];
-    const fwd_t ex = t0 + (fwd_t)1e-8, ey = t1 + (fwd_t)1e-8, ez = t2 + (fwd_t)1e-8;
-    const fwd_t a = sqrt(ex * ex + ey * ey + ez * ez);
-    const fwd_t dx = t0 / a, dy = t1 / a, dz = t2 / a;
-    fwd_t s, c;
-    sincos_t(a, &s, &c);
-    const fwd_t K[9] = {0, -dz, dy, dz, 0, -dx, -dy, dx, 0};
-    const fwd_t omc = (fwd_t)1 - c;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const fwd_t kk = K[i * 3 + 0] * K[0 * 3 + j] + K[i * 3 + 1] * K[1 * 3 + j] + K[i * 3 + 2] * K[2 * 3 + j];
-            R[i * 3 + j] = ((i == j) ? (fwd_t)1 : (fwd_t)0) + s * K[i * 3 + j] + omc * kk;
-        }
-}
-
-// reverse of rodrigues_fwd: dth += J^T dR
-template <class Real>
-__device__ __forceinline__ void rodrigues_bwd(const Real* th, const Real* dR, Real* dth) {
-    const Real eps = rodrigues_eps<Real>();
-    const Real ex = th[0] + eps, ey = th[1] + eps, ez = th[2] + eps;
-    const Real a = r_sqrt(ex * ex + ey * ey + ez * ez);
-    const Real inv = 1.f / a;
-    const Real d[3] = {th[0] * inv, th[1] * inv, th[2] * inv};
-    const Real s = r_sin(a), c = r_cos(a), omc = 1.f - c;
-    const Real K[9] = {0.f, -d[2], d[1], d[2], 0.f, -d[0], -d[1], d[0], 0.f};
-    Real KK[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            KK[i * 3 + j] = K[i * 3 + 0] * K[j] + K[i * 3 + 1] * K[3 + j] + K[i * 3 + 2] * K[6 + j];
-    Real dRK = 0.f, dRKK = 0.f;
-#pragma unroll
-    for (int e = 0; e < 9; ++e) { dRK += dR[e] * K[e]; dRKK += dR[e] * KK[e]; }
-    Real da = c * dRK + s * dRKK;
-    // dK = s dR + (1-c) (dR K^T + K^T dR)
-    Real dK[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            Real t1 = 0.f, t2 = 0.f;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                t1 += dR[i * 3 + k] * K[j * 3 + k];     // dR K^T
-                t2 += K[k * 3 + i] * dR[k * 3 + j];     // K^T dR
-            }
-            dK[i * 3 + j] = s * dR[i * 3 + j] + omc * (t1 + t2);
-        }
-    const Real dd[3] = {dK[7] - dK[5], dK[2] - dK[6], dK[3] - dK[1]};
-    const Real ddth = dd[0] * th[0] + dd[1] * th[1] + dd[2] * th[2];
-    da -= ddth * inv * inv;
-    dth[0] += dd[0] * inv + da * ex * inv;
-    dth[1] += dd[1] * inv + da * ey * inv;
-    dth[2] += dd[2] * inv + da * ez * inv;
-}
-
-template <class Real>
-__device__ __forceinline__ Real gmof_grad(Real r, Real rho2) {
-    // d/dr [ rho^2 r^2 / (r^2 + rho^2) ] = 2 r rho^4 / (r^2 + rho^2)^2
-    const Real den = r * r + rho2;
-    return 2.f * r * (rho2 / den) * (rho2 / den);
-}
 
 // Reverse sweep with a caller-supplied upstream (lbs_backward.hip: the backward pass of the stand-alone LBS).  Passed as the last
 // argument of closure_body it selects, at compile time, the form in which the loss section (priors, projection) is skipped: d joints
@@ -789,7 +444,7 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
     }
     __syncthreads();
     };
-    if (args.use_dense_verts && !args.from_scratch_items) {
+    if (args.use_dense_verts) {
         // dense path: the GEMM that produced the vertices also left the blend offsets (v_posed - v_template) of every item
         // vertex (lbs_dense.hip epilogue) -- of the static items and of every vertex a dynamic-contour item can land on,
         // whichever LUT row this frame's head pose selects: no blend-shape row is streamed forward here

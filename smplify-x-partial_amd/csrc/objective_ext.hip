@@ -21,7 +21,7 @@
 // A keypoint whose weight is 0 is skipped as a whole: it adds +0 to every sum and its row of d joints is +0, whatever its
 // coordinates hold.
 #include "../../include/sfx.h"
-#include "closure_body.h"
+#include "closure_math.h"
 
 #define OBJ_WAVES 4
 #define OBJ_MAX_K 512        // keypoints per frame (the shipped joint maps: 25 .. 144)

@@ -139,7 +139,7 @@ struct DevModel {
     const int*   item_wj;      // [n_items][SFX_NW] = Wsp_j[item_vid]                  } one round trip at kernel entry
     const float* item_ww;      // [n_items][SFX_NW] = Wsp_w[item_vid]                  }
     const float* uniq_dirs;    // [ceil(n_uniq / 16) * 3][32][64][4] the blend-shape rows of the exported vertices as the B operands of
-                               // closure_body.h self_blend_offsets: per (tile of 16 export indices, coordinate) the 128 MFMA steps of
+                               // closure_lds.h self_blend_offsets: per (tile of 16 export indices, coordinate) the 128 MFMA steps of
                                // the dense GEMM's K order, four steps per lane and 16-byte load (model_tables.h)
     const void*  gap9_[3];
     int Vpad;
@@ -308,10 +308,9 @@ struct ClosureArgs {
     int stage_override;     // -2: use per-frame stage[]; otherwise stage for all frames
     int forward_only;       // 1: export joints / full_pose / featR / AT only
     int use_dense_verts;    // 1: the blend offsets of the item vertices come from the dense GEMM (BatchDev.uvp); 2: dense mode, but the
-                            //    workgroup forms them itself from its column of BatchDev.featR (closure_body.h self_blend_offsets: same bits)
+                            //    workgroup forms them itself from its column of BatchDev.featR (closure_lds.h self_blend_offsets: same bits)
     int export_dense;       // 1: write featR / AT for the dense kernel
     int from_X;             // 1: evaluate at X instead of Xt
-    int from_scratch_items; // 1: dense mode, but evaluate the item rows here (the GEMM export belongs to another call)
     int keep_tables;        // 1: S.meta / S.fd are still valid from the previous evaluation of this workgroup
     int reuse_fwd;          // 1: forward state of this trial point was saved by the export pass
     const float* x_lds;     // the trial point in the workgroup's LDS (k_tick_dense: left there by the optimiser tick); NULL: read X / Xt

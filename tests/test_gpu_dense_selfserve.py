@@ -1,6 +1,6 @@
 """Self-served blend offsets in the dense loop (run with -m gpu).  In rounds of the third form (csrc/api.hip DenseLoop::round_self) the tick
 workgroup no longer reads the blend offsets of its keypoint vertices from the dense GEMM's export (BatchDev.uvp): it forms them
-itself from its operand row with the GEMM's own chain of fp32 operations (csrc/closure_body.h self_blend_offsets), and the whole
+itself from its operand row with the GEMM's own chain of fp32 operations (csrc/closure_lds.h self_blend_offsets), and the whole
 GEMM of every evaluation runs beside the tick chain.  Nobody's arithmetic changes, so every comparison here is bit for bit:
 the routine against the GEMM's export, the loops against each other, a frame of a job against the frame alone."""
 import json
