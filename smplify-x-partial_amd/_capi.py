@@ -254,6 +254,25 @@ def check(rc):
         raise SfxError("libsfx error %d: %s" % (rc, load().sfx_last_error().decode()))
 
 
+class Handle(object):
+    """Owner of one library handle: `_lib`, `_h` and their release.  A subclass names its destroy symbol in `_destroy` and
+    sets `_lib` / `_h` once its create call has succeeded; before that (an __init__ that raised) close() finds nothing to do."""
+    _destroy = None
+    _lib = None
+    _h = None
+
+    def close(self):
+        h, self._h = self._h, None
+        if h:
+            getattr(self._lib, self._destroy)(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:       # (interpreter shutdown: the library or this module may be half gone)
+            pass
+
+
 def fptr(a):
     """numpy float32 C-contiguous array -> float* (None -> NULL).  Keeps no reference."""
     if a is None:

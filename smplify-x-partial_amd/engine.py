@@ -5,10 +5,13 @@ frames (the reference handles exactly one, fit_single_frame.py:119) and runs the
 reference's per-frame schedule for all of them on device.  The drop-in modules
 (`smplx`, `fitting`, `fit_single_frame`, ...) are thin adapters over these two classes.
 """
+import collections
 import ctypes as C
+import functools
 
 import numpy as np
 
+from . import _args as A
 from . import _capi as capi
 from .synthetic import SMPLX_EXTRA_VERTEX_IDS
 
@@ -65,10 +68,11 @@ def stage_weights_from_cfg(cfg, struct=None):
     return out, n
 
 
-class DeviceModel(object):
+class DeviceModel(capi.Handle):
     """SMPL-X constants resident in HBM (sfx_model).  `model` is a dict with the .npz key
     set of SURVEY.md appendix A.1 (a real SMPLX_*.npz loaded with numpy, or
     synthetic.make_synthetic_model())."""
+    _destroy = "sfx_model_destroy"
 
     def __init__(self, model, joint_map=None, num_betas=10, num_expression_coeffs=10,
                  num_pca_comps=12, flat_hand_mean=False, use_face_contour=True,
@@ -151,13 +155,9 @@ class DeviceModel(object):
         (fit_single_frame.py:316-328)."""
         sg, pr = capi.i32(np.asarray(segm).astype(np.int64)), capi.i32(np.asarray(parents).astype(np.int64))
         assert sg.shape == (self.F,) and pr.shape == (self.F,), "one label per face"
-        pairs = []
-        for p in ign_part_pairs or []:
-            a, b = (int(x) for x in str(p).split(",")) if isinstance(p, str) else p
-            pairs.append((a, b))
-        ign = capi.i32(np.asarray(pairs, np.int64).reshape(-1, 2))
+        ign = A.ign_pairs(ign_part_pairs)
         capi.check(self._lib.sfx_model_set_parts(self._h, capi.iptr(sg), capi.iptr(pr),
-                                                 capi.iptr(ign) if pairs else None, len(pairs)))
+                                                 capi.iptr(ign) if len(ign) else None, len(ign)))
         self.has_parts = True
 
     def clear_parts(self):
@@ -174,26 +174,39 @@ class DeviceModel(object):
         self.vposer_latent = latent
         self.vposer_weights = a          # the encoder (if present) runs on the host: vposer.encode
 
-    def lbs_forward(self, global_orient, body_pose, betas, expression, jaw_pose, leye_pose, reye_pose,
-                    left_hand_pose, right_hand_pose, return_verts=True, return_full_pose=True, stream=None):
-        """torch CUDA tensors in/out (containers only); one dense LBS launch sequence."""
-        import torch
-        B = global_orient.shape[0]
-        dev = global_orient.device
-        ptr = lambda t: C.c_void_p(t.contiguous().data_ptr()) if t is not None else None
-        ins = [t.contiguous().float() if t is not None else None for t in
-               (global_orient, body_pose, betas, expression, jaw_pose, leye_pose, reye_pose,
-                left_hand_pose, right_hand_pose)]
-        verts = torch.empty([B, self.V, 3], dtype=torch.float32, device=dev) if return_verts else None
-        joints = torch.empty([B, self.K, 3], dtype=torch.float32, device=dev)
-        fp = torch.empty([B, 165], dtype=torch.float32, device=dev) if return_full_pose else None
-        s = C.c_void_p(stream if stream is not None else torch.cuda.current_stream().cuda_stream)
-        capi.check(self._lib.sfx_lbs_forward(self._h, B, *[ptr(t) for t in ins], ptr(verts), ptr(joints), ptr(fp), s))
-        return verts, joints, fp
-
     # the nine inputs of lbs_forward / lbs_backward under the reference's parameter names, in the C ABI's order
     LBS_INPUTS = ("global_orient", "body_pose", "betas", "expression", "jaw_pose", "leye_pose", "reye_pose",
                   "left_hand_pose", "right_hand_pose")
+
+    @staticmethod
+    def _lbs_arg(name, t, shape, dev, optional):
+        """One tensor of lbs_forward / lbs_backward as the library reads it: float32, contiguous, of `shape`, on `dev` (any
+        dtype is converted; a tensor elsewhere is moved there)."""
+        import torch
+        if torch.is_tensor(t):
+            t = t.detach().to(dev)
+            if name == "body_pose" and t.dim() != 2:      # [B][21][3] as the reference passes it
+                t = t.reshape(shape[0], -1)
+        return A.tensor(name, t, shape, dev, optional=optional, convert=True, make_contiguous=True, non_tensor=ValueError)
+
+    def _lbs_inputs(self, ins, optional):
+        """B, device (both global_orient's) and the nine inputs as [B][n] tensors; optional: None passes (a NULL pointer)."""
+        B, dev = ins[0].shape[0], ins[0].device
+        want = (3, 63, self.num_betas, self.num_expr, 3, 3, 3, self.num_pca, self.num_pca)
+        return B, dev, [self._lbs_arg(name, t, (B, n), dev, optional) for name, t, n in zip(self.LBS_INPUTS, ins, want)]
+
+    def lbs_forward(self, global_orient, body_pose, betas, expression, jaw_pose, leye_pose, reye_pose,
+                    left_hand_pose, right_hand_pose, return_verts=True, return_full_pose=True, stream=None):
+        """torch CUDA tensors in/out (containers only); one dense LBS launch sequence.  Inputs [B][n] of any dtype (body_pose
+        [B][63] or [B][21][3]); None = not given."""
+        import torch
+        B, dev, ins = self._lbs_inputs((global_orient, body_pose, betas, expression, jaw_pose, leye_pose, reye_pose,
+                                        left_hand_pose, right_hand_pose), optional=True)
+        verts = torch.empty([B, self.V, 3], dtype=torch.float32, device=dev) if return_verts else None
+        joints = torch.empty([B, self.K, 3], dtype=torch.float32, device=dev)
+        fp = torch.empty([B, 165], dtype=torch.float32, device=dev) if return_full_pose else None
+        capi.check(self._lib.sfx_lbs_forward(self._h, B, *[A.ptr(t) for t in ins + [verts, joints, fp]], A.stream(stream)))
+        return verts, joints, fp
 
     def lbs_backward(self, global_orient, body_pose, betas, expression, jaw_pose, leye_pose, reye_pose,
                      left_hand_pose, right_hand_pose, dvertices=None, djoints=None, stream=None):
@@ -205,45 +218,36 @@ class DeviceModel(object):
         import torch
         if dvertices is None and djoints is None:
             raise ValueError("lbs_backward needs an upstream gradient: dvertices, djoints or both")
-        B = global_orient.shape[0]
-        dev = global_orient.device
-        ins = [t.detach().to(dev, torch.float32).contiguous() for t in
-               (global_orient, body_pose, betas, expression, jaw_pose, leye_pose, reye_pose, left_hand_pose, right_hand_pose)]
-        ins[1] = ins[1].reshape(B, -1)
-        want = (3, 63, self.num_betas, self.num_expr, 3, 3, 3, self.num_pca, self.num_pca)
-        for name, t, n in zip(self.LBS_INPUTS, ins, want):
-            if tuple(t.shape) != (B, n):
-                raise ValueError("%s: shape %s, expected %s" % (name, tuple(t.shape), (B, n)))
-        ups = []
-        for name, t, shape in (("dvertices", dvertices, (B, self.V, 3)), ("djoints", djoints, (B, self.K, 3))):
-            if t is not None:
-                if tuple(t.shape) != shape:
-                    raise ValueError("%s: shape %s, expected %s" % (name, tuple(t.shape), shape))
-                t = t.detach().to(dev, torch.float32).contiguous()
-            ups.append(t)
+        B, dev, ins = self._lbs_inputs((global_orient, body_pose, betas, expression, jaw_pose, leye_pose, reye_pose,
+                                        left_hand_pose, right_hand_pose), optional=False)
+        ups = [self._lbs_arg("dvertices", dvertices, (B, self.V, 3), dev, True),
+               self._lbs_arg("djoints", djoints, (B, self.K, 3), dev, True)]
         outs = [torch.empty_like(t) for t in ins]
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        s = C.c_void_p(stream if stream is not None else torch.cuda.current_stream().cuda_stream)
-        capi.check(self._lib.sfx_lbs_backward(self._h, B, *[ptr(t) for t in ins + ups + outs], s))
+        capi.check(self._lib.sfx_lbs_backward(self._h, B, *[A.ptr(t) for t in ins + ups + outs], A.stream(stream)))
         return dict(zip(self.LBS_INPUTS, outs))
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.sfx_model_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+# an input of the stand-alone VPoser calls: any dtype and any strides are taken (converted, copied)
+_vposer_in = functools.partial(A.tensor, convert=True, make_contiguous=True, non_tensor=ValueError)
 
 
-class VPoserDecoder(object):
+def _flat(t):
+    """[B][21][3] / [B][1][21][3], as the reference passes poses, -> [B][63]; anything else as it is."""
+    import torch
+    return t.reshape(t.shape[0], -1) if torch.is_tensor(t) and t.dim() > 2 else t
+
+
+def _cuda(index):
+    import torch
+    return torch.device("cuda", index)
+
+
+class VPoserDecoder(capi.Handle):
     """VPoser-v1 decoder weights resident in HBM (sfx_vposer): `decode` / `decode_backward` for whole batches of latents,
     outside any fit (inside one the closure workgroup decodes: csrc/vposer.h).  `weights` is the numpy dict
     DeviceModel.set_vposer takes (fc1_w [512][L], fc1_b, fc2_w, fc2_b, out_w [126][512], out_b).  The handle lives on the
-    device that is current when it is made."""
+    device that is current when it is made (`device_index`)."""
+    _destroy = "sfx_vposer_destroy"
 
     def __init__(self, weights):
         lib = capi.load()
@@ -256,61 +260,28 @@ class VPoserDecoder(object):
         h = C.c_void_p()
         capi.check(lib.sfx_vposer_create(latent, hidden, capi.fptr(a["fc1_w"]), capi.fptr(a["fc1_b"]), capi.fptr(a["fc2_w"]),
                                          capi.fptr(a["fc2_b"]), capi.fptr(a["out_w"]), capi.fptr(a["out_b"]), C.byref(h)))
+        import torch
         self._h, self._lib = h, lib
         self.latent = latent
-
-    def _in(self, name, t, n, B=None):
-        import torch
-        if not torch.is_tensor(t) or t.dim() != 2 or t.shape[1] != n or (B is not None and t.shape[0] != B):
-            raise ValueError("%s: shape %s, expected %s" % (name, tuple(getattr(t, "shape", ())), ("B" if B is None else B, n)))
-        if t.device.type != "cuda":
-            raise ValueError("%s: a CUDA tensor is needed (no CPU fallback), got device %s" % (name, t.device))
-        return t.detach().to(torch.float32).contiguous()
+        self.device_index = torch.cuda.current_device()      # where the weights live: every tensor of a call must be there
 
     def decode(self, z, out=None, stream=None):
         """z [B][latent] (torch CUDA tensor) -> body_pose [B][63], axis-angle of the 21 body joints.  `out`: a float32
         contiguous [B][63] tensor on z's device to write into.  Only enqueues on the current (or the given) stream."""
-        import torch
-        z = self._in("z", z, self.latent)
+        z = _vposer_in("z", z, (None, self.latent), _cuda(self.device_index), holder="the decoder's weights")
         B = z.shape[0]
-        if out is None:
-            out = torch.empty([B, 63], dtype=torch.float32, device=z.device)
-        elif tuple(out.shape) != (B, 63) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != z.device:
-            raise ValueError("out: a contiguous float32 %s tensor on %s is needed" % ((B, 63), z.device))
-        s = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(z.device).cuda_stream)
-        capi.check(self._lib.sfx_vposer_decode(self._h, B, C.c_void_p(z.data_ptr()), C.c_void_p(out.data_ptr()), s))
+        out = A.out_tensor("out", out, (B, 63), z.device)
+        capi.check(self._lib.sfx_vposer_decode(self._h, B, A.ptr(z), A.ptr(out), A.stream(stream, z.device)))
         return out
 
     def decode_backward(self, z, dbody, out=None, stream=None):
         """d sum(dbody * decode(z)) / d z: [B][latent].  Stateless: z is given again and the forward re-evaluated at it."""
-        import torch
-        z = self._in("z", z, self.latent)
+        z = _vposer_in("z", z, (None, self.latent), _cuda(self.device_index), holder="the decoder's weights")
         B = z.shape[0]
-        if torch.is_tensor(dbody) and dbody.dim() > 2:
-            dbody = dbody.reshape(dbody.shape[0], -1)
-        dbody = self._in("dbody", dbody, 63, B)
-        if dbody.device != z.device:
-            raise ValueError("dbody: on %s, z on %s" % (dbody.device, z.device))
-        if out is None:
-            out = torch.empty([B, self.latent], dtype=torch.float32, device=z.device)
-        elif (tuple(out.shape) != (B, self.latent) or out.dtype != torch.float32 or not out.is_contiguous()
-              or out.device != z.device):
-            raise ValueError("out: a contiguous float32 %s tensor on %s is needed" % ((B, self.latent), z.device))
-        s = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(z.device).cuda_stream)
-        capi.check(self._lib.sfx_vposer_decode_backward(self._h, B, C.c_void_p(z.data_ptr()), C.c_void_p(dbody.data_ptr()),
-                                                        C.c_void_p(out.data_ptr()), s))
+        dbody = _vposer_in("dbody", _flat(dbody), (B, 63), z.device, holder="z")
+        out = A.out_tensor("out", out, (B, self.latent), z.device)
+        capi.check(self._lib.sfx_vposer_decode_backward(self._h, B, A.ptr(z), A.ptr(dbody), A.ptr(out), A.stream(stream, z.device)))
         return out
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.sfx_vposer_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 _ENC_KEYS = ("enc_bn1_w", "enc_bn1_b", "enc_bn1_mean", "enc_bn1_var", "enc_fc1_w", "enc_fc1_b",
@@ -318,11 +289,12 @@ _ENC_KEYS = ("enc_bn1_w", "enc_bn1_b", "enc_bn1_mean", "enc_bn1_var", "enc_fc1_w
              "enc_mu_w", "enc_mu_b", "enc_logvar_w", "enc_logvar_b")
 
 
-class VPoserEncoder(object):
+class VPoserEncoder(capi.Handle):
     """VPoser-v1 encoder weights resident in HBM (sfx_vposer_encoder): `encode` / `encode_backward` for whole batches of
     poses.  `weights` is the numpy dict of vposer.load_vposer with its `enc_*` keys (bn1, fc1 [512][63 | 189], bn2, fc2, mu and
     logvar [L][512]); the batch norms are folded into the linear layers on the host.  The handle lives on the device that is
     current when it is made."""
+    _destroy = "sfx_vposer_encoder_destroy"
 
     def __init__(self, weights):
         lib = capi.load()
@@ -348,30 +320,8 @@ class VPoserEncoder(object):
         self.latent, self.n_in = latent, n_in
         self.device_index = torch.cuda.current_device()      # where the weights live: every tensor of a call must be there
 
-    def _in(self, name, t, n, B=None):
-        import torch
-        if not torch.is_tensor(t) or t.dim() != 2 or t.shape[1] != n or (B is not None and t.shape[0] != B):
-            raise ValueError("%s: shape %s, expected %s" % (name, tuple(getattr(t, "shape", ())), ("B" if B is None else B, n)))
-        if t.device.type != "cuda":
-            raise ValueError("%s: a CUDA tensor is needed (no CPU fallback), got device %s" % (name, t.device))
-        return t.detach().to(torch.float32).contiguous()
-
-    def _out(self, name, out, shape, device):
-        import torch
-        if out is None:
-            return torch.empty(list(shape), dtype=torch.float32, device=device)
-        if tuple(out.shape) != tuple(shape) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != device:
-            raise ValueError("%s: a contiguous float32 %s tensor on %s is needed" % (name, tuple(shape), device))
-        return out
-
     def _pose(self, pose):
-        import torch
-        if torch.is_tensor(pose) and pose.dim() > 2:
-            pose = pose.reshape(pose.shape[0], -1)
-        pose = self._in("pose", pose, 63)
-        if pose.device.index != self.device_index:
-            raise ValueError("pose: on %s, the encoder's weights on cuda:%d" % (pose.device, self.device_index))
-        return pose
+        return _vposer_in("pose", _flat(pose), (None, 63), _cuda(self.device_index), holder="the encoder's weights")
 
     def encode(self, pose, out_mean=None, out_sigma=None, stream=None):
         """pose [B][63] (torch CUDA tensor; [B][21][3] and [B][1][21][3] are flattened) -> (mean, sigma), both [B][latent]: the
@@ -379,47 +329,26 @@ class VPoserEncoder(object):
         contiguous [B][latent] tensors on pose's device to write into.  `out_sigma=False`: sigma is not wanted (a prior on the
         mean alone) -- it is neither evaluated nor stored, and (mean, None) is returned.  Only enqueues on the current (or the
         given) stream."""
-        import torch
         pose = self._pose(pose)
         B = pose.shape[0]
-        mean = self._out("out_mean", out_mean, (B, self.latent), pose.device)
-        sigma = None if out_sigma is False else self._out("out_sigma", out_sigma, (B, self.latent), pose.device)
-        s = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(pose.device).cuda_stream)
-        capi.check(self._lib.sfx_vposer_encode(self._h, B, C.c_void_p(pose.data_ptr()), C.c_void_p(mean.data_ptr()),
-                                               C.c_void_p(sigma.data_ptr()) if sigma is not None else None, s))
+        mean = A.out_tensor("out_mean", out_mean, (B, self.latent), pose.device)
+        sigma = None if out_sigma is False else A.out_tensor("out_sigma", out_sigma, (B, self.latent), pose.device)
+        capi.check(self._lib.sfx_vposer_encode(self._h, B, A.ptr(pose), A.ptr(mean), A.ptr(sigma), A.stream(stream, pose.device)))
         return mean, sigma
 
     def encode_backward(self, pose, dmean, dsigma, out=None, stream=None):
         """d (sum(dmean * mean) + sum(dsigma * sigma)) / d pose: [B][63].  One of dmean / dsigma may be None (= zeros).
         Stateless: pose is given again and the forward re-evaluated at it."""
-        import torch
         pose = self._pose(pose)
         B = pose.shape[0]
         if dmean is None and dsigma is None:
             raise ValueError("dmean and dsigma: at least one is needed")
-        grads = []
-        for name, d in (("dmean", dmean), ("dsigma", dsigma)):
-            if d is not None:
-                d = self._in(name, d, self.latent, B)
-                if d.device != pose.device:
-                    raise ValueError("%s: on %s, pose on %s" % (name, d.device, pose.device))
-            grads.append(d)
-        out = self._out("out", out, (B, 63), pose.device)
-        s = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(pose.device).cuda_stream)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        capi.check(self._lib.sfx_vposer_encode_backward(self._h, B, ptr(pose), ptr(grads[0]), ptr(grads[1]), ptr(out), s))
+        grads = [_vposer_in(name, d, (B, self.latent), pose.device, optional=True, holder="pose")
+                 for name, d in (("dmean", dmean), ("dsigma", dsigma))]
+        out = A.out_tensor("out", out, (B, 63), pose.device)
+        capi.check(self._lib.sfx_vposer_encode_backward(self._h, B, A.ptr(pose), A.ptr(grads[0]), A.ptr(grads[1]), A.ptr(out),
+                                                        A.stream(stream, pose.device)))
         return out
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.sfx_vposer_encoder_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 PRECISIONS = ("mixed", "float64")
@@ -465,8 +394,44 @@ def widen_stage_weights(stages):
     return out
 
 
-class FrameBatch(object):
+# the two number formats a FrameBatch exchanges its host arrays in: numpy dtype, conversion to it (contiguous), pointer,
+# suffix of the sfx_batch_* entry points that take it
+_Mode = collections.namedtuple("_Mode", "dtype cast ptr suffix")
+_F32 = _Mode(np.float32, capi.f32, capi.fptr, "")
+_F64 = _Mode(np.float64, capi.f64, capi.dptr, "_f64")
+
+
+def _pack_frames(m, B, K, keypoints, joint_weights, cam_init_mask, focal, center, data_weight, est_tz=None, cam_rot=None):
+    """The five arrays of sfx_batch_set_frames in mode `m`: keypoints [B][K][3], joint weights and camera-init mask [B][K] (one
+    frame's are broadcast), the camera record [B][6] = (fx, fy, cx, cy, data_weight, est_tz or 0) and the rotation [B][9]
+    (None = identity).  The data -- keypoints, weights, masks, rotation -- are fp32 numbers, widened in float64 mode; the
+    camera record is made in the mode's own dtype."""
+    kp = m.cast(capi.f32(keypoints)).reshape(B, K, 3)
+    jw = m.cast(np.broadcast_to(np.asarray(joint_weights, np.float32), (B, K)))
+    cm = m.cast(np.broadcast_to(np.asarray(cam_init_mask, np.float32), (B, K)))
+    cam = np.zeros((B, 6), m.dtype)
+    cam[:, 0] = cam[:, 1] = np.asarray(focal, m.dtype)
+    cam[:, 2:4] = np.asarray(center, m.dtype).reshape(-1, 2)
+    cam[:, 4] = np.asarray(data_weight, m.dtype)
+    if est_tz is not None:
+        cam[:, 5] = np.asarray(est_tz, m.dtype)
+    R = np.tile(np.eye(3, dtype=m.dtype).reshape(1, 9), (B, 1)) if cam_rot is None else capi.f32(cam_rot).reshape(B, 9)
+    return kp, jw, cm, cam, m.cast(R)
+
+
+def _pack_params(m, B, sizes, nemb, regression_pose, params):
+    """The arguments of sfx_batch_set_params in mode `m`: one [B][sizes[name]] array (one frame's values are broadcast) or
+    None per PARAM_NAMES entry, taken in the mode's own dtype, and the regression pose [B][nemb], an fp32 number in both."""
+    args = [None if params.get(n) is None else
+            m.cast(np.broadcast_to(np.asarray(params[n], m.dtype).reshape(-1, sizes[n]), (B, sizes[n]))) for n in PARAM_NAMES]
+    reg = None if regression_pose is None else m.cast(capi.f32(
+        np.broadcast_to(np.asarray(regression_pose, np.float32).reshape(-1, nemb), (B, nemb))))
+    return args, reg
+
+
+class FrameBatch(capi.Handle):
     """B frames under one configuration (sfx_batch)."""
+    _destroy = "sfx_batch_destroy"
 
     def __init__(self, model, B, cfg, lbs_mode="dense", reuse_entry_eval=True, has_regression_pose=True,
                  stages=None, num_body_joints=None, side_view=False, slots=0, precision="mixed"):
@@ -482,6 +447,7 @@ class FrameBatch(object):
         self._lib = model._lib
         hp = check_precision(cfg, lbs_mode, has_regression_pose, precision)
         self.float64 = hp == 2
+        self._mode = _F64 if self.float64 else _F32
         stages64 = None
         if self.float64:
             stages64 = stage_weights_from_cfg(cfg, capi.StageWeights64)[0] if stages is None else widen_stage_weights(stages)
@@ -543,71 +509,31 @@ class FrameBatch(object):
             capi.check(self._lib.sfx_batch_set_stage_weights_f64(self._h, arr64))
 
     # ---- data ------------------------------------------------------------------------------
+    def _call(self, name, *args):
+        """sfx_batch_<name> in the batch's own number format (_Mode.suffix)."""
+        capi.check(getattr(self._lib, "sfx_batch_" + name + self._mode.suffix)(self._h, *args))
+
     def set_frames(self, keypoints, joint_weights, cam_init_mask, focal, center, data_weight, est_tz=None,
                    cam_rot=None):
-        B, K = self.B, self.K
-        if self.float64:        # keypoints, weights, masks, rotation widened from fp32; the camera in double
-            kp = capi.f64(capi.f32(keypoints)).reshape(B, K, 3)
-            jw = capi.f64(np.broadcast_to(np.asarray(joint_weights, np.float32), (B, K)))
-            cm = capi.f64(np.broadcast_to(np.asarray(cam_init_mask, np.float32), (B, K)))
-            cam = np.zeros((B, 6), np.float64)
-            cam[:, 0] = cam[:, 1] = np.asarray(focal, np.float64)
-            cam[:, 2:4] = np.asarray(center, np.float64).reshape(-1, 2)
-            cam[:, 4] = np.asarray(data_weight, np.float64)
-            if est_tz is not None:
-                cam[:, 5] = np.asarray(est_tz, np.float64)
-            R = np.tile(np.eye(3).reshape(1, 9), (B, 1)) if cam_rot is None else capi.f64(capi.f32(cam_rot)).reshape(B, 9)
-            capi.check(self._lib.sfx_batch_set_frames_f64(self._h, capi.dptr(kp), capi.dptr(jw), capi.dptr(cm),
-                                                          capi.dptr(cam), capi.dptr(capi.f64(R))))
-            return
-        kp = capi.f32(keypoints).reshape(B, K, 3)
-        jw = capi.f32(np.broadcast_to(np.asarray(joint_weights, np.float32), (B, K)))
-        cm = capi.f32(np.broadcast_to(np.asarray(cam_init_mask, np.float32), (B, K)))
-        cam = np.zeros((B, 6), np.float32)
-        cam[:, 0] = cam[:, 1] = np.asarray(focal, np.float32)
-        cam[:, 2:4] = np.asarray(center, np.float32).reshape(-1, 2)
-        cam[:, 4] = np.asarray(data_weight, np.float32)
-        if est_tz is not None:
-            cam[:, 5] = np.asarray(est_tz, np.float32)
-        R = np.tile(np.eye(3, dtype=np.float32).reshape(1, 9), (B, 1)) if cam_rot is None else \
-            capi.f32(cam_rot).reshape(B, 9)
-        capi.check(self._lib.sfx_batch_set_frames(self._h, capi.fptr(kp), capi.fptr(jw), capi.fptr(cm),
-                                                  capi.fptr(cam), capi.fptr(capi.f32(R))))
+        arrays = _pack_frames(self._mode, self.B, self.K, keypoints, joint_weights, cam_init_mask, focal, center, data_weight,
+                              est_tz, cam_rot)
+        self._call("set_frames", *[self._mode.ptr(a) for a in arrays])
+
+    def _sizes(self):
+        return dict(cam_translation=3, global_orient=3, betas=self.model.num_betas,
+                    left_hand_pose=self.model.num_pca, right_hand_pose=self.model.num_pca,
+                    expression=self.model.num_expr, jaw_pose=3, leye_pose=3, reye_pose=3,
+                    pose_embedding=self.nemb)
 
     def set_params(self, regression_pose=None, **p):
-        B = self.B
-        sizes = dict(cam_translation=3, global_orient=3, betas=self.model.num_betas,
-                     left_hand_pose=self.model.num_pca, right_hand_pose=self.model.num_pca,
-                     expression=self.model.num_expr, jaw_pose=3, leye_pose=3, reye_pose=3,
-                     pose_embedding=self.nemb)
-        if self.float64:
-            args = [None if p.get(n) is None else capi.f64(np.broadcast_to(np.asarray(p[n], np.float64).reshape(-1, sizes[n]),
-                                                                          (B, sizes[n]))) for n in PARAM_NAMES]
-            reg = None if regression_pose is None else capi.f64(capi.f32(
-                np.broadcast_to(np.asarray(regression_pose, np.float32).reshape(-1, self.nemb), (B, self.nemb))))
-            capi.check(self._lib.sfx_batch_set_params_f64(self._h, *[capi.dptr(a) for a in args], capi.dptr(reg)))
-            return
-        args = []
-        for n in PARAM_NAMES:
-            v = p.get(n)
-            a = None if v is None else capi.f32(np.broadcast_to(np.asarray(v, np.float32).reshape(-1, sizes[n]), (B, sizes[n])))
-            args.append(a)
-        reg = None if regression_pose is None else capi.f32(
-            np.broadcast_to(np.asarray(regression_pose, np.float32).reshape(-1, self.nemb), (B, self.nemb)))
-        capi.check(self._lib.sfx_batch_set_params(self._h, *[capi.fptr(a) for a in args], capi.fptr(reg)))
+        args, reg = _pack_params(self._mode, self.B, self._sizes(), self.nemb, regression_pose, p)
+        self._call("set_params", *[self._mode.ptr(a) for a in args + [reg]])
 
     def get_params(self):
-        B = self.B
-        sizes = [3, 3, self.model.num_betas, self.model.num_pca, self.model.num_pca, self.model.num_expr,
-                 3, 3, 3, self.nemb, 63]
-        if self.float64:
-            outs = [np.zeros((B, n), np.float64) for n in sizes]
-            capi.check(self._lib.sfx_batch_get_params_f64(self._h, *[capi.dptr(a) for a in outs]))
-            return dict(zip(PARAM_NAMES + ("body_pose",), outs))
-        outs = [np.zeros((B, n), np.float32) for n in sizes]
-        capi.check(self._lib.sfx_batch_get_params(self._h, *[capi.fptr(a) for a in outs]))
-        d = dict(zip(PARAM_NAMES + ("body_pose",), outs))
-        return d
+        sizes = self._sizes()
+        outs = [np.zeros((self.B, n), self._mode.dtype) for n in [sizes[name] for name in PARAM_NAMES] + [63]]
+        self._call("get_params", *[self._mode.ptr(a) for a in outs])
+        return dict(zip(PARAM_NAMES + ("body_pose",), outs))
 
     # ---- compute ---------------------------------------------------------------------------
     def num_vars(self, stage):
@@ -615,15 +541,10 @@ class FrameBatch(object):
 
     def closure(self, stage):
         """(loss[B], grad[B,N]) at the current parameters; stage -1 = camera-init loss.  float64 on a float64 batch."""
-        N = self.num_vars(stage)
-        if self.float64:
-            loss = np.zeros(self.B, np.float64)
-            grad = np.zeros((self.B, N), np.float64)
-            capi.check(self._lib.sfx_batch_closure_f64(self._h, stage, capi.dptr(loss), capi.dptr(grad), None))
-            return loss, grad
-        loss = np.zeros(self.B, np.float32)
-        grad = np.zeros((self.B, N), np.float32)
-        capi.check(self._lib.sfx_batch_closure(self._h, stage, capi.fptr(loss), capi.fptr(grad), None))
+        m = self._mode
+        loss = np.zeros(self.B, m.dtype)
+        grad = np.zeros((self.B, self.num_vars(stage)), m.dtype)
+        self._call("closure", stage, m.ptr(loss), m.ptr(grad), None)
         return loss, grad
 
     def guess_init(self, pairs):
@@ -694,12 +615,8 @@ class FrameBatch(object):
 
     def last_grad(self, stage):
         """Gradient [B,N] of the most recent closure evaluation (what var.grad holds after step()); float64 on a float64 batch."""
-        if self.float64:
-            grad = np.zeros((self.B, self.num_vars(stage)), np.float64)
-            capi.check(self._lib.sfx_batch_get_grad_f64(self._h, stage, capi.dptr(grad)))
-            return grad
-        grad = np.zeros((self.B, self.num_vars(stage)), np.float32)
-        capi.check(self._lib.sfx_batch_get_grad(self._h, stage, capi.fptr(grad)))
+        grad = np.zeros((self.B, self.num_vars(stage)), self._mode.dtype)
+        self._call("get_grad", stage, self._mode.ptr(grad))
         return grad
 
     def trace(self, capacity, evaluations=False):
@@ -730,26 +647,14 @@ class FrameBatch(object):
     def forward(self, want_verts=True):
         """Final meshes/joints at the current parameters as torch CUDA tensors."""
         import torch
-        dev = torch.device("cuda", torch.cuda.current_device())
+        dev = _cuda(torch.cuda.current_device())
         verts = torch.empty([self.B, self.model.V, 3], dtype=torch.float32, device=dev) if want_verts else None
         joints = torch.empty([self.B, self.K, 3], dtype=torch.float32, device=dev)
-        capi.check(self._lib.sfx_batch_forward(self._h, C.c_void_p(verts.data_ptr()) if want_verts else None,
-                                               C.c_void_p(joints.data_ptr()), None))
+        capi.check(self._lib.sfx_batch_forward(self._h, A.ptr(verts), A.ptr(joints), None))
         return verts, joints
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.sfx_batch_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class BatchOptimizer(object):
+class BatchOptimizer(capi.Handle):
     """The engine's optimiser for losses the CALLER evaluates (sfx_opt_*, csrc/opt_ext.hip): B independent problems of N <= 192
     float32 variables, each with its own run_fitting / LBFGS.step / strong-Wolfe state on the device (one wavefront per problem,
     one evaluation of every running problem per launch).  Reverse communication over torch CUDA tensors:
@@ -765,7 +670,9 @@ class BatchOptimizer(object):
     history_size, tolerance_grad, tolerance_change (lbfgs_ls.LBFGS; defaults of oracle/lbfgs_machine.StageMachine, whose
     spellings history / tol_grad / tol_change are accepted too), reuse_entry_eval.  There is no CPU fallback."""
 
+    _destroy = "sfx_opt_destroy"
     _ALIASES = dict(history="history_size", tol_grad="tolerance_grad", tol_change="tolerance_change")
+    _STATE = "the optimiser's state"        # what lives on self.device, for the message that refuses a tensor elsewhere
 
     def __init__(self, B, N, groups=None, **hyper):
         h = dict(maxiters=30, ftol=1e-9, gtol=1e-9, lr=1.0, max_iter=None, max_eval=None, history_size=100,
@@ -794,29 +701,9 @@ class BatchOptimizer(object):
         import torch
         self._h, self._lib = hnd, lib
         self.B, self.N, self.hyper = int(B), int(N), h
-        self.device = torch.device("cuda", torch.cuda.current_device())      # where the state lives: every tensor of a call must be there
+        self.device = _cuda(torch.cuda.current_device())      # where the state lives: every tensor of a call must be there
         self.x_trial = None
         self._trace_cap = 0
-
-    def _tensor(self, name, t, shape):
-        import torch
-        if not torch.is_tensor(t):
-            raise TypeError("%s: a torch tensor is needed, got %s" % (name, type(t).__name__))
-        if t.device.type != "cuda":
-            raise ValueError("%s: a CUDA tensor is needed (no CPU fallback), got device %s" % (name, t.device))
-        if t.device != self.device:
-            raise ValueError("%s: on %s, the optimiser's state on %s" % (name, t.device, self.device))
-        if t.dtype != torch.float32:
-            raise ValueError("%s: float32 is needed, got %s" % (name, t.dtype))
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError("%s: shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
-        if not t.is_contiguous():
-            raise ValueError("%s: a contiguous tensor is needed (strides %s)" % (name, tuple(t.stride())))
-        return t.detach()
-
-    def _stream(self, stream):
-        import torch
-        return C.c_void_p(stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream)
 
     def begin(self, x0, mode="fit", resume=False, stream=None):
         """Start at x0 [B][N].  mode "fit": the whole run_fitting loop; "step": ONE LBFGS.step (resume=True continues the
@@ -825,11 +712,11 @@ class BatchOptimizer(object):
         import torch
         if mode not in ("fit", "step"):
             raise ValueError("mode: 'fit' or 'step', got %r" % (mode,))
-        x0 = self._tensor("x0", x0, (self.B, self.N))
+        x0 = A.tensor("x0", x0, (self.B, self.N), self.device, holder=self._STATE)
         if self.x_trial is None:
             self.x_trial = torch.empty((self.B, self.N), dtype=torch.float32, device=self.device)
-        capi.check(self._lib.sfx_opt_begin(self._h, 0 if mode == "fit" else 1, int(bool(resume)), C.c_void_p(x0.data_ptr()),
-                                           C.c_void_p(self.x_trial.data_ptr()), self._stream(stream)))
+        capi.check(self._lib.sfx_opt_begin(self._h, 0 if mode == "fit" else 1, int(bool(resume)), A.ptr(x0), A.ptr(self.x_trial),
+                                           A.stream(stream, self.device)))
         return self.x_trial
 
     def tell(self, loss, grad, stream=None):
@@ -837,15 +724,14 @@ class BatchOptimizer(object):
         ignore their entries, so calling this more often than needed is harmless."""
         if self.x_trial is None:
             raise RuntimeError("BatchOptimizer.tell before begin")
-        loss = self._tensor("loss", loss, (self.B,))
-        grad = self._tensor("grad", grad, (self.B, self.N))
-        capi.check(self._lib.sfx_opt_tell(self._h, C.c_void_p(loss.data_ptr()), C.c_void_p(grad.data_ptr()),
-                                          C.c_void_p(self.x_trial.data_ptr()), self._stream(stream)))
+        loss = A.tensor("loss", loss, (self.B,), self.device, holder=self._STATE)
+        grad = A.tensor("grad", grad, (self.B, self.N), self.device, holder=self._STATE)
+        capi.check(self._lib.sfx_opt_tell(self._h, A.ptr(loss), A.ptr(grad), A.ptr(self.x_trial), A.stream(stream, self.device)))
 
     def active(self, stream=None):
         """Problems still running.  Waits for the stream: the one host synchronisation of a loop."""
         n = C.c_int32(0)
-        capi.check(self._lib.sfx_opt_active(self._h, C.byref(n), self._stream(stream)))
+        capi.check(self._lib.sfx_opt_active(self._h, C.byref(n), A.stream(stream, self.device)))
         return int(n.value)
 
     def result(self):
@@ -857,8 +743,7 @@ class BatchOptimizer(object):
         res = np.zeros(self.B, np.float32)
         ev = np.zeros(self.B, np.int32)
         st = np.zeros(self.B, np.int32)
-        capi.check(self._lib.sfx_opt_get(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(g.data_ptr()), capi.fptr(res), capi.iptr(ev),
-                                         capi.iptr(st)))
+        capi.check(self._lib.sfx_opt_get(self._h, A.ptr(x), A.ptr(g), capi.fptr(res), capi.iptr(ev), capi.iptr(st)))
         return dict(x=x, grad=g, result=res, evals=ev, status=st)
 
     def trace(self, capacity):
@@ -877,17 +762,6 @@ class BatchOptimizer(object):
             raise RuntimeError("optimiser trace overflowed: %d records, capacity %d" % (cnt.max(), cap))
         return [rec[i, :cnt[i]].copy() for i in range(self.B)]
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.sfx_opt_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 # ---- the objective on tensors the caller supplies (sfx_objective_eval / sfx_camera_init_eval, csrc/objective_ext.hip) --------
 PRIOR_FORMS = dict(embedding=0, target=1, body_pose=2, mixture=3)      # SFX_PRIOR_*
@@ -899,26 +773,6 @@ OBJECTIVE_GRADS = ("joints", "rotation", "translation", "body_pose", "prior", "b
                    "left_hand_pose", "right_hand_pose")
 
 
-def _obj_in(name, t, shape, dev):
-    """One input of the stand-alone objective: a float32 contiguous CUDA tensor of `shape` on `dev` (None passes through)."""
-    import torch
-    if t is None:
-        return None
-    if not torch.is_tensor(t):
-        raise TypeError("%s: a torch tensor is needed, got %s" % (name, type(t).__name__))
-    if t.device.type != "cuda":
-        raise ValueError("%s: a CUDA tensor is needed (no CPU fallback), got device %s" % (name, t.device))
-    if dev is not None and t.device != dev:
-        raise ValueError("%s: on %s, joints on %s" % (name, t.device, dev))
-    if t.dtype != torch.float32:
-        raise ValueError("%s: float32 is needed, got %s" % (name, t.dtype))
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError("%s: shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
-    if not t.is_contiguous():
-        raise ValueError("%s: a contiguous tensor is needed (strides %s)" % (name, tuple(t.stride())))
-    return t.detach()
-
-
 def _obj_joints(joints):
     import torch
     if not torch.is_tensor(joints) or joints.dim() != 3 or joints.shape[2] != 3:
@@ -928,11 +782,7 @@ def _obj_joints(joints):
         raise ValueError("joints: at least one frame is needed, got B = %d" % B)
     if K < 1 or K > OBJECTIVE_MAX_K:
         raise ValueError("joints: K = %d keypoints, supported 1..%d" % (K, OBJECTIVE_MAX_K))
-    return B, K, _obj_in("joints", joints, (B, K, 3), None)
-
-
-def _obj_ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
+    return B, K, A.tensor("joints", joints, (B, K, 3))
 
 
 def objective_eval(joints, rotation, translation, focal_x, focal_y, center, gt_joints, joint_weights, body_pose, prior, betas,
@@ -951,6 +801,7 @@ def objective_eval(joints, rotation, translation, focal_x, focal_y, center, gt_j
     import torch
     B, K, joints = _obj_joints(joints)
     dev = joints.device
+    arg = functools.partial(A.tensor, device=dev, optional=True, holder="joints")      # every other tensor: where joints is
     if prior_form not in PRIOR_FORMS:
         raise ValueError("prior_form: one of %s, got %r" % (sorted(PRIOR_FORMS), prior_form))
     if not torch.is_tensor(prior) or prior.dim() != 2:
@@ -967,18 +818,18 @@ def objective_eval(joints, rotation, translation, focal_x, focal_y, center, gt_j
     if use_face and (expression is None or jaw_pose is None):
         raise ValueError("use_face needs expression and jaw_pose")
     ins = dict(joints=joints,
-               cam_rot=_obj_in("rotation", rotation, (B, 3, 3), dev), cam_t=_obj_in("translation", translation, (B, 3), dev),
-               focal_x=_obj_in("focal_x", focal_x, (B,), dev), focal_y=_obj_in("focal_y", focal_y, (B,), dev),
-               center=_obj_in("center", center, (B, 2), dev), gt_joints=_obj_in("gt_joints", gt_joints, (B, K, 2), dev),
-               joints_conf=_obj_in("joints_conf", joints_conf, (B, K), dev),
-               joint_weights=_obj_in("joint_weights", joint_weights, (B, K), dev),
-               body_pose=_obj_in("body_pose", body_pose, (B, 63), dev), prior=_obj_in("prior", prior, (B, n), dev),
-               prior_target=_obj_in("prior_target", prior_target, (B, n), dev) if prior_form == "target" else None,
-               betas=_obj_in("betas", betas, (B, nb), dev),
-               expression=_obj_in("expression", expression, (B, ne), dev) if use_face else None,
-               jaw=_obj_in("jaw_pose", jaw_pose, (B, 3), dev) if use_face else None,
-               lhand=_obj_in("left_hand_pose", left_hand_pose, (B, 45), dev) if use_hands else None,
-               rhand=_obj_in("right_hand_pose", right_hand_pose, (B, 45), dev) if use_hands else None)
+               cam_rot=arg("rotation", rotation, (B, 3, 3)), cam_t=arg("translation", translation, (B, 3)),
+               focal_x=arg("focal_x", focal_x, (B,)), focal_y=arg("focal_y", focal_y, (B,)),
+               center=arg("center", center, (B, 2)), gt_joints=arg("gt_joints", gt_joints, (B, K, 2)),
+               joints_conf=arg("joints_conf", joints_conf, (B, K)),
+               joint_weights=arg("joint_weights", joint_weights, (B, K)),
+               body_pose=arg("body_pose", body_pose, (B, 63)), prior=arg("prior", prior, (B, n)),
+               prior_target=arg("prior_target", prior_target, (B, n)) if prior_form == "target" else None,
+               betas=arg("betas", betas, (B, nb)),
+               expression=arg("expression", expression, (B, ne)) if use_face else None,
+               jaw=arg("jaw_pose", jaw_pose, (B, 3)) if use_face else None,
+               lhand=arg("left_hand_pose", left_hand_pose, (B, 45)) if use_hands else None,
+               rhand=arg("right_hand_pose", right_hand_pose, (B, 45)) if use_hands else None)
     c = capi.ObjectiveCfg()
     c.rho = float(rho)
     weights = weights or {}
@@ -1001,9 +852,9 @@ def objective_eval(joints, rotation, translation, focal_x, focal_y, center, gt_j
         M, D = int(mu.shape[0]), int(mu.shape[1])
         if D != 63 or n != 63:
             raise ValueError("the mixture prior acts on the 63 body-pose values: means [M, %d], operand [B, %d]" % (D, n))
-        keep = [_obj_in("mixture['means']", mu, (M, D), dev), _obj_in("mixture['precisions']", mixture["precisions"], (M, D, D), dev),
-                _obj_in("mixture['nll_weights']", mixture["nll_weights"], (M,), dev),
-                _obj_in("mixture['comp_const']", mixture.get("comp_const"), (M,), dev)]
+        keep = [arg("mixture['means']", mu, (M, D)), arg("mixture['precisions']", mixture["precisions"], (M, D, D)),
+                arg("mixture['nll_weights']", mixture["nll_weights"], (M,)),
+                arg("mixture['comp_const']", mixture.get("comp_const"), (M,))]
         c.gmm_M, c.gmm_D = M, D
         c.gmm_means_dev, c.gmm_precisions_dev, c.gmm_nll_weights_dev, c.gmm_comp_const_dev = [t.data_ptr() if t is not None else None for t in keep]
     a = capi.ObjectiveIn()
@@ -1021,9 +872,8 @@ def objective_eval(joints, rotation, translation, focal_x, focal_y, center, gt_j
             if like[name] is not None:
                 grads[name] = torch.empty_like(like[name])
                 setattr(g, "d_" + field + "_dev", grads[name].data_ptr())
-    s = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
     with torch.cuda.device(dev):
-        capi.check(capi.load().sfx_objective_eval(C.byref(c), C.byref(a), C.byref(g) if g is not None else None, _obj_ptr(loss), s))
+        capi.check(capi.load().sfx_objective_eval(C.byref(c), C.byref(a), C.byref(g) if g is not None else None, A.ptr(loss), A.stream(stream, dev)))
     return loss, grads
 
 
@@ -1036,23 +886,23 @@ def camera_init_eval(joints, rotation, translation, focal_x, focal_y, center, gt
     import torch
     B, K, joints = _obj_joints(joints)
     dev = joints.device
+    arg = functools.partial(A.tensor, device=dev, optional=True, holder="joints")      # every other tensor: where joints is
     if use_conf and joints_conf is None:
         raise ValueError("use_conf needs joints_conf")
-    ins = [joints, _obj_in("rotation", rotation, (B, 3, 3), dev), _obj_in("translation", translation, (B, 3), dev),
-           _obj_in("focal_x", focal_x, (B,), dev), _obj_in("focal_y", focal_y, (B,), dev), _obj_in("center", center, (B, 2), dev),
-           _obj_in("gt_joints", gt_joints, (B, K, 2), dev), _obj_in("init_count", init_count, (K,), dev),
-           _obj_in("joints_conf", joints_conf, (B, K), dev) if use_conf else None, _obj_in("est_tz", est_tz, (B,), dev)]
+    ins = [joints, arg("rotation", rotation, (B, 3, 3)), arg("translation", translation, (B, 3)),
+           arg("focal_x", focal_x, (B,)), arg("focal_y", focal_y, (B,)), arg("center", center, (B, 2)),
+           arg("gt_joints", gt_joints, (B, K, 2)), arg("init_count", init_count, (K,)),
+           arg("joints_conf", joints_conf, (B, K)) if use_conf else None, arg("est_tz", est_tz, (B,))]
     c = capi.CameraInitCfg()
     c.data_weight, c.depth_loss_weight, c.use_conf = float(data_weight), float(depth_loss_weight), int(bool(use_conf))
     loss = torch.empty([B], dtype=torch.float32, device=dev)
     grads = {}
     if want_grads:
         grads = dict(joints=torch.empty_like(ins[0]), rotation=torch.empty_like(ins[1]), translation=torch.empty_like(ins[2]))
-    s = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
     with torch.cuda.device(dev):
-        capi.check(capi.load().sfx_camera_init_eval(C.byref(c), B, K, *[_obj_ptr(t) for t in ins], _obj_ptr(loss),
-                                                    _obj_ptr(grads.get("joints")), _obj_ptr(grads.get("rotation")),
-                                                    _obj_ptr(grads.get("translation")), s))
+        capi.check(capi.load().sfx_camera_init_eval(C.byref(c), B, K, *[A.ptr(t) for t in ins], A.ptr(loss),
+                                                    A.ptr(grads.get("joints")), A.ptr(grads.get("rotation")),
+                                                    A.ptr(grads.get("translation")), A.stream(stream, dev)))
     return loss, grads
 
 
@@ -1129,30 +979,29 @@ def _read_pairs(call):
     return out[:int(n.value)].astype(np.int64)
 
 
-class Penetration(object):
+class Penetration(capi.Handle):
     """Interpenetration term on a batch of posed meshes (sfx_pen_*):
     BVH + FilterFaces + DistanceFieldPenetrationLoss of the reference's external package
     (fitting.py:437-455).  `segm` / `parents`: per-face part labels (smplx_parts_segm.pkl);
     `ign_part_pairs`: the cfg's ["9,16", ...] strings or (a, b) tuples."""
+    _destroy = "sfx_pen_destroy"
 
     def __init__(self, num_verts, faces, segm=None, parents=None, ign_part_pairs=None, max_collisions=128,
                  max_batch=1):
         self._lib = capi.load()
         faces = capi.i32(np.asarray(faces).astype(np.int64).reshape(-1, 3))
         self.V, self.F, self.max_batch = int(num_verts), int(faces.shape[0]), int(max_batch)
-        pairs = []
-        for p in ign_part_pairs or []:
-            a, b = (int(x) for x in str(p).split(",")) if isinstance(p, str) else p
-            pairs.append((a, b))
-        ign = capi.i32(np.asarray(pairs, np.int64).reshape(-1, 2))
+        ign = A.ign_pairs(ign_part_pairs)
         sg = capi.i32(segm) if segm is not None else None
         pr = capi.i32(parents) if parents is not None else None
         h = C.c_void_p()
-        capi.check(self._lib.sfx_pen_create(self.V, self.F, capi.iptr(faces), capi.iptr(sg) if sg is not None else None,
-                                            capi.iptr(pr) if pr is not None else None,
-                                            capi.iptr(ign) if len(pairs) else None, len(pairs), int(max_collisions),
+        capi.check(self._lib.sfx_pen_create(self.V, self.F, capi.iptr(faces), capi.iptr(sg), capi.iptr(pr),
+                                            capi.iptr(ign) if len(ign) else None, len(ign), int(max_collisions),
                                             self.max_batch, C.byref(h)))
         self._h = h
+
+    def _verts(self, verts):
+        return A.tensor("verts", verts, (None, self.V, 3), make_contiguous=True)
 
     def eval(self, verts, sigma, penalize_outside=True, stream=None, point2plane=False):
         """verts: float32 CUDA tensor [B, V, 3] -> (loss [B], d loss / d verts [B, V, 3]) on the GPU.
@@ -1160,15 +1009,13 @@ class Penetration(object):
         if point2plane:
             _warn_point2plane()
         import torch
+        v = self._verts(verts)
         capi.check(self._lib.sfx_pen_set_point2plane(self._h, int(bool(point2plane))))
-        assert verts.is_cuda and verts.dtype == torch.float32 and verts.shape[1:] == (self.V, 3)
-        v = verts.contiguous()
         B = v.shape[0]
         loss = torch.empty([B], dtype=torch.float32, device=v.device)
         dv = torch.empty_like(v)
-        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        capi.check(self._lib.sfx_pen_eval(self._h, B, C.c_void_p(v.data_ptr()), float(sigma), int(bool(penalize_outside)),
-                                          C.c_void_p(loss.data_ptr()), C.c_void_p(dv.data_ptr()), C.c_void_p(s)))
+        capi.check(self._lib.sfx_pen_eval(self._h, B, A.ptr(v), float(sigma), int(bool(penalize_outside)), A.ptr(loss), A.ptr(dv),
+                                          A.stream(stream)))
         return loss, dv
 
     def eval_pairs(self, verts, pairs, sigma, penalize_outside=True, point2plane=False, stream=None):
@@ -1178,18 +1025,15 @@ class Penetration(object):
         import torch
         if point2plane:
             _warn_point2plane()
-        capi.check(self._lib.sfx_pen_set_point2plane(self._h, int(bool(point2plane))))
-        assert verts.is_cuda and verts.dtype == torch.float32 and verts.shape[1:] == (self.V, 3)
-        assert pairs.is_cuda and pairs.dtype == torch.int32 and pairs.dim() == 3 and pairs.shape[2] == 2 and pairs.shape[0] == verts.shape[0]
-        v, pr = verts.contiguous(), pairs.contiguous()
+        v = self._verts(verts)
         B = v.shape[0]
+        pr = A.tensor("pairs", pairs, (B, None, 2), v.device, dtype=torch.int32, make_contiguous=True, holder="verts")
+        capi.check(self._lib.sfx_pen_set_point2plane(self._h, int(bool(point2plane))))
         loss = torch.empty([B], dtype=torch.float32, device=v.device)
         dv = torch.empty_like(v)
         dtri = torch.empty([B, self.F, 3, 3], dtype=torch.float32, device=v.device)
-        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        capi.check(self._lib.sfx_pen_eval_pairs(self._h, B, C.c_void_p(v.data_ptr()), C.c_void_p(pr.data_ptr()), int(pr.shape[1]), float(sigma),
-                                                int(bool(penalize_outside)), C.c_void_p(loss.data_ptr()), C.c_void_p(dv.data_ptr()),
-                                                C.c_void_p(dtri.data_ptr()), C.c_void_p(s)))
+        capi.check(self._lib.sfx_pen_eval_pairs(self._h, B, A.ptr(v), A.ptr(pr), int(pr.shape[1]), float(sigma),
+                                                int(bool(penalize_outside)), A.ptr(loss), A.ptr(dv), A.ptr(dtri), A.stream(stream)))
         return loss, dv, dtri
 
     def stats(self, B):
@@ -1210,14 +1054,3 @@ class Penetration(object):
         res = out / 100.0
         res[:, 10] = out[:, 10]
         return res
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.sfx_pen_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

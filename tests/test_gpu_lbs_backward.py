@@ -301,3 +301,35 @@ def test_memory_and_errors(gpu, synth_model):
     v1, j1, _ = dm.lbs_forward(*ins)
     assert torch.equal(v0, v1) and torch.equal(j0, j1)
     dm.close()
+
+
+def test_forward_refuses_what_backward_refuses(gpu, synth_model):
+    """lbs_forward hands the library nine pointers and B: a tensor of another width or batch is a ValueError naming it, as in
+    lbs_backward (one code path), not a read past its end.  What it always took still passes, with the same bits: any dtype,
+    body_pose as [B][21][3], inputs left out (None)."""
+    cfg = _cfg("body")
+    B = 2
+    P, _ = _inputs(B, 5, cfg["num_pca_comps"])
+    t = lambda a: torch.tensor(a, device=gpu)
+    dm = _dm(synth_model, cfg)
+    ins = [t(P[n]) for n in NAMES]
+    dj = torch.ones(B, dm.K, 3, device=gpu)
+    for i, name, bad in ((2, "betas", torch.zeros(B, dm.num_betas + 1, device=gpu)), (2, "betas", ins[2][:1]),
+                         (8, "right_hand_pose", torch.zeros(B, dm.num_pca - 1, device=gpu)), (4, "jaw_pose", torch.zeros(B, 1, 3, device=gpu)),
+                         (1, "body_pose", torch.zeros(B, 62, device=gpu))):
+        wrong = ins[:i] + [bad] + ins[i + 1:]
+        with pytest.raises(ValueError, match=name + ": shape"):
+            dm.lbs_forward(*wrong)
+        with pytest.raises(ValueError, match=name + ": shape"):
+            dm.lbs_backward(*wrong, djoints=dj)
+    with pytest.raises(ValueError, match="no CPU fallback"):
+        dm.lbs_forward(*[x.cpu() for x in ins])
+    v, j, fp = dm.lbs_forward(*ins)
+    assert torch.isfinite(v).all() and v.abs().max() > 0
+    v2, j2, fp2 = dm.lbs_forward(*[x.double() for x in ins[:1]], ins[1].reshape(B, 21, 3), *[x.double() for x in ins[2:]])
+    assert torch.equal(v, v2) and torch.equal(j, j2) and torch.equal(fp, fp2)
+    zeros = [torch.zeros_like(x) for x in ins]
+    vz, jz, _ = dm.lbs_forward(*ins[:3], *zeros[3:])
+    vn, jn, _ = dm.lbs_forward(*ins[:3], *[None] * 6)
+    assert torch.equal(vz, vn) and torch.equal(jz, jn)
+    dm.close()

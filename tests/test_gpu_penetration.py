@@ -127,6 +127,29 @@ def test_part_filter_and_separated_meshes():
     assert pen.stats(1)["pairs"][0] == 2 * len(pairs) > 0
 
 
+def test_mis_shaped_vertices_are_refused_before_any_launch():
+    """eval / eval_pairs hand the library a pointer and V: vertices of another count, another dtype or on the host are a
+    ValueError (a TypeError when no tensor at all), not a read past the buffer -- also under `python -O`, which is why these are
+    no asserts.  The checks come before the first call into the library, so nothing is launched here."""
+    verts, faces, segm, parents = _two_spheres(0.13)
+    V = len(verts)
+    pen = engine.Penetration(V, faces, segm, parents, max_collisions=64, max_batch=1)
+    good = torch.tensor(verts[None], dtype=torch.float32, device="cuda")
+    pairs = torch.zeros(1, 4, 2, dtype=torch.int32, device="cuda")
+    for bad, msg in ((good[:, :V - 1], "shape"), (good.double(), "float32"), (good.cpu(), "no CPU fallback"), (good[0], "shape")):
+        with pytest.raises(ValueError, match="verts.*" + msg):
+            pen.eval(bad, 0.5)
+        with pytest.raises(ValueError, match="verts.*" + msg):
+            pen.eval_pairs(bad, pairs, 0.5)
+    with pytest.raises(TypeError, match="verts"):
+        pen.eval(verts[None].astype(np.float32), 0.5)
+    for bad, msg in ((pairs.long(), "int32"), (pairs.cpu(), "no CPU fallback"), (pairs[:, :, :1], "shape"),
+                     (torch.zeros(2, 4, 2, dtype=torch.int32, device="cuda"), "shape")):
+        with pytest.raises(ValueError, match="pairs.*" + msg):
+            pen.eval_pairs(good, bad, 0.5)
+    pen.close()
+
+
 def test_max_collisions_cap_keeps_the_lowest_ids():
     """A triangle with more than max_collisions partners keeps the max_collisions LOWEST triangle ids -- a rule on ids,
     not on which pair a wavefront happened to find first --, a pair counts only if both triangles kept each other, and

@@ -208,6 +208,29 @@ def test_torch_surface(gpu):
     vp.close()
 
 
+def test_refused_outputs_and_devices(gpu):
+    """`out` is written through a raw pointer with B and the width the call works out: anything but a contiguous float32
+    tensor of exactly that shape is a ValueError.  The handle lives on one device: a latent elsewhere is refused, not
+    dereferenced."""
+    L, B = 12, 2
+    R = reference(L)
+    dec = decoder(L, gpu)
+    z, db = torch.tensor(R["z"][:B], device=gpu), torch.tensor(R["dbody"][:B], device=gpu)
+    for call, n in ((lambda out: dec.decode(z, out=out), 63), (lambda out: dec.decode_backward(z, db, out=out), L)):
+        for bad in (torch.empty(B, n - 1, device=gpu), torch.empty(B + 1, n, device=gpu), torch.empty(B * n, device=gpu),
+                    torch.empty(B, n, dtype=torch.float64, device=gpu), torch.empty(n, B, device=gpu).t(), torch.empty(B, n)):
+            with pytest.raises(ValueError, match="out: a contiguous float32"):
+                call(bad)
+        mine = torch.empty(B, n, device=gpu)
+        assert call(mine) is mine
+    assert dec.device_index == gpu.index
+    if torch.cuda.device_count() > 1:
+        with pytest.raises(ValueError, match="decoder's weights on cuda:0"):
+            dec.decode(z.to("cuda:1"))
+        with pytest.raises(ValueError, match="decoder's weights on cuda:0"):
+            dec.decode_backward(z.to("cuda:1"), db.to("cuda:1"))
+
+
 def test_agrees_with_the_in_loop_decoder(gpu, synth_model):
     """A use_vposer FrameBatch decodes its accepted latents with the closure workgroup (csrc/vposer.h, sfx_batch_get_params);
     the stand-alone decode of the same latents is another fp32 evaluation with another summation tree.  Each is within test
