@@ -48,7 +48,7 @@ struct ExtUpstream {
 // NULL the flat gradient / loss are ALSO left in LDS (gflat[NVAR_MAX], *fout) for a consumer in
 // the same workgroup (fused kernels).
 // Real = LDS::real_t: float, or double in the float64 mode (FrameLDSSmall64 with StageW64 weights; body-only needed-rows
-// path: the dense export, VPoser, the GMM prior and the interpenetration term are fp32-only and refused by api.hip).
+// path: the dense export, VPoser, the GMM prior and the interpenetration term are fp32-only and refused by host/batch.hip).
 template <class LDS, class SW, class EXT = NoUpstream>
 __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const BatchDev& D,
                                              const VarList* __restrict__ vls, const SW* __restrict__ sws,

@@ -1,4 +1,4 @@
-// column_pool.h -- host bookkeeping of the dense loop's column pool (continuous batching, cfg.slots; api.hip DenseLoop).
+// column_pool.h -- host bookkeeping of the dense loop's column pool (continuous batching, cfg.slots; host/fit_loop.hip DenseLoop).
 // `pool` GEMM columns; frames beyond the first `pool` wait in a queue (column -1, not in the running list) and take over the
 // column of a frame that has finished.  Frames are independent and a column's arithmetic does not depend on its index: results
 // equal those of a batch with one column per frame.  Host only, no device call: tests/column_pool_check.cpp walks it alone.

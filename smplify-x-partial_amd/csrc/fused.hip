@@ -45,7 +45,7 @@ void k_fit_rows(DevModel M, BatchDev D, const VarList* __restrict__ vls, const S
 // (small variant, OCC = 2: two workgroups per CU -- batches of more than 256 frames then run two latency-bound frames per
 //  CU; OCC = 1 is the same code with the whole register file, launched when every frame has a CU of its own: no spills,
 //  73.8 instead of 76.2 us per launch)
-// The overlapped loop (api.hip run_ticks) rotates three sets of GEMM operand buffers: the export pass writes featR_w / AT_w while
+// The overlapped loop (host/fit_loop.hip DenseLoop) rotates three sets of GEMM operand buffers: the export pass writes featR_w / AT_w while
 // GEMMs in flight read featR / AT (the operands of the latest evaluation) and the third set.  A frame that has finished exports
 // no more, so its column would go on cycling through the operands of its last three evaluations and D.verts would end on any
 // of their meshes.  Its workgroup therefore copies the column from the set of the latest evaluation into the one that is

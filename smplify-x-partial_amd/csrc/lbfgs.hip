@@ -25,7 +25,7 @@ __global__ __launch_bounds__(64)
 void k_debug_two_loop(OptState* gst, float* hist, const float* S_in, const float* Y_in, int cnt, int hist_cap, const float* g_in, float* d_out) {
     __shared__ float s_al[SFX_HIST_MAX + 2 * LB_BS];
     const int lane = threadIdx.x;
-    const int R = hist_cap > SFX_HIST ? hist_cap : SFX_HIST, hrows = R + 8;      // (the ring api.hip gives a batch of that history_size)
+    const int R = hist_cap > SFX_HIST ? hist_cap : SFX_HIST, hrows = R + 8;      // (the ring host/batch.hip gives a batch of that history_size)
     float* hY = hist; float* hS = hY + (size_t)hrows * SFX_NVAR_MAX;
     for (int i = lane; i < hrows * LB_BROW; i += 64) { gst->syb[i] = 0.f; gst->syt[i] = 0.f; }
     LB_SYNC();

@@ -1,5 +1,5 @@
 // model_tables.h -- every derived constant table of a model, built from its descriptor on the host: no HIP call, no device
-// memory.  sfx_model_create (api.hip) uploads the result; tests/model_tables_check.cpp checks it on the CPU.  The arrays a model
+// memory.  sfx_model_create (host/model.hip) uploads the result; tests/model_tables_check.cpp checks it on the CPU.  The arrays a model
 // takes over unchanged (v_template, lbs_weights, hand components, pose_mean) are uploaded straight from the descriptor.
 #pragma once
 #include "../../include/sfx.h"

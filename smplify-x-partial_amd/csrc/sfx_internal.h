@@ -1,4 +1,4 @@
-// Internal structures shared by the host layer (api.hip) and the gfx950 kernels.
+// Internal structures shared by the host layer (host/) and the gfx950 kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -59,7 +59,7 @@
 #define SFX_META_N 1632
 
 // Per-frame record (floats): keypoints, confidences, joint weights, camera-init mask, camera, camera rotation, regression
-// pose -- packed by k_pack_fd (api.hip) from the arrays the host fills, read by the closure workgroup in ONE 16-byte copy
+// pose -- packed by k_pack_fd (host/batch.hip) from the arrays the host fills, read by the closure workgroup in ONE 16-byte copy
 #define FD_GT 0
 #define FD_CONF (2 * SFX_MAX_K)
 #define FD_JW (3 * SFX_MAX_K)
@@ -260,7 +260,7 @@ struct BatchDev {
     double* f64;            // [B]
     double* g64;            // [B][NVAR_MAX]
     double* cam64;          // [B][8]
-    // where the export pass WRITES the GEMM operands.  Everywhere but in the overlapped dense loop (api.hip run_ticks) these are
+    // where the export pass WRITES the GEMM operands.  Everywhere but in the overlapped dense loop (host/fit_loop.hip DenseLoop) these are
     // featR / AT themselves; there the rest-tile GEMM of evaluation i still reads featR / AT while the tick kernel exports
     // evaluation i + 1, so the export goes to another set of buffers and the host rotates the sets after every tick launch
     float* featR_w;         // [Bpad][KD_PAD]

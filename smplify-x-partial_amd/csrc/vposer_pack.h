@@ -1,4 +1,4 @@
-// vposer_pack.h -- host side of the VPoser-v1 decoder weights, shared by sfx_model_set_vposer (api.hip: the in-loop decoder of
+// vposer_pack.h -- host side of the VPoser-v1 decoder weights, shared by sfx_model_set_vposer (host/model.hip: the in-loop decoder of
 // vposer.h) and sfx_vposer_create (vposer_batch.hip: the stand-alone operator): the one shape refusal and the transposed,
 // padded copies the forward products stream ([in][out]).  Below them the encoder's side (sfx_vposer_encoder_create,
 // vposer_encode.hip): its refusals, the batch norms folded into the linear layers, both orientations of every matrix.

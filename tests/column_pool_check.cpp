@@ -1,5 +1,5 @@
 // CPU check of the dense loop's column pool (csrc/column_pool.h) on scripted stage-flag snapshots: B frames through `pool`
-// columns, driven as csrc/api.hip DenseLoop::poll drives it (retire, then admission / compaction by slice_emptied / nothing),
+// columns, driven as csrc/host/fit_loop.hip DenseLoop::poll drives it (retire, then admission / compaction by slice_emptied / nothing),
 // with snapshots that lag behind the admissions as the polled loop's do.  After every poll: the frame -> column map and the
 // running list against what the poll's retirements dictate; and the compaction rule's table.  Stand-alone: own main, no
 // device.  Built and run by tests/test_column_pool_host.py (host AddressSanitizer + UBSan).

@@ -1,5 +1,5 @@
 """CPU test of the dense loop's column pool (csrc/column_pool.h): compiles tests/column_pool_check.cpp -- a stand-alone program
-that drives the pool with scripted stage-flag snapshots as csrc/api.hip DenseLoop::poll does (5 frames through 2 columns, 32
+that drives the pool with scripted stage-flag snapshots as csrc/host/fit_loop.hip DenseLoop::poll does (5 frames through 2 columns, 32
 resident, 70 / 32, 48 / 32, 40 / 16, a random finishing order at 200 / 64) and checks map, running list, admission order and
 the compaction rule after every poll -- for the host only, with AddressSanitizer and UBSan, and runs it.  No GPU needed."""
 import os

@@ -1,5 +1,5 @@
 """The overlapped dense loop (run with -m gpu): the GEMM's key tiles in front of the tick kernel, every other tile beside it on a
-second stream, three sets of operand buffers (csrc/api.hip DenseLoop::round_key_rest).  Nobody's arithmetic changes, so every comparison here
+second stream, three sets of operand buffers (csrc/host/fit_loop.hip DenseLoop::round_key_rest).  Nobody's arithmetic changes, so every comparison here
 is bit for bit: against the serial whole-grid loop (lab build, SFX_DENSE_OVERLAP=0), against the same frame fitted alone,
 against the same job resident instead of pooled, and against itself run twice."""
 import numpy as np

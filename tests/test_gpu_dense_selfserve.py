@@ -1,4 +1,4 @@
-"""Self-served blend offsets in the dense loop (run with -m gpu).  In rounds of the third form (csrc/api.hip DenseLoop::round_self) the tick
+"""Self-served blend offsets in the dense loop (run with -m gpu).  In rounds of the third form (csrc/host/fit_loop.hip DenseLoop::round_self) the tick
 workgroup no longer reads the blend offsets of its keypoint vertices from the dense GEMM's export (BatchDev.uvp): it forms them
 itself from its operand row with the GEMM's own chain of fp32 operations (csrc/closure_lds.h self_blend_offsets), and the whole
 GEMM of every evaluation runs beside the tick chain.  Nobody's arithmetic changes, so every comparison here is bit for bit:

@@ -332,7 +332,7 @@ def test_blocked_two_loop_matches_the_sequential_recursion(count):
                                            (407, 400), (408, 400), (801, 400), (60, 37), (101, 101)])
 def test_blocked_two_loop_with_a_history_size_other_than_100(count, history):
     """LBFGS(history_size=...) (lbfgs_ls.py:200,271,325 takes any; refused beyond 100 until round 5): a history_size above 100
-    gets a ring of that many slots (api.hip hist_ring) -- window, wrap and mirror rows at every offset against the sequential
+    gets a ring of that many slots (host/batch.hip hist_ring) -- window, wrap and mirror rows at every offset against the sequential
     recursion in fp64 over the LAST history_size pairs; below 100 the window is shorter than the ring's 100 slots."""
     import ctypes as C
     from smplifyx_amd import _capi
