@@ -466,6 +466,51 @@ int  sfx_camera_init_eval(const sfx_camera_init_cfg* cfg, int32_t B, int32_t K,
                           const float* est_tz_dev /* or NULL */, float* loss_dev, float* d_joints_dev /* [B][K][3] or NULL */,
                           float* d_cam_rot_dev /* [B][3][3] or NULL */, float* d_cam_t_dev /* [B][3] or NULL */, void* stream);
 
+/* ---- evaluation of fitted meshes on the device (csrc/evaluate.hip) -----------------------------------------------------
+ * Both entries are stateless like the two above: device pointers, sizes, a stream; no handle, no allocation, no
+ * synchronisation.  B == 0 returns 0 before any pointer is looked at.  A refusal returns -1, sets the error text and
+ * launches nothing.  Masks are uint8 [B][points] or NULL (every point valid); 0 takes the point out.
+ *
+ * Alignment and per-point error of B estimated point sets against their ground truth: ProcrustesAlignment
+ * (smplifyx/utils.py:540-595), mpjpe / vertex_to_vertex_error (utils.py:597-614), PelvisAlignment (utils.py:650-668) and
+ * ScaleAlignment (utils.py:729-772).
+ *   est_dev, gt_dev   [B][N][3] float32
+ *   mask_dev          a masked point is left out of every sum of its mesh and its error is exactly 0 (the reference's protocol
+ *                     scores another vertex subset in every frame, eval.py:102-121)
+ *   anchors           HOST int32 [n_anchors], 1 <= n_anchors <= SFX_ALIGN_MAX_ANCHORS, read by SFX_ALIGN_PELVIS only (NULL
+ *                     otherwise): rows whose mean each set is moved by (the hip joints 2, 3 of the reference).  Read during
+ *                     the call; an anchor outside 0 .. N-1 is refused.  Anchor rows are read whether masked or not.
+ *   err_dev           [B][N] float32: Euclidean distance after alignment
+ *   mean_dev          [B] or NULL: mean of err over the valid points (no valid point: NaN, the errors all 0)
+ *   xform_dev         [B][13] float32 or NULL: scale, R row-major, t of the map  p -> scale R p + t  applied to the estimate.
+ *                     NONE: 1, I, 0.  SCALE: R = I.  PELVIS: 1, I, t = -(mean of the estimate's anchor rows); the ground truth is
+ *                     moved by the mean of its own anchor rows, which is not part of xform.
+ * Centroids, the cross-covariance K = X1 X2^T, var1 and var2 are float64 sums over centred points (two passes) in a fixed
+ * order without atomics; the 3x3 solve (csrc/procrustes3.h: R = V Z U^T with det R = +1, utils.py:575-581) and the
+ * application of the transform are float64, only the stored values are rounded to float32.  A mesh's bits depend on its own
+ * points only.  Where the reference divides by zero (one valid point, var1 = 0) the result is non-finite as the reference's. */
+enum { SFX_ALIGN_NONE = 0, SFX_ALIGN_PROCRUSTES = 1, SFX_ALIGN_SCALE = 2, SFX_ALIGN_PELVIS = 3 };
+#define SFX_ALIGN_MAX_ANCHORS 8
+int  sfx_eval_align(int32_t mode, int32_t B, int32_t N, const float* est_dev, const float* gt_dev,
+                    const unsigned char* mask_dev, const int32_t* anchors /* HOST */, int32_t n_anchors,
+                    float* err_dev, float* mean_dev, float* xform_dev, void* stream);
+
+/* The two nearest-neighbour queries of point_fscore (smplifyx/utils.py:622-648; the reference asks open3d) for B pairs of
+ * point sets: for every valid point of a the distance to the nearest valid point of b, and the same for b against a.
+ *   a_dev [B][Na][3], b_dev [B][Nb][3] float32; mask_a_dev [B][Na], mask_b_dev [B][Nb]
+ *   thresh            HOST double [n_thresh], n_thresh <= SFX_NEAREST_MAX_THRESH (read during the call)
+ *   dist_ab_dev [B][Na], dist_ba_dev [B][Nb]   float32 or NULL; 0 at masked points
+ *   count_ab_dev, count_ba_dev [B][n_thresh]   int32: valid points whose distance is < thresh[t] (required when n_thresh > 0)
+ *   valid_dev [B][2]                           int32 or NULL: valid points of a and of b
+ * precision = count_ba / valid[1], recall = count_ab / valid[0] with a = the prediction (utils.py:633-636).
+ * Brute force: squared distances from coordinate differences in float32.  A set with no valid point gives distances 0 and
+ * counts 0 in both directions.  The counts are integers and do not depend on the order of the work.                      */
+#define SFX_NEAREST_MAX_THRESH 8
+int  sfx_eval_nearest(int32_t B, int32_t Na, int32_t Nb, const float* a_dev, const float* b_dev,
+                      const unsigned char* mask_a_dev, const unsigned char* mask_b_dev,
+                      int32_t n_thresh, const double* thresh /* HOST */, float* dist_ab_dev, float* dist_ba_dev,
+                      int32_t* count_ab_dev, int32_t* count_ba_dev, int32_t* valid_dev, void* stream);
+
 /* Gaussian-mixture body pose prior (MaxMixturePrior, smplifyx/prior.py:100-231; body_prior_type 'gmm'):
  * used by the closure when use_vposer is off and the batch has no regression pose (fitting.py:399-401).
  * means [M][D], precisions [M][D][D], nll_weights [M] = the module's buffers; D = 63, M <= 8 (HOST). */

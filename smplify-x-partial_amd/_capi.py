@@ -168,6 +168,10 @@ SYMBOLS = {
     "sfx_objective_eval": (C.c_int, [C.POINTER(ObjectiveCfg), C.POINTER(ObjectiveIn), C.POINTER(ObjectiveGrads), C.c_void_p, C.c_void_p]),
     # cfg, B, K, joints, rotation, translation, focal x / y, center, gt, init_count, conf, est_tz, loss, three gradients, stream
     "sfx_camera_init_eval": (C.c_int, [C.POINTER(CameraInitCfg), C.c_int32, C.c_int32] + [C.c_void_p] * 14 + [C.c_void_p]),
+    # mode, B, N, est, gt, mask, anchors (host), n_anchors, err, mean, xform, stream
+    "sfx_eval_align": (C.c_int, [C.c_int32] * 3 + [C.c_void_p] * 3 + [i32p, C.c_int32] + [C.c_void_p] * 3 + [C.c_void_p]),
+    # B, Na, Nb, a, b, mask_a, mask_b, n_thresh, thresh (host), dist_ab, dist_ba, count_ab, count_ba, valid, stream
+    "sfx_eval_nearest": (C.c_int, [C.c_int32] * 3 + [C.c_void_p] * 4 + [C.c_int32, f64p] + [C.c_void_p] * 5 + [C.c_void_p]),
     "sfx_pen_create": (C.c_int, [C.c_int32, C.c_int32, i32p, i32p, i32p, i32p, C.c_int32, C.c_int32, C.c_int32,
                                  C.POINTER(C.c_void_p)]),
     "sfx_pen_destroy": (None, [C.c_void_p]),

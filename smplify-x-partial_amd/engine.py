@@ -906,6 +906,116 @@ def camera_init_eval(joints, rotation, translation, focal_x, focal_y, center, gt
     return loss, grads
 
 
+# ---- evaluation of fitted meshes (sfx_eval_align / sfx_eval_nearest, csrc/evaluate.hip) -------------------------------------
+ALIGN_MODES = dict(none=0, procrustes=1, scale=2, pelvis=3)            # SFX_ALIGN_*
+ALIGN_MAX_ANCHORS = 8                                                   # SFX_ALIGN_MAX_ANCHORS
+NEAREST_MAX_THRESH = 8                                                  # SFX_NEAREST_MAX_THRESH
+
+
+def _points(name, t):
+    """(B, N) of a [B, N, 3] tensor; what it is and where it lives is left to A.tensor."""
+    import torch
+    if not torch.is_tensor(t):
+        raise TypeError("%s: a torch tensor is needed, got %s" % (name, type(t).__name__))
+    if t.dim() != 3 or t.shape[2] != 3 or t.shape[1] < 1:
+        raise ValueError("%s: shape %s, expected (B, N, 3) with N >= 1" % (name, tuple(t.shape)))
+    return int(t.shape[0]), int(t.shape[1])
+
+
+def _expect_shape(name, t, shape):
+    """The shape (and, for a mask, the dtype) of a further argument, checked before where ANY argument lives: A.tensor
+    checks one tensor at a time, what it is before where it is."""
+    import torch
+    if t is None:
+        return
+    if not torch.is_tensor(t):
+        raise TypeError("%s: a torch tensor is needed, got %s" % (name, type(t).__name__))
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError("%s: shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
+    if len(shape) == 2 and t.dtype not in (torch.bool, torch.uint8):
+        raise ValueError("%s: torch.bool or torch.uint8 is needed, got %s" % (name, t.dtype))
+
+
+def _point_mask(name, mask, shape, dev, holder):
+    import torch
+    return A.tensor(name, mask, shape, device=dev, dtype=torch.uint8, optional=True, convert=True, holder=holder)
+
+
+def align_errors(est, gt, mode="procrustes", mask=None, anchors=(2, 3), return_transform=False, stream=None):
+    """Per-point error of B estimated point sets against their ground truth after an alignment (sfx_eval_align):
+    mode 'none' (mpjpe / vertex_to_vertex_error, utils.py:597-614), 'procrustes' (ProcrustesAlignment, utils.py:540-595),
+    'scale' (ScaleAlignment, utils.py:729-772) or 'pelvis' (PelvisAlignment, utils.py:650-668: each set moved by the mean of
+    its own rows `anchors`).  est, gt: float32 contiguous CUDA tensors [B, N, 3]; mask: [B, N] torch.bool / torch.uint8 or
+    None -- a masked point is left out of every sum and its error is exactly 0.
+    Returns (err [B, N], mean [B]: the mean over the valid points), and xform [B, 13] (scale, R row-major, t of the map
+    applied to the estimate; include/sfx.h) as a third value with return_transform.  Only enqueues on the current (or the
+    given) stream."""
+    import torch
+    if mode not in ALIGN_MODES:
+        raise ValueError("mode: one of %s, got %r" % (sorted(ALIGN_MODES), mode))
+    B, N = _points("est", est)
+    anc = None
+    if mode == "pelvis":
+        anc = capi.i32(list(anchors)).reshape(-1)
+        if not 1 <= anc.size <= ALIGN_MAX_ANCHORS:
+            raise ValueError("anchors: %d given, supported 1..%d" % (anc.size, ALIGN_MAX_ANCHORS))
+        if anc.min() < 0 or anc.max() >= N:
+            raise ValueError("anchors: %s outside the %d points" % (anc.tolist(), N))
+    _expect_shape("gt", gt, (B, N, 3))
+    _expect_shape("mask", mask, (B, N))
+    est = A.tensor("est", est, (B, N, 3))
+    dev = est.device
+    gt = A.tensor("gt", gt, (B, N, 3), device=dev, holder="est")
+    mask = _point_mask("mask", mask, (B, N), dev, "est")
+    err = torch.empty([B, N], dtype=torch.float32, device=dev)
+    mean = torch.empty([B], dtype=torch.float32, device=dev)
+    xform = torch.empty([B, 13], dtype=torch.float32, device=dev) if return_transform else None
+    if B > 0:
+        with torch.cuda.device(dev):
+            capi.check(capi.load().sfx_eval_align(ALIGN_MODES[mode], B, N, A.ptr(est), A.ptr(gt), A.ptr(mask), capi.iptr(anc),
+                                                  0 if anc is None else anc.size, A.ptr(err), A.ptr(mean), A.ptr(xform),
+                                                  A.stream(stream, dev)))
+    return (err, mean, xform) if return_transform else (err, mean)
+
+
+def nearest_distances(a, b, thresholds=(), mask_a=None, mask_b=None, return_distances=True, stream=None):
+    """The two nearest-neighbour queries of point_fscore (utils.py:622-648) for B pairs of point sets (sfx_eval_nearest):
+    a [B, Na, 3], b [B, Nb, 3] float32 contiguous CUDA tensors, masks [B, Na] / [B, Nb] torch.bool / torch.uint8 or None;
+    thresholds: up to 8 distances.  Returns a dict of tensors on the device:
+      dist_ab [B, Na], dist_ba [B, Nb]     distance of every valid point to the nearest valid point of the other set, 0 at
+                                           masked points (with return_distances)
+      count_ab, count_ba [B, n_thresh]     int32: valid points nearer than each threshold
+      valid [B, 2]                         int32: valid points of a and of b
+    A set with no valid point gives distances 0 and counts 0.  Only enqueues on the current (or the given) stream."""
+    import torch
+    B, Na = _points("a", a)
+    Nb = _points("b", b)[1]
+    th = capi.f64(list(thresholds)).reshape(-1)
+    if th.size > NEAREST_MAX_THRESH:
+        raise ValueError("thresholds: %d given, at most %d" % (th.size, NEAREST_MAX_THRESH))
+    _expect_shape("b", b, (B, Nb, 3))
+    _expect_shape("mask_a", mask_a, (B, Na))
+    _expect_shape("mask_b", mask_b, (B, Nb))
+    a = A.tensor("a", a, (B, Na, 3))
+    dev = a.device
+    b = A.tensor("b", b, (B, Nb, 3), device=dev, holder="a")
+    mask_a = _point_mask("mask_a", mask_a, (B, Na), dev, "a")
+    mask_b = _point_mask("mask_b", mask_b, (B, Nb), dev, "a")
+    out = dict(count_ab=torch.empty([B, th.size], dtype=torch.int32, device=dev),           # (zeroed by the library)
+               count_ba=torch.empty([B, th.size], dtype=torch.int32, device=dev),
+               valid=torch.empty([B, 2], dtype=torch.int32, device=dev))
+    if return_distances:
+        out["dist_ab"] = torch.empty([B, Na], dtype=torch.float32, device=dev)
+        out["dist_ba"] = torch.empty([B, Nb], dtype=torch.float32, device=dev)
+    if B > 0:
+        with torch.cuda.device(dev):
+            capi.check(capi.load().sfx_eval_nearest(B, Na, Nb, A.ptr(a), A.ptr(b), A.ptr(mask_a), A.ptr(mask_b), th.size,
+                                                    capi.dptr(th), A.ptr(out.get("dist_ab")), A.ptr(out.get("dist_ba")),
+                                                    A.ptr(out["count_ab"]), A.ptr(out["count_ba"]), A.ptr(out["valid"]),
+                                                    A.stream(stream, dev)))
+    return out
+
+
 def prof_enable(on=True, every=1):
     """HIP-event timing of the named kernel launches; `every` = N times only every N-th launch of
     each name (an event pair costs two queue packets per launch)."""
