@@ -246,6 +246,9 @@ typedef struct sfx_batch_cfg {
                                        sfx_pen_set_point2plane                                                     */
 } sfx_batch_cfg;
 
+/* Device memory of note: a dense batch without the interpenetration term keeps several sets of GEMM operand buffers for its
+ * overlapped fitting loop, 4.7 KB per frame and set -- three sets in all; seventeen (21 MB at 256 frames, 82 MB at 1 024) where the
+ * multi-round form of the loop can run: body-only keypoints without the VPoser decoder.                                     */
 int  sfx_batch_create(sfx_model* m, const sfx_batch_cfg* cfg,
                       const sfx_stage_weights* stages /* [n_stages] */, sfx_batch** out);
 /* Releases everything the batch owns, EXCEPT the collision buffers of a batch with interpenetration = 1 (about 45 MB per GEMM

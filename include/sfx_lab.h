@@ -18,7 +18,13 @@
  *   SFX_DENSE_OVERLAP=0      the serial dense loop: one whole-grid GEMM in front of every tick launch, one stream
  *   SFX_OVERLAP_SERIAL=n     the overlapped dense loop's rule: rounds at <= n active columns stay serial, whichever overlapped form
  *                            is selected (default: 160 for the key / rest form; SFX_OV_SELF_SERIAL for the self-served one)
- *   SFX_DENSE_SELF=0         no self-served rounds: the key / rest form wherever the loop overlaps
+ *                            = 0: every round a self-served single launch down to one column (no multi-round launches either)
+ *   SFX_DENSE_MULTI=0        no multi-round tick launches: serial rounds below the self-served band, as before the form existed
+ *   SFX_DENSE_MULTI_MAX=n    multi-round launches at <= n active columns (default SFX_OV_MULTI_MAX = 96; with SFX_OVERLAP_SERIAL
+ *                            given, that value); the form comes before the self-served and key / rest forms up to n
+ *   SFX_DENSE_MULTI_R=n      rounds per multi-round launch, 1 .. 8 (default 8; never more than half the rounds a finished frame
+ *                            stays listed for, csrc/operand_ring.h rounds_per_launch)
+ *   SFX_DENSE_SELF=0         no self-served rounds: the key / rest form wherever the loop overlaps (and no multi-round launches)
  *   SFX_DENSE_SELF_MAX=n     self-served rounds at <= n active columns only (default SFX_OV_SELF_MAX); above, the key / rest rule
  *   SFX_DENSE_SELF_SERIAL=1  serial rounds launch the tick kernel with self-served blend offsets too (its cost per launch, alone)
  *   SFX_DEBUG_NACT, SFX_DEBUG_HOST        loop diagnostics on stderr
@@ -62,7 +68,9 @@ int  sfx_debug_pen_phase_ticks(int64_t* ticks_host);
  * and detach (enable=0): out[0..18] = closure phase stamps of the last launch, out[32+i] =
  * shader-clock cycles frame 0 spent between optimiser-tick marks i-1 and i, out[63] = ticks.
  * enable = N > 1: the stamps of the dense tick kernel freeze after its N-th launch (default 40),
- * out[24..26] = its start / end of adjoint+tick / end, out[40..56] = phases of its adjoint pass.  */
+ * out[24..26] = its start / end of adjoint+tick / end, out[40..56] = phases of its adjoint pass.
+ * A multi-round launch (k_tick_dense_multi) counts as one launch and stamps its round 0; the per-workgroup
+ * duration statistics (out[29], [30], [58..60]) cover single-round launches only (SFX_DENSE_MULTI=0: all).  */
 int  sfx_debug_clocks(sfx_batch* b, int32_t enable, int64_t* out /* [64] or NULL */);
 
 #ifdef __cplusplus

@@ -44,22 +44,39 @@ struct ExtUpstream {
     float* gc;              // [B][SFX_NPAR_MAX] out: gradient with respect to the parameter block
 };
 
+// Which GEMM operand buffers an evaluation touches.  OwnOperands (the default): BatchDev's -- featR read by self_blend_offsets,
+// featR_w / AT_w written by the export pass.  OperandSets: the caller names them per call (k_tick_dense_multi, whose rounds
+// walk a ring of sets; BatchDev itself stays the untouched kernel argument, so its members stay scalar loads).
+struct OwnOperands {
+    __device__ __forceinline__ int tid() const { return threadIdx.x; }
+    __device__ __forceinline__ const float* featR(const BatchDev& D) const { return D.featR; }
+    __device__ __forceinline__ float* featR_w(const BatchDev& D) const { return D.featR_w; }
+    __device__ __forceinline__ float* AT_w(const BatchDev& D) const { return D.AT_w; }
+};
+struct OperandSets {
+    const float* r; float* fw; float* aw; int t;      // t: the caller's thread index (a loop over rounds passes one the compiler cannot hoist address arithmetic on)
+    __device__ __forceinline__ int tid() const { return t; }
+    __device__ __forceinline__ const float* featR(const BatchDev&) const { return r; }
+    __device__ __forceinline__ float* featR_w(const BatchDev&) const { return fw; }
+    __device__ __forceinline__ float* AT_w(const BatchDev&) const { return aw; }
+};
+
 // One closure evaluation of frame b by the whole workgroup (CT threads).  When `gflat` is not
 // NULL the flat gradient / loss are ALSO left in LDS (gflat[NVAR_MAX], *fout) for a consumer in
 // the same workgroup (fused kernels).
 // Real = LDS::real_t: float, or double in the float64 mode (FrameLDSSmall64 with StageW64 weights; body-only needed-rows
 // path: the dense export, VPoser, the GMM prior and the interpenetration term are fp32-only and refused by host/batch.hip).
-template <class LDS, class SW, class EXT = NoUpstream>
+template <class LDS, class SW, class EXT = NoUpstream, class OPS = OwnOperands>
 __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const BatchDev& D,
                                              const VarList* __restrict__ vls, const SW* __restrict__ sws,
                                              const ClosureArgs& args, const int b, typename LDS::real_t* gflat,
-                                             typename LDS::real_t* fout, const EXT& ext = EXT{}) {
+                                             typename LDS::real_t* fout, const EXT& ext = EXT{}, const OPS ops = OPS{}) {
     using Real = typename LDS::real_t;
     constexpr bool F64 = std::is_same<Real, double>::value;
     constexpr bool kExt = !std::is_same<EXT, NoUpstream>::value;
     static_assert(!kExt || !F64, "the external-upstream sweep is fp32");
     constexpr int CT = LDS::kThreads;
-    const int t = threadIdx.x;
+    const int t = ops.tid();
     const int lane = t & 63, wv = t >> 6;
     const ParLayout& L = D.L;
     const BatchCfgDev& C = D.cfg;
@@ -135,7 +152,7 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
     // operand row, behind the entry's requests and in front of their wait -- into S.dvert, which nobody touches before the
     // reverse sweep ("needed vertices" below picks them up)
     if constexpr (!F64) {
-        if (self_uvp) self_blend_offsets(M.uniq_dirs, M.n_uniq, D.featR + (size_t)args.self_col * SFX_KD_PAD, S.dvert, wv, CT / 64, lane);
+        if (self_uvp) self_blend_offsets(M.uniq_dirs, M.n_uniq, ops.featR(D) + (size_t)args.self_col * SFX_KD_PAD, S.dvert, wv, CT / 64, lane);
     }
     lds_dma_wait();
     __syncthreads();
@@ -295,11 +312,11 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
         // coefficients of this frame: one contiguous 2-KiB row (entries >= KD are zero).  (As a COLUMN of a [K][frames]
         // matrix -- what the GEMM's A operand looks like in LDS -- these were 506 scattered 4-byte writes per frame into
         // lines shared by 32 frames: 10 k cycles of the launch; the GEMM transposes while staging instead.)
-        if (t < SFX_KD_PAD / 4) reinterpret_cast<float4*>(D.featR_w + (size_t)slot * SFX_KD_PAD)[t] = reinterpret_cast<const float4*>(S.feat)[t];
+        if (t < SFX_KD_PAD / 4) reinterpret_cast<float4*>(ops.featR_w(D) + (size_t)slot * SFX_KD_PAD)[t] = reinterpret_cast<const float4*>(S.feat)[t];
         MARK(17);
         for (int i = t; i < SFX_J * 12; i += CT) {
             const int j = i / 12, e = i % 12;
-            D.AT_w[((size_t)e * SFX_JPAD + j) * D.Bpad + slot] = S.A[i];
+            ops.AT_w(D)[((size_t)e * SFX_JPAD + j) * D.Bpad + slot] = S.A[i];
         }
         MARK(18);
         if (args.forward_only == 2) {           // export pass only: keep the forward state for the adjoint pass

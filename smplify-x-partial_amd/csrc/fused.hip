@@ -7,6 +7,9 @@
 //  k_tick_dense (dense LBS): between two launches of the batched MFMA GEMM (lbs_dense.hip) one
 //               launch does [loss + adjoint of evaluation i] -> [optimiser tick] -> [pose
 //               assembly / kinematic chain of evaluation i+1 and its export to the GEMM operands].
+//  k_tick_dense_multi (dense LBS, body-only, few frames): up to SFX_TICK_ROUNDS such rounds in one launch -- the tick needs
+//               nothing of the GEMM there (self-served blend offsets), so a workgroup walks its frame's rounds over a ring of
+//               operand sets and the GEMMs follow behind the launch.
 #include "closure_body.h"
 #include "lbfgs_body.h"
 
@@ -146,6 +149,79 @@ void k_tick_dense(DevModel M, BatchDev D, const VarList* __restrict__ vls, const
     }
 }
 
+// k_tick_dense_multi: up to SFX_TICK_ROUNDS rounds of the self-served form (has_eval = 2) of k_tick_dense<FrameLDSSmall8, 1> in ONE
+// launch.  T(i+1) of a frame reads only what T(i) of the same workgroup wrote -- optimiser state, trial point, forward-state
+// blob, its column of the operands -- so the workgroup loops over its frame's rounds and keeps its CU between them: no kernel
+// boundary, no cold entry (the tables stay in LDS: keep_tables from the second round on) and no waiting for the slowest frame
+// of every round.  Round r reads operand set r (blend offsets, column copy) and exports to set r + 1; the host launches the
+// GEMMs of sets 1 .. R behind the launch, on the CUs the ticks do not hold (host/fit_loop.hip DenseLoop::launch_multi).  Between
+// rounds: one workgroup barrier, state through global memory exactly as between two launches (same-workgroup visibility
+// behind a barrier, as in k_fit_rows).  No flags, no polling, nothing between workgroups.
+// A frame that finishes in round r (or is found finished at entry: r = 0) copies its column of set r into EVERY later set of the
+// launch and leaves the loop, so each GEMM behind this launch skins its last evaluation (copy_operand_column, generalised).
+// The debug clocks stamp round 0.
+__global__ __launch_bounds__(FrameLDSSmall8::kThreads, 1)
+void k_tick_dense_multi(DevModel M, BatchDev D, const VarList* __restrict__ vls, const StageW* __restrict__ sws,
+                        int first_stage, int last_stage, TickSets sets, int R) {
+    using LDS = FrameLDSSmall8;
+    constexpr int CTK = LDS::kThreads;
+    __shared__ LDS S;
+    __shared__ float gflat[SFX_NVAR_MAX];
+    __shared__ float fval;
+    __shared__ float s_al[SFX_HIST_MAX + 2 * LB_BS];
+    __shared__ OptScal st;
+    __shared__ __align__(16) float s_pf[2048];          // the optimiser tick's working set, prefetched (k_tick_dense: PF)
+    __shared__ __align__(16) VarList s_vl[2];
+    __shared__ int s_stage;
+    __shared__ float* s_featR[SFX_TICK_ROUNDS + 1];       // the operand sets, indexed by round (a kernel argument indexed at run time would live in scratch)
+    __shared__ float* s_AT[SFX_TICK_ROUNDS + 1];
+    const int b = D.act ? D.act[blockIdx.x] : blockIdx.x;
+    const int slot = D.slot[b];
+    const int self_col = __builtin_amdgcn_readfirstlane(M.n_uniq > 0 ? slot : 0);
+    const bool stamp = D.dbg && blockIdx.x == 0 && threadIdx.x == 0;
+    if (stamp) { D.dbg[62] += 1; if (D.dbg[62] <= D.dbg[61]) D.dbg[24] = clock64(); }
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int q = 0; q <= SFX_TICK_ROUNDS; ++q) { s_featR[q] = sets.featR[q]; s_AT[q] = sets.AT[q]; }
+    }
+    __syncthreads();
+    int r = 0;
+#pragma clang loop unroll(disable)
+    for (bool live = D.stage[b] <= last_stage; live && r < R; ++r) {
+        if (r) __syncthreads();
+        int t = threadIdx.x;
+        asm volatile("" : "+v"(t));                   // opaque per round: address arithmetic on it stays inside the round instead of being hoisted and spilled
+        const OperandSets ops{s_featR[r], s_featR[r + 1], s_AT[r + 1], t};
+        ClosureArgs a{};
+        a.stage_override = -2; a.use_dense_verts = 2; a.reuse_fwd = 1; a.keep_tables = r > 0; a.self_col = self_col;
+        lds_fill_async16<CTK>(s_pf, D.vec + (size_t)b * NVEC * SFX_NVAR_MAX, NVEC * SFX_NVAR_MAX / 4);
+        lds_fill_async16<CTK>(s_pf + NVEC * SFX_NVAR_MAX, D.X + (size_t)b * SFX_NPAR_MAX, SFX_NPAR_MAX / 4);
+        lds_fill_async16<CTK>(s_pf + NVEC * SFX_NVAR_MAX + SFX_NPAR_MAX, D.Xt + (size_t)b * SFX_NPAR_MAX, SFX_NPAR_MAX / 4);
+        lds_fill_async<CTK>(&st, &(reinterpret_cast<const OptState*>(D.opt) + b)->s, (int)(sizeof(OptScal) / 4));
+        if (r == 0) lds_fill_async<CTK>(s_vl, vls, (int)(2 * sizeof(VarList) / 4));
+        closure_body(S, M, D, vls, sws, a, b, gflat, &fval, NoUpstream{}, ops);
+        __syncthreads();
+        if (t < 64)
+            lbfgs_tick_body<SFX_SETS_SMALL8, true>(M, D, s_vl, first_stage, last_stage, 0, 0, b, t, s_al, st, s_pf, &fval, gflat, &s_stage);
+        __syncthreads();
+        if (stamp && r == 0 && D.dbg[62] <= D.dbg[61]) { D.dbg[25] = clock64(); for (int i = 0; i < 17; ++i) D.dbg[40 + i] = D.dbg[i]; }
+        const int stage_now = s_stage;
+        if (stage_now > last_stage) { live = false; break; }      // finished in this round: set r holds its last evaluation
+        ClosureArgs e{};
+        e.stage_override = stage_now; e.export_dense = 1; e.forward_only = 2; e.keep_tables = 1;
+        e.x_lds = s_pf + NVEC * SFX_NVAR_MAX + SFX_NPAR_MAX;
+        closure_body(S, M, D, vls, sws, e, b, nullptr, nullptr, NoUpstream{}, ops);
+        if (stamp && r == 0 && D.dbg[62] <= D.dbg[61]) D.dbg[26] = clock64();
+    }
+    if (r == R) return;                                  // every round exported
+    const float4* const f0 = reinterpret_cast<const float4*>(s_featR[r] + (size_t)slot * SFX_KD_PAD);
+    const float* const a0 = s_AT[r];
+    for (int q = r + 1; q <= R; ++q) {
+        if (threadIdx.x < SFX_KD_PAD / 4) reinterpret_cast<float4*>(s_featR[q] + (size_t)slot * SFX_KD_PAD)[threadIdx.x] = f0[threadIdx.x];
+        for (int i = threadIdx.x; i < 12 * SFX_JPAD; i += CTK) s_AT[q][(size_t)i * D.Bpad + slot] = a0[(size_t)i * D.Bpad + slot];
+    }
+}
+
 // debug / tests (sfx_batch_debug_read "uvp_self"): self_blend_offsets for every column of the current D.featR, one workgroup of four
 // wavefronts per column -- what a tick workgroup launched with has_eval = 2 would use in place of that column's row of D.uvp
 __global__ __launch_bounds__(256)
@@ -166,25 +242,41 @@ void launch_fit_rows(const DevModel& M, const BatchDev& D, const VarList* vl_dev
     else
         hipLaunchKernelGGL(k_fit_rows<FrameLDS>, dim3(D.cfg.B), dim3(FrameLDS::kThreads), 0, s, M, D, vl_dev, sw_dev, first_stage, last_stage, max_ticks);
 }
+// The launch shapes of the body-only dense tick: a workgroup per CU while the grid fits the chip -- eight wavefronts
+// (FrameLDSSmall8: same bits as four, closure_body.h; lab build, SFX_TICK_THREADS=256: the four-wavefront kernel of round 3, a
+// measurement switch) -- and two four-wavefront workgroups per CU beyond.  launch_tick_dense and tick_dense_multi_ok both ask here.
+enum TickShape { TICK_SMALL8, TICK_SMALL_CU, TICK_SMALL_OCC };
+static TickShape tick_small_shape(int grid) {
+    static const int n_cu = [] { hipDeviceProp_t p; int dev = 0; (void)hipGetDevice(&dev); return hipGetDeviceProperties(&p, dev) == hipSuccess ? p.multiProcessorCount : 256; }();
+#ifdef SFX_LAB
+    static const bool t256 = [] { const char* e = getenv("SFX_TICK_THREADS"); return e && atoi(e) == 256; }();
+#else
+    constexpr bool t256 = false;
+#endif
+    return grid > n_cu ? TICK_SMALL_OCC : t256 ? TICK_SMALL_CU : TICK_SMALL8;
+}
+bool tick_dense_multi_ok(const DevModel& M, const BatchDev& D) {
+    return M.n_uniq > 0 && M.n_uniq <= FrameLDSSmall8::kMaxItems && sfx_small_closure(M, D) && tick_small_shape(D.act ? D.nrun : D.cfg.B) == TICK_SMALL8;
+}
+void launch_tick_dense_multi(const DevModel& M, const BatchDev& D, const VarList* vl_dev, const StageW* sw_dev,
+                             int first_stage, int last_stage, const TickSets& sets, int R, hipStream_t s) {
+    const int grid = D.act ? D.nrun : D.cfg.B;
+    if (grid <= 0 || R <= 0) return;
+    hipLaunchKernelGGL(k_tick_dense_multi, dim3(grid), dim3(FrameLDSSmall8::kThreads), 0, s, M, D, vl_dev, sw_dev, first_stage, last_stage, sets, R);
+}
 void launch_tick_dense(const DevModel& M, const BatchDev& D, const VarList* vl_dev, const StageW* sw_dev,
                        int first_stage, int last_stage, int has_eval, hipStream_t s) {
     const int grid = D.act ? D.nrun : D.cfg.B;
     if (grid <= 0) return;
-    static const int n_cu = [] { hipDeviceProp_t p; int dev = 0; (void)hipGetDevice(&dev); return hipGetDeviceProperties(&p, dev) == hipSuccess ? p.multiProcessorCount : 256; }();
     if (sfx_small_closure(M, D)) {
-        // a workgroup per CU: eight wavefronts (FrameLDSSmall8: same bits as four, closure_body.h); lab build, SFX_TICK_THREADS=256:
-        // the four-wavefront kernel of round 3 (measurement switch)
-#ifdef SFX_LAB
-        static const bool t256 = [] { const char* e = getenv("SFX_TICK_THREADS"); return e && atoi(e) == 256; }();
-#else
-        constexpr bool t256 = false;
-#endif
-        if (grid <= n_cu && !t256)
-            hipLaunchKernelGGL((k_tick_dense<FrameLDSSmall8, 1>), dim3(grid), dim3(FrameLDSSmall8::kThreads), 0, s, M, D, vl_dev, sw_dev, first_stage, last_stage, has_eval);
-        else if (grid <= n_cu)
-            hipLaunchKernelGGL((k_tick_dense<FrameLDSSmall, 1>), dim3(grid), dim3(FrameLDSSmall::kThreads), 0, s, M, D, vl_dev, sw_dev, first_stage, last_stage, has_eval);
-        else
-            hipLaunchKernelGGL((k_tick_dense<FrameLDSSmall, SFX_TICK_OCC>), dim3(grid), dim3(FrameLDSSmall::kThreads), 0, s, M, D, vl_dev, sw_dev, first_stage, last_stage, has_eval);
+        switch (tick_small_shape(grid)) {
+        case TICK_SMALL8:
+            hipLaunchKernelGGL((k_tick_dense<FrameLDSSmall8, 1>), dim3(grid), dim3(FrameLDSSmall8::kThreads), 0, s, M, D, vl_dev, sw_dev, first_stage, last_stage, has_eval); break;
+        case TICK_SMALL_CU:
+            hipLaunchKernelGGL((k_tick_dense<FrameLDSSmall, 1>), dim3(grid), dim3(FrameLDSSmall::kThreads), 0, s, M, D, vl_dev, sw_dev, first_stage, last_stage, has_eval); break;
+        case TICK_SMALL_OCC:
+            hipLaunchKernelGGL((k_tick_dense<FrameLDSSmall, SFX_TICK_OCC>), dim3(grid), dim3(FrameLDSSmall::kThreads), 0, s, M, D, vl_dev, sw_dev, first_stage, last_stage, has_eval); break;
+        }
     } else
         hipLaunchKernelGGL((k_tick_dense<FrameLDS, 1>), dim3(grid), dim3(FrameLDS::kThreads), 0, s, M, D, vl_dev, sw_dev, first_stage, last_stage, has_eval);
 }

@@ -138,10 +138,14 @@ extern "C" int sfx_batch_create(sfx_model* m, const sfx_batch_cfg* c, const sfx_
     D.featR = b->mem.zeros<float>((size_t)SFX_KD_PAD * D.Bpad);
     D.AT = b->mem.zeros<float>((size_t)12 * SFX_JPAD * D.Bpad);
     D.featR_w = D.featR; D.AT_w = D.AT;
+    b->op_f[0] = D.featR; b->op_a[0] = D.AT;
     if (c->lbs_mode == 1 && !D.cfg.pen) {
-        for (int i = 0; i < 2; ++i) {
-            b->featR_o[i] = b->mem.zeros<float>((size_t)SFX_KD_PAD * D.Bpad);
-            b->AT_o[i] = b->mem.zeros<float>((size_t)12 * SFX_JPAD * D.Bpad);
+        // the overlapped loop's further operand sets: two for the single rounds, a rotation of 2 x SFX_TICK_ROUNDS + 1 where the
+        // multi-round form can run (host.h: 17 sets in all, 21 MB at 256 frames)
+        b->n_sets = (m->M.n_uniq > 0 && m->M.n_uniq <= SFX_OV_SELF_UNIQ && sfx_small_closure(m->M, D)) ? OperandRing::kMaxSets : 3;
+        for (int i = 1; i < b->n_sets; ++i) {
+            b->op_f[i] = b->mem.zeros<float>((size_t)SFX_KD_PAD * D.Bpad);
+            b->op_a[i] = b->mem.zeros<float>((size_t)12 * SFX_JPAD * D.Bpad);
         }
     }
     D.verts = b->mem.zeros<float>((size_t)B * m->M.V * 3);

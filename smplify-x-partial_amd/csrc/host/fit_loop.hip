@@ -1,6 +1,7 @@
 // fit_loop.hip -- the hot loop of libsfx.so: sfx_batch_fit / sfx_batch_step are a stream of kernel launches with no host
-// arithmetic and one small device->host poll every POLL ticks.  DenseLoop is the polled loop of a fused dense fit (three round
-// forms over the column pool of column_pool.h), run_synced the loop of everything else, run_ticks chooses between them.
+// arithmetic and one small device->host poll every POLL ticks.  DenseLoop is the polled loop of a fused dense fit (four round
+// forms over the column pool of column_pool.h and the operand sets of operand_ring.h), run_synced the loop of everything else,
+// run_ticks chooses between them.
 #include "host.h"
 #include "../column_pool.h"
 
@@ -25,6 +26,7 @@ struct DenseSwitches {
     int rpb = 0, ahead = 0;                                                 // 0: the loop's own 8 rounds per batch, 3 / 1 batches ahead
     bool ov_on = true, self_on = true, self_in_serial = false;
     int ov_serial = SFX_OV_SERIAL, self_serial = SFX_OV_SELF_SERIAL, self_max = SFX_OV_SELF_MAX;
+    int multi_max = SFX_OV_MULTI_MAX, multi_R = SFX_OV_MULTI_R;           // the multi-round form: up to this many columns, rounds per launch
 };
 static const DenseSwitches& dense_switches() {
 #ifdef SFX_LAB
@@ -36,6 +38,10 @@ static const DenseSwitches& dense_switches() {
         v.ov_on = num("SFX_DENSE_OVERLAP", 1) != 0; v.self_on = num("SFX_DENSE_SELF", 1) != 0; v.self_in_serial = num("SFX_DENSE_SELF_SERIAL", 0) != 0;
         v.ov_serial = num("SFX_OVERLAP_SERIAL", SFX_OV_SERIAL); v.self_max = num("SFX_DENSE_SELF_MAX", SFX_OV_SELF_MAX);
         v.self_serial = num("SFX_OVERLAP_SERIAL", SFX_OV_SELF_SERIAL);      // (SFX_OVERLAP_SERIAL: whichever form is selected)
+        // the multi-round form stands where the serial rounds below the self-served band stood, so a given SFX_OVERLAP_SERIAL moves
+        // it too (= 0: every round a self-served single launch, down to one column)
+        v.multi_max = num("SFX_DENSE_MULTI", 1) != 0 ? num("SFX_DENSE_MULTI_MAX", getenv("SFX_OVERLAP_SERIAL") ? v.self_serial : SFX_OV_MULTI_MAX) : 0;
+        v.multi_R = num("SFX_DENSE_MULTI_R", SFX_OV_MULTI_R);
         return v;
     }();
 #else
@@ -50,25 +56,31 @@ namespace {
 // compaction) therefore lags by 8 rounds: finished frames only ever stay finished, so that is safe; the surplus rounds at the
 // end find nothing to do.  Frames beyond cfg.slots columns queue for the column of a frame that finishes (column_pool.h).
 //
-// A round is one GEMM and one tick launch, in one of three forms (round_serial, round_key_rest, round_self).  The two overlapped
-// forms run over THREE sets of operand buffers: cur = D.featR / D.AT, nxt = b->featR_o[0] / AT_o[0], and the set the GEMM of the
-// round before may still be reading, b->featR_o[1] / AT_o[1]; the host rotates them after every tick launch (the kernels take
-// BatchDev by value and know no parity).  T(i) overwrites what the GEMM of round i-2 read, hence its wait, which never blocks in
+// A round is one GEMM and one tick of every running frame, in one of four forms.  Three launch the tick of one round at a time
+// (round_serial, round_key_rest, round_self); the fourth (launch_multi) launches the ticks of up to eight rounds as ONE kernel
+// whose workgroups keep their CUs between rounds, and the GEMMs of those rounds behind it.  The form is chosen per polled batch.
+// The overlapped forms run over SETS of operand buffers (b->op_f / op_a); b->ring (operand_ring.h) decides which set an export
+// writes and which GEMM event s must have waited for first, and D.featR / D.AT always name its `cur`, the set of the latest
+// export (the kernels take BatchDev by value and know no parity).
+// Single overlapped rounds rotate THREE sets: T(i) overwrites what the GEMM of round i-2 read, hence its wait, which never blocks in
 // practice: with two sets T(i) had to wait for Gr(i-1) and then raced Gr(i) for the CUs -- a tick workgroup needs 300 to 512
 // registers per SIMD free and starves behind the GEMM's small workgroups (measured: 99 instead of 46 us per tick launch at 256
 // frames, no gain).  With three, T(i) is queued while Gr(i-1) drains and takes the CUs as they empty; Gr(i) fills what is left.
-// A finished frame's workgroup copies its column of cur to nxt for as long as it is listed (fused.hip).  Admission and
-// compaction exports write cur IN PLACE once s has waited for the latest Gr -- the columns of the frames that keep running hold
-// their pending evaluation in cur only.  Two records and two waits per round; no other cross-stream traffic.
+// A finished frame's workgroup copies its column of cur to the set written for as long as it is listed (fused.hip).  Admission
+// and compaction exports write cur IN PLACE once s has waited for the latest GEMM -- the columns of the frames that keep running
+// hold their pending evaluation in cur only.  Two records and two waits per round or multi-round launch; no other cross-stream traffic.
 struct DenseLoop {
     sfx_batch* const b; const hipStream_t s; const int first_stage, last_stage;
     BatchDev& D = b->D; const DevModel& M = b->m->M; const int B = D.cfg.B;
     bool overlap = false, self_form = false;            // a second stream and operand sets to overlap on; the model may serve itself
-    hipEvent_t last_G = nullptr, prev_G = nullptr;     // E_G of the latest overlapped round and of the one before (NULL: s has waited for it)
+    OperandRing& ring = b->ring;
+    long g_tok = OperandRing::kFree;                   // token of the newest GEMM event (its round's ov_i) s has not waited for
     hipEvent_t last_T = nullptr;                       // E_T of the latest self-served round (NULL: the latest round was of another form)
-    long ov_i = 0, tick = 0;                           // overlapped rounds (their slot in the event rings), rounds
+    long ov_i = 0, tick = 0;                           // overlapped rounds and multi-round launches (their slot in the event rings), rounds
     ColumnPool pool;
     int upl = 0, rpb = 8;                              // next upload buffer, rounds per polled batch
+    int rot = 0;                                       // operand sets in the rotation of the latest batch's form (0: exports in place)
+    int multi_R = 1;                                   // rounds per multi-round launch; the form rotates 2 multi_R + 1 operand sets
     // how much of the loop's wall time the HOST spends enqueueing (its headroom against a busy box) and waiting for stage flags
     double host_enq_s = 0.0, host_wait_s = 0.0; long host_batches = 0;
     static inline long nact_hist[9] = {};              // rounds by active GEMM columns: <=32, <=64, ..., <=256, more (cumulative)
@@ -76,9 +88,12 @@ struct DenseLoop {
         ProfScope p(name, s, Dx.nrun);
         launch_tick_dense(M, Dx, b->vl_dev, b->sw_dev, first_stage, last_stage, has_eval, s);
     }
-    int join_s2() {                                     // before s writes operands in place: every Gr has read them
-        if (last_G) SFX_CHECK(hipStreamWaitEvent(s, last_G, 0));
-        last_G = prev_G = nullptr;
+    hipEvent_t ev_G(long tok) const { return b->ov_ev[1][tok % SFX_OV_EVENTS]; }
+    int wait_G(long tok) { if (tok != OperandRing::kFree) SFX_CHECK(hipStreamWaitEvent(s, ev_G(tok), 0)); return 0; }
+    void point_at_cur() { D.featR = D.featR_w = b->op_f[ring.cur]; D.AT = D.AT_w = b->op_a[ring.cur]; }
+    int join_s2() {                                     // before s writes operands in place: every GEMM has read them
+        if (int rc = wait_G(g_tok)) return rc;
+        g_tok = OperandRing::kFree; ring.joined();
         return 0;
     }
     int upload(const std::vector<int>* fresh) {         // slot[], running list (+ admitted list) through pinned memory
@@ -95,15 +110,15 @@ struct DenseLoop {
         D.act = b->act_dev; D.nrun = (int)run.size();
         return 0;
     }
-    // the tail of both overlapped forms: s waits for E_G(i-2), T(i) exports evaluation i + 1 to nxt, the operand sets rotate
-    int tick_beside(hipEvent_t e_G, int has_eval) {
-        if (prev_G) SFX_CHECK(hipStreamWaitEvent(s, prev_G, 0));
-        prev_G = last_G; last_G = e_G;
-        BatchDev Dt = D; Dt.featR_w = b->featR_o[0]; Dt.AT_w = b->AT_o[0];
+    // the tail of both single overlapped forms: the GEMM of round k, E_G(k) behind it, reads cur; s waits for the reader of the
+    // next set (E_G(k-2)), T(k) exports evaluation k + 1 to it, and it becomes cur
+    int tick_beside(long k, int has_eval) {
+        const OperandRing::Write w = ring.next_single();
+        if (int rc = wait_G(w.wait)) return rc;
+        ring.gemm_reads_cur(k); g_tok = k;
+        BatchDev Dt = D; Dt.featR_w = b->op_f[w.set]; Dt.AT_w = b->op_a[w.set];
         tick_kernel("tick", Dt, has_eval);
-        float* const f = D.featR; D.featR = b->featR_o[0]; b->featR_o[0] = b->featR_o[1]; b->featR_o[1] = f;
-        float* const a = D.AT; D.AT = b->AT_o[0]; b->AT_o[0] = b->AT_o[1]; b->AT_o[1] = a;
-        D.featR_w = D.featR; D.AT_w = D.AT;
+        ring.exported(w.set); point_at_cur();
         return 0;
     }
     // Self-served form (models that export at most SFX_OV_SELF_UNIQ vertices: body-only keypoints).  The tick workgroup forms the
@@ -117,12 +132,13 @@ struct DenseLoop {
     // key / rest form records and waits for at once: a wait holds the record it was enqueued behind, so slot k + 1 of this
     // round is free again when round i + 4 records it.
     int round_self() {
-        const int k = (int)(ov_i++ % SFX_OV_EVENTS);
-        if (!last_G || !last_T) { SFX_CHECK(hipEventRecord(b->ov_ev[0][k], s)); last_T = b->ov_ev[0][k]; }
+        const long i = ov_i++;
+        const int k = (int)(i % SFX_OV_EVENTS);
+        if (g_tok == OperandRing::kFree || !last_T) { SFX_CHECK(hipEventRecord(b->ov_ev[0][k], s)); last_T = b->ov_ev[0][k]; }
         SFX_CHECK(hipStreamWaitEvent(b->s2, last_T, 0));
         { ProfScope p("lbs_dense", b->s2, D.nact); launch_lbs_dense(M, D, b->s2); }
         SFX_CHECK(hipEventRecord(b->ov_ev[1][k], b->s2));
-        if (int rc = tick_beside(b->ov_ev[1][k], 2)) return rc;
+        if (int rc = tick_beside(i, 2)) return rc;
         last_T = b->ov_ev[0][(k + 1) % SFX_OV_EVENTS];
         SFX_CHECK(hipEventRecord(last_T, s));
         return 0;
@@ -135,15 +151,17 @@ struct DenseLoop {
     // the loop joins first: Gk(i) on s and G(i-1) on s2 both write the key tiles of D.verts.
     int round_key_rest() {
         if (last_T) { if (int rc = join_s2()) return rc; last_T = nullptr; }
-        const int k = (int)(ov_i++ % SFX_OV_EVENTS);
+        const long i = ov_i++;
+        const int k = (int)(i % SFX_OV_EVENTS);
         if (b->m->n_key) { ProfScope p("lbs_dense_key", s, D.nact); launch_lbs_dense_list(M, D, b->m->tile_key, b->m->n_key, s); }
         SFX_CHECK(hipEventRecord(b->ov_ev[0][k], s));
         SFX_CHECK(hipStreamWaitEvent(b->s2, b->ov_ev[0][k], 0));
         { ProfScope p("lbs_dense", b->s2, D.nact); launch_lbs_dense_list(M, D, b->m->tile_rest, b->m->n_rest, b->s2); }
         SFX_CHECK(hipEventRecord(b->ov_ev[1][k], b->s2));
-        return tick_beside(b->ov_ev[1][k], 1);
+        return tick_beside(i, 1);
     }
-    // Everything on s: whole-grid GEMM, the interpenetration step (which needs every vertex before the tick), tick.
+    // Everything on s: whole-grid GEMM, the interpenetration step (which needs every vertex before the tick), tick; the export
+    // goes to cur in place.
     int round_serial() {
         if (int rc = join_s2()) return rc;
         last_T = nullptr;
@@ -152,8 +170,51 @@ struct DenseLoop {
         tick_kernel("tick", D, (dense_switches().self_in_serial && !b->pen && M.n_uniq <= SFX_OV_SELF_UNIQ) ? 2 : 1);
         return 0;
     }
+    // Multi-round form (where the self-served form applies and the tick kernel has a CU per workgroup: tick_dense_multi_ok).
+    // T(i+1) of a frame reads only what T(i) of the same workgroup wrote, so n <= multi_R rounds are ONE launch P whose workgroups
+    // loop over their frame's rounds (fused.hip k_tick_dense_multi): no kernel boundary and no cold entry per round, no waiting
+    // for the slowest frame of every round, and the workgroups never give their CUs to the GEMM's 655 small ones in between --
+    // which is what made single self-served rounds serial again at few columns.  The n GEMMs run beside the NEXT launch:
+    //     stream s :  wait E_G(b-2) | P(b): n rounds, reads cur, exports evaluations to the n sets behind it | record E_P(b)
+    //     stream s2:  wait E_P(b)   | G x n, a whole-mesh GEMM per evaluation P(b) consumed (cur and all it wrote but the last), in order | record E_G(b)
+    // The ring rotates 2 multi_R + 1 sets, so P(b) overwrites exactly what G(b-2) read.  Every evaluation still gets exactly one
+    // whole-mesh GEMM, in order, and as in the other forms the evaluation left in cur is the one that has had none: admission and
+    // compaction exports find the loop where a serial loop would be.  E_P takes the ring the other forms record E_T / E_K in.
+    int launch_multi(int n) {
+        const long i = ov_i++;
+        const int k = (int)(i % SFX_OV_EVENTS);
+        const OperandRing::Launch L = ring.next_multi(n, OperandRing::span(multi_R));
+        if (int rc = wait_G(L.wait)) return rc;
+        TickSets ts{};
+        for (int q = 0; q <= n; ++q) { ts.featR[q] = b->op_f[L.set[q]]; ts.AT[q] = b->op_a[L.set[q]]; }
+        { ProfScope p("tick_multi", s, (double)D.nrun * n); launch_tick_dense_multi(M, D, b->vl_dev, b->sw_dev, first_stage, last_stage, ts, n, s); }
+        hipEvent_t const e_P = b->ov_ev[0][(k + 1) % SFX_OV_EVENTS];
+        SFX_CHECK(hipEventRecord(e_P, s));
+        SFX_CHECK(hipStreamWaitEvent(b->s2, e_P, 0));
+        for (int q = 0; q < n; ++q) {
+            BatchDev Dg = D; Dg.featR = ts.featR[q]; Dg.AT = ts.AT[q];
+            ProfScope p("lbs_dense", b->s2, D.nact); launch_lbs_dense(M, Dg, b->s2);
+        }
+        SFX_CHECK(hipEventRecord(b->ov_ev[1][k], b->s2));
+        g_tok = i;
+        ring.launched_multi(L, i); point_at_cur();
+        return 0;
+    }
+    // Entering a form that rotates another number of sets (joined): every set of its rotation must hold the last column of the
+    // frames that have finished since the latest compaction -- their columns are still skinned, and their workgroups stop
+    // copying them before a wider rotation has come round -- so cur goes to all of them, once.  Not before the first round of a
+    // fit: nobody has finished.
+    int spread_cur(int n_rot) {
+        for (int i = 0; i < n_rot; ++i) {
+            if (i == ring.cur) continue;
+            SFX_CHECK(hipMemcpyAsync(b->op_f[i], b->op_f[ring.cur], (size_t)SFX_KD_PAD * D.Bpad * sizeof(float), hipMemcpyDeviceToDevice, s));
+            SFX_CHECK(hipMemcpyAsync(b->op_a[i], b->op_a[ring.cur], (size_t)12 * SFX_JPAD * D.Bpad * sizeof(float), hipMemcpyDeviceToDevice, s));
+        }
+        return 0;
+    }
     // One polled batch: rpb rounds, each in the form its count of active columns selects, then the stage flags to poll buffer
-    // `buf`.  Self-served at SFX_OV_SELF_SERIAL < columns <= SFX_OV_SELF_MAX: the band where the form won (LAB_NOTES 4.9).
+    // `buf`.  Multi-round launches at columns <= SFX_OV_MULTI_MAX (LAB_NOTES 4.14); entering a rotation of another size joins.
+    // Self-served at SFX_OV_SELF_SERIAL < columns <= SFX_OV_SELF_MAX: the band where the form won (LAB_NOTES 4.9).
     // Key / rest at SFX_OV_SERIAL < columns <= SFX_OV_MAX (LAB_NOTES "GEMM beside tick"): below, a short rest GEMM saves less
     // than it costs the tick kernel it runs beside (frames/s by threshold: 32: 581, 96: 597, 160: 605, 192: 603; serial loop
     // 563); above, 1 024 frames through the 512-column pool lost 6 % overlapped: two tick workgroups per CU and a GEMM that fills
@@ -163,9 +224,23 @@ struct DenseLoop {
         const DenseSwitches& sw = dense_switches();
         if (sw.dbg_nact) nact_hist[std::min(8, (D.nact - 1) / 32)] += rpb;
         const auto h0 = std::chrono::steady_clock::now();
-        for (int q = 0; q < rpb; ++q, ++tick) {
-            const int rc = self_form && D.nact > sw.self_serial && D.nact <= sw.self_max ? round_self()
-                         : overlap && D.nact > sw.ov_serial && D.nact <= SFX_OV_MAX      ? round_key_rest() : round_serial();
+        const bool multi = self_form && D.nact > 0 && D.nact <= sw.multi_max && OperandRing::span(multi_R) <= b->n_sets && tick_dense_multi_ok(M, D);
+        const bool self = !multi && self_form && D.nact > sw.self_serial && D.nact <= sw.self_max;
+        const bool key_rest = !multi && !self && overlap && D.nact > sw.ov_serial && D.nact <= SFX_OV_MAX;
+        const int rot_new = multi ? OperandRing::span(multi_R) : (self || key_rest) ? 3 : 0;
+        if (rot_new != rot && rot_new) {
+            if (int rc = join_s2()) return rc;
+            last_T = nullptr;
+            if (tick > 0) if (int rc = spread_cur(rot_new)) return rc;
+        }
+        rot = rot_new;
+        if (multi) for (int q = 0; q < rpb; q += multi_R) {
+            const int n = std::min(multi_R, rpb - q);
+            if (int rc = launch_multi(n)) return rc;
+            tick += n;
+        }
+        else for (int q = 0; q < rpb; ++q, ++tick) {
+            const int rc = self ? round_self() : key_rest ? round_key_rest() : round_serial();
             if (rc) return rc;
         }
         SFX_CHECK(hipMemcpyAsync(b->stage_host + (size_t)buf * B, D.stage, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -201,7 +276,7 @@ struct DenseLoop {
     }
     int run(long max_ticks, bool& done) {
         const DenseSwitches& sw = dense_switches();
-        overlap = sw.ov_on && !b->pen && b->featR_o[0] && b->featR_o[1] && b->AT_o[0] && b->AT_o[1];
+        overlap = sw.ov_on && !b->pen && b->n_sets >= 3;
         if (overlap && !b->s2) {
             int lo = 0, hi = 0;
             SFX_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));         // (lowest priority: the key tiles and the tick are the round's critical path)
@@ -217,10 +292,13 @@ struct DenseLoop {
             pool.reset(B, ncol);
             D.nact = ncol;
             if (int rc = upload(nullptr)) return rc;
+            ring.joined(); point_at_cur();      // (both streams are drained between fits)
+            rot = 0;
             tick_kernel("tick", D, 0);
             const double wall0 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
             rpb = std::max(1, std::min(64, sw.rpb > 0 ? sw.rpb : 8));
             const int ahead = std::max(1, std::min(SFX_POLL_BUFS - 1, sw.ahead > 0 ? sw.ahead : (b->pen ? 1 : 3)));
+            multi_R = OperandRing::rounds_per_launch(sw.multi_R, (long)ahead * rpb);      // (a finished frame stays listed for `ahead` batches)
             long q_head = 0, q_next = 0;       // batches processed / queued
             for (; q_next < ahead; ++q_next) if (int rc = rounds((int)(q_next % SFX_POLL_BUFS))) return rc;
             while (!done && tick < max_ticks + (long)rpb * (ahead + 1)) {

@@ -10,6 +10,7 @@
 #include "../../../include/sfx.h"
 #include "../sfx_internal.h"
 #include "../collide_host.h"
+#include "../operand_ring.h"
 #include "idle_slot.h"
 
 #include <map>
@@ -63,6 +64,16 @@ struct sfx_model {
 #define SFX_OV_SELF_MAX 192
 #endif
 #define SFX_OV_SELF_UNIQ 16  // one tile of exported vertices: three of the tick workgroup's wavefronts carry one MFMA chain each
+// the multi-round form (DenseLoop::launch_multi: up to SFX_OV_MULTI_R self-served rounds per tick launch, their GEMMs beside the next
+// launch) at 1 .. SFX_OV_MULTI_MAX active columns: in place of the serial rounds below the self-served band and of that band's
+// lowest slice.  Swept in LAB_NOTES 4.14 (frames/s with the form up to n columns: 0: 636.5, 16: 647.6, 32: 657.2, 64: 673.5,
+// 96: 677.2, 128: 677.6; at 128 columns with 2 / 4 / 8 rounds per launch: 624.4 / 659.5 / 677.6)
+#ifndef SFX_OV_MULTI_MAX
+#define SFX_OV_MULTI_MAX 96
+#endif
+#ifndef SFX_OV_MULTI_R
+#define SFX_OV_MULTI_R SFX_TICK_ROUNDS
+#endif
 struct sfx_batch {
     sfx_model* m = nullptr;
     BatchDev D{};
@@ -76,10 +87,15 @@ struct sfx_batch {
     int* act_new_dev = nullptr;   // [B] frames admitted at the latest poll (export-only launch)
     int slots = 0;                // GEMM columns of the fused dense loop (0: one per frame)
     hipEvent_t poll_ev[SFX_POLL_BUFS] = {};
-    // the overlapped dense loop (DenseLoop): the second and third set of GEMM operand buffers (owned by mem; D.featR / D.AT
-    // name the set of the most recent evaluation, whichever that is), the stream of the rest-tile GEMMs and the two rings of events that
-    // order them against the tick kernels; stream and events are made by the first fit that overlaps
-    float *featR_o[2] = {nullptr, nullptr}, *AT_o[2] = {nullptr, nullptr};      // [0] the next export's target, [1] the one after
+    // the overlapped dense loop (DenseLoop): the sets of GEMM operand buffers (owned by mem; set 0 is what D.featR / D.AT were
+    // created as, and D.featR / D.AT name set ring.cur, the one of the most recent evaluation), the bookkeeping that hands them
+    // out (operand_ring.h; it outlives a fit, like the buffers), the stream of the GEMMs beside the ticks and the two rings of
+    // events that order them against the tick kernels; stream and events are made by the first fit that overlaps.
+    // n_sets: 1 (no overlap: interpenetration, needed-rows), 3 (the single overlapped rounds) or OperandRing::kMaxSets (models the
+    // multi-round form serves: body-only; 2 x SFX_TICK_ROUNDS + 1) -- (SFX_KD_PAD + 12 SFX_JPAD) x Bpad floats each, 1.2 MB at 256 frames
+    float *op_f[OperandRing::kMaxSets] = {}, *op_a[OperandRing::kMaxSets] = {};
+    int n_sets = 1;
+    OperandRing ring;
     hipStream_t s2 = nullptr;
     hipEvent_t ov_ev[2][SFX_OV_EVENTS] = {};
     int K = 0;

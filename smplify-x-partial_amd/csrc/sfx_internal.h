@@ -362,5 +362,13 @@ void launch_fit_rows(const DevModel& M, const BatchDev& D, const VarList* vl_dev
 // self-served blend offsets (nothing of the GEMM of the pending evaluation is read)
 void launch_tick_dense(const DevModel& M, const BatchDev& D, const VarList* vl_dev, const StageW* sw_dev,
                        int first_stage, int last_stage, int has_eval, hipStream_t s);
+// R <= SFX_TICK_ROUNDS self-served rounds (has_eval = 2) in one launch of k_tick_dense_multi (fused.hip): round r reads operand set
+// r and exports to set r + 1, so `sets` names R + 1 of them, the first being the set of the pending evaluation.  Only where
+// tick_dense_multi_ok: the launch shape of the eight-wavefront body-only kernel with a workgroup per CU.
+#define SFX_TICK_ROUNDS 8
+struct TickSets { float* featR[SFX_TICK_ROUNDS + 1]; float* AT[SFX_TICK_ROUNDS + 1]; };
+bool tick_dense_multi_ok(const DevModel& M, const BatchDev& D);
+void launch_tick_dense_multi(const DevModel& M, const BatchDev& D, const VarList* vl_dev, const StageW* sw_dev,
+                             int first_stage, int last_stage, const TickSets& sets, int R, hipStream_t s);
 // debug / tests: the self-served blend offsets of every column from the current D.featR, out [B][n_uniq][3] (device)
 void launch_uvp_self(const DevModel& M, const BatchDev& D, float* out, hipStream_t s);
