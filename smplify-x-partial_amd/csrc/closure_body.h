@@ -47,19 +47,48 @@ struct ExtUpstream {
 // Which GEMM operand buffers an evaluation touches.  OwnOperands (the default): BatchDev's -- featR read by self_blend_offsets,
 // featR_w / AT_w written by the export pass.  OperandSets: the caller names them per call (k_tick_dense_multi, whose rounds
 // walk a ring of sets; BatchDev itself stays the untouched kernel argument, so its members stay scalar loads).
+// The policy also says where the forward state of a reuse_fwd pass is and whether an export pass saves it: between two launches
+// it travels through BatchDev.fwd (OwnOperands: always); between two rounds of one launch the export pass of the same workgroup
+// has left it in S, where nothing writes it until the next export (fwd_resident: no reload), and only an export whose successor
+// is not in the launch has to save it (fwd_store).
 struct OwnOperands {
     __device__ __forceinline__ int tid() const { return threadIdx.x; }
     __device__ __forceinline__ const float* featR(const BatchDev& D) const { return D.featR; }
     __device__ __forceinline__ float* featR_w(const BatchDev& D) const { return D.featR_w; }
     __device__ __forceinline__ float* AT_w(const BatchDev& D) const { return D.AT_w; }
+    __device__ __forceinline__ constexpr bool fwd_resident() const { return false; }
+    __device__ __forceinline__ constexpr bool fwd_store() const { return true; }
 };
 struct OperandSets {
     const float* r; float* fw; float* aw; int t;      // t: the caller's thread index (a loop over rounds passes one the compiler cannot hoist address arithmetic on)
+    bool resident, store;
     __device__ __forceinline__ int tid() const { return t; }
     __device__ __forceinline__ const float* featR(const BatchDev&) const { return r; }
     __device__ __forceinline__ float* featR_w(const BatchDev&) const { return fw; }
     __device__ __forceinline__ float* AT_w(const BatchDev&) const { return aw; }
+    __device__ __forceinline__ bool fwd_resident() const { return resident; }
+    __device__ __forceinline__ bool fwd_store() const { return store; }
 };
+
+// The forward state an export pass hands to the loss / adjoint pass of the same trial point (ClosureArgs.reuse_fwd): the leading
+// members of the working set, the hand poses, the LUT row and the VPoser activations, into the frame's row of BatchDev.fwd.
+template <class LDS>
+__device__ __forceinline__ void save_forward_state(const LDS& S, float* fwd, const int t, const bool use_vposer) {
+    constexpr int CT = LDS::kThreads;
+    constexpr int FWD_PREFIX = (int)(offsetof(LDS, vp) / sizeof(float));
+    const float* sp = reinterpret_cast<const float*>(&S);
+    for (int i = t; i < FWD_PREFIX / 4; i += CT)
+        reinterpret_cast<float4*>(fwd)[i] = reinterpret_cast<const float4*>(sp)[i];
+    float* ex = fwd + FWD_PREFIX;
+    if (t < SFX_NHAND) { ex[t] = S.lh45[t]; ex[SFX_NHAND + t] = S.rh45[t]; }
+    if (t == 64) ex[2 * SFX_NHAND] = __int_as_float(S.lut_row);
+    if constexpr (!std::is_same<decltype(S.V), EmptyLDS>::value) if (use_vposer) {
+        float* vx = ex + 96;
+        for (int i = t; i < VP_H; i += CT) { vx[i] = S.V.h1[i]; vx[VP_H + i] = S.V.h2[i]; }
+        if (t < 128) vx[2 * VP_H + t] = S.V.o[t];
+        if (t < 64) vx[2 * VP_H + 128 + t] = S.V.body[t];
+    }
+}
 
 // One closure evaluation of frame b by the whole workgroup (CT threads).  When `gflat` is not
 // NULL the flat gradient / loss are ALSO left in LDS (gflat[NVAR_MAX], *fout) for a consumer in
@@ -115,34 +144,34 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
     // every global source of this section goes to LDS asynchronously (lds_fill_async): one round trip for all of it
     if (!reuse) {
         if (args.x_lds) { for (int i = t; i < L.npar; i += CT) S.x[i] = args.x_lds[i]; }      // (published by the barrier below)
-        else lds_fill_async<CT>(S.x, xsrc, L.npar * (int)(sizeof(Real) / 4));
+        else lds_fill_async<CT>(S.x, xsrc, L.npar * (int)(sizeof(Real) / 4), t);
     }
     if (!args.keep_tables) {   // (a persistent workgroup keeps the tables and its frame's data in LDS between evaluations)
     static_assert(SFX_META_N % 4 == 0 && FD_N % 4 == 0 && offsetof(LDS, meta) % 16 == 0 && offsetof(LDS, fd) % 16 == 0, "16-byte copies");
-    lds_fill_async16<CT>(S.meta, M.meta, SFX_META_N / 4);
-    lds_fill_async16<CT>(S.fd, D.fd + (size_t)b * FD_N, FD_N / 4);     // per-frame record (packed by k_pack_fd)
+    lds_fill_async16<CT>(S.meta, M.meta, SFX_META_N / 4, t);
+    lds_fill_async16<CT>(S.fd, D.fd + (size_t)b * FD_N, FD_N / 4, t);     // per-frame record (packed by k_pack_fd)
     // static items (vertex joints, static landmarks): vertex ids, weights, template rows, skinning weights, per-joint
     // adjoint lists -- none of it depends on the pose, so it is fetched here, next to the other tables (a persistent
     // workgroup keeps it for the whole fit), not item by item inside the evaluation
     const int ns = M.n_static_items;
-    lds_fill_async<CT>(S.ivid, M.item_vid, ns); lds_fill_async<CT>(S.iw, M.item_w, ns); lds_fill_async<CT>(S.uslot, M.item_uslot, ns);
-    lds_fill_async<CT>(S.vt, M.item_vt, ns * 3);
-    lds_fill_async<CT>(S.wj, M.item_wj, ns * SFX_NW); lds_fill_async<CT>(S.ww, M.item_ww, ns * SFX_NW);
+    lds_fill_async<CT>(S.ivid, M.item_vid, ns, t); lds_fill_async<CT>(S.iw, M.item_w, ns, t); lds_fill_async<CT>(S.uslot, M.item_uslot, ns, t);
+    lds_fill_async<CT>(S.vt, M.item_vt, ns * 3, t);
+    lds_fill_async<CT>(S.wj, M.item_wj, ns * SFX_NW, t); lds_fill_async<CT>(S.ww, M.item_ww, ns * SFX_NW, t);
     if (M.n_sj <= LDS::kMaxItems * SFX_NW) {
-        lds_fill_async<CT>(S.sjs, M.sj_start, SFX_J + 1);
-        lds_fill_async<CT>(S.sji, M.sj_item, M.n_sj); lds_fill_async<CT>(S.sjw, M.sj_w, M.n_sj);
+        lds_fill_async<CT>(S.sjs, M.sj_start, SFX_J + 1, t);
+        lds_fill_async<CT>(S.sji, M.sj_item, M.n_sj, t); lds_fill_async<CT>(S.sjw, M.sj_w, M.n_sj, t);
     }
     }
-    if (reuse) {
+    if (reuse && !ops.fwd_resident()) {      // (resident: the export pass of this workgroup's previous round left all of it in S)
         static_assert(F64 || offsetof(LDS, lut_row) == offsetof(LDS, lh45) + 2 * SFX_NHAND * sizeof(float), "hand poses + LUT row are one run");
-        lds_fill_async16<CT>(&S, fwd, FWD_PREFIX / 4);
+        lds_fill_async16<CT>(&S, fwd, FWD_PREFIX / 4, t);
         const float* ex = fwd + FWD_PREFIX;
-        lds_fill_async<CT>(S.lh45, ex, 2 * SFX_NHAND + 1);
+        lds_fill_async<CT>(S.lh45, ex, 2 * SFX_NHAND + 1, t);
         if constexpr (HAS_VP) if (C.use_vposer) {
             const float* vx = ex + 96;
             static_assert(offsetof(VposerLDS, h2) == VP_H * sizeof(float) && offsetof(VposerLDS, o) == 2 * VP_H * sizeof(float), "h1 | h2 | o are one run");
-            lds_fill_async16<CT>(S.V.h1, vx, (2 * VP_H + 128) / 4);
-            lds_fill_async16<CT>(S.V.body, vx + 2 * VP_H + 128, 64 / 4);
+            lds_fill_async16<CT>(S.V.h1, vx, (2 * VP_H + 128) / 4, t);
+            lds_fill_async16<CT>(S.V.body, vx + 2 * VP_H + 128, 64 / 4, t);
         }
     }
     for (int i = t; i < SFX_KD_PAD; i += CT) { if (!reuse) S.feat[i] = 0.f; S.dfeat[i] = 0.f; }
@@ -152,7 +181,12 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
     // operand row, behind the entry's requests and in front of their wait -- into S.dvert, which nobody touches before the
     // reverse sweep ("needed vertices" below picks them up)
     if constexpr (!F64) {
-        if (self_uvp) self_blend_offsets(M.uniq_dirs, M.n_uniq, ops.featR(D) + (size_t)args.self_col * SFX_KD_PAD, S.dvert, wv, CT / 64, lane);
+        // (the operand row: the frame's column of the set the pending evaluation was exported to -- or, while the forward state is
+        //  resident, S.feat, which that export copied there: the same 2 KiB without the trip through memory)
+        if (self_uvp) {
+            if (reuse && ops.fwd_resident()) self_blend_offsets(M.uniq_dirs, M.n_uniq, reinterpret_cast<const float*>(S.feat), S.dvert, wv, CT / 64, lane);
+            else self_blend_offsets(M.uniq_dirs, M.n_uniq, ops.featR(D) + (size_t)args.self_col * SFX_KD_PAD, S.dvert, wv, CT / 64, lane);
+        }
     }
     lds_dma_wait();
     __syncthreads();
@@ -320,20 +354,7 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
         }
         MARK(18);
         if (args.forward_only == 2) {           // export pass only: keep the forward state for the adjoint pass
-            if (fwd) {
-                const float* sp = reinterpret_cast<const float*>(&S);
-                for (int i = t; i < FWD_PREFIX / 4; i += CT)
-                    reinterpret_cast<float4*>(fwd)[i] = reinterpret_cast<const float4*>(sp)[i];
-                float* ex = fwd + FWD_PREFIX;
-                if (t < SFX_NHAND) { ex[t] = S.lh45[t]; ex[SFX_NHAND + t] = S.rh45[t]; }
-                if (t == 64) ex[2 * SFX_NHAND] = __int_as_float(S.lut_row);
-                if constexpr (HAS_VP) if (C.use_vposer) {
-                    float* vx = ex + 96;
-                    for (int i = t; i < VP_H; i += CT) { vx[i] = S.V.h1[i]; vx[VP_H + i] = S.V.h2[i]; }
-                    if (t < 128) vx[2 * VP_H + t] = S.V.o[t];
-                    if (t < 64) vx[2 * VP_H + 128 + t] = S.V.body[t];
-                }
-            }
+            if (fwd && ops.fwd_store()) save_forward_state(S, fwd, t, C.use_vposer != 0);
             MARK(19);
             return;
         }
@@ -349,14 +370,14 @@ __device__ __forceinline__ void closure_body(LDS& S, const DevModel& M, const Ba
     if (dyn_live) {
         const int ns = M.n_static_items, nd = M.n_dyn_items;
         const size_t ro = (size_t)S.lut_row * nd;
-        lds_fill_async<CT>(S.ivid + ns, M.dynp_vid + ro, nd); lds_fill_async<CT>(S.iw + ns, M.dynp_w + ro, nd);
-        lds_fill_async<CT>(S.vt + ns * 3, M.dynp_vt + ro * 3, nd * 3);
-        if (M.dynp_us) lds_fill_async<CT>(S.uslot + ns, M.dynp_us + ro, nd);
-        lds_fill_async<CT>(S.wj + ns * SFX_NW, M.dynp_wj + ro * SFX_NW, nd * SFX_NW);
-        lds_fill_async<CT>(S.ww + ns * SFX_NW, M.dynp_ww + ro * SFX_NW, nd * SFX_NW);
+        lds_fill_async<CT>(S.ivid + ns, M.dynp_vid + ro, nd, t); lds_fill_async<CT>(S.iw + ns, M.dynp_w + ro, nd, t);
+        lds_fill_async<CT>(S.vt + ns * 3, M.dynp_vt + ro * 3, nd * 3, t);
+        if (M.dynp_us) lds_fill_async<CT>(S.uslot + ns, M.dynp_us + ro, nd, t);
+        lds_fill_async<CT>(S.wj + ns * SFX_NW, M.dynp_wj + ro * SFX_NW, nd * SFX_NW, t);
+        lds_fill_async<CT>(S.ww + ns * SFX_NW, M.dynp_ww + ro * SFX_NW, nd * SFX_NW, t);
         if (dyn_lds) {
-            lds_fill_async<CT>(S.djs, M.dynp_js + (size_t)S.lut_row * (SFX_J + 1), SFX_J + 1);
-            lds_fill_async<CT>(S.dji, M.dynp_ji + ro * SFX_NW, nd * SFX_NW); lds_fill_async<CT>(S.djw, M.dynp_jw + ro * SFX_NW, nd * SFX_NW);
+            lds_fill_async<CT>(S.djs, M.dynp_js + (size_t)S.lut_row * (SFX_J + 1), SFX_J + 1, t);
+            lds_fill_async<CT>(S.dji, M.dynp_ji + ro * SFX_NW, nd * SFX_NW, t); lds_fill_async<CT>(S.djw, M.dynp_jw + ro * SFX_NW, nd * SFX_NW, t);
         }
         lds_dma_wait();
         __syncthreads();

@@ -27,12 +27,12 @@ struct EmptyLDS {};
 // tables, this frame's record, the forward state of the previous launch -- is requested back to back this way: ONE memory
 // round trip instead of one per copy loop (the entry of k_tick_dense was 7.7 us body-only / 11 us with hands + face).
 // The destination of one wave-instruction is a contiguous run of 64 dwords (or 64 x 16 bytes) starting at a wave-uniform
-// LDS address; sources are per-lane.
+// LDS address; sources are per-lane.  tid: the caller's thread index where it is not to be threadIdx.x itself (OperandSets.t).
 typedef __attribute__((address_space(3))) void* sfx_lds_vp;
 typedef const __attribute__((address_space(1))) void* sfx_glb_vp;
 template <int CT>
-__device__ __forceinline__ void lds_fill_async(void* lds_dst, const void* gsrc, const int n_dwords) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+__device__ __forceinline__ void lds_fill_async(void* lds_dst, const void* gsrc, const int n_dwords, const int tid = threadIdx.x) {
+    const int lane = tid & 63, wv = tid >> 6;
     const char* g = reinterpret_cast<const char*>(gsrc);
     char* l = reinterpret_cast<char*>(lds_dst);
     for (int base = wv * 64; base < n_dwords; base += CT) {
@@ -46,8 +46,8 @@ __device__ __forceinline__ void lds_fill_async(void* lds_dst, const void* gsrc, 
 __device__ __forceinline__ void lds_dma_wait() { __builtin_amdgcn_s_waitcnt(0x0F70); }      // vmcnt(0); expcnt / lgkmcnt untouched
 // the same in 16-byte units (both sides 16-byte aligned)
 template <int CT>
-__device__ __forceinline__ void lds_fill_async16(void* lds_dst, const void* gsrc, const int n16) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+__device__ __forceinline__ void lds_fill_async16(void* lds_dst, const void* gsrc, const int n16, const int tid = threadIdx.x) {
+    const int lane = tid & 63, wv = tid >> 6;
     const char* g = reinterpret_cast<const char*>(gsrc);
     char* l = reinterpret_cast<char*>(lds_dst);
     for (int base = wv * 64; base < n16; base += CT) {

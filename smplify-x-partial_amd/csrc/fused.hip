@@ -155,8 +155,9 @@ void k_tick_dense(DevModel M, BatchDev D, const VarList* __restrict__ vls, const
 // boundary, no cold entry (the tables stay in LDS: keep_tables from the second round on) and no waiting for the slowest frame
 // of every round.  Round r reads operand set r (blend offsets, column copy) and exports to set r + 1; the host launches the
 // GEMMs of sets 1 .. R behind the launch, on the CUs the ticks do not hold (host/fit_loop.hip DenseLoop::launch_multi).  Between
-// rounds: one workgroup barrier, state through global memory exactly as between two launches (same-workgroup visibility
-// behind a barrier, as in k_fit_rows).  No flags, no polling, nothing between workgroups.
+// rounds: one workgroup barrier; the frame's state stays in LDS (forward state in S, the tick's working set in s_pf / st) and is
+// written to global memory as between two launches, for the host and for whoever runs the frame's next round, but not read
+// back.  No flags, no polling, nothing between workgroups.
 // A frame that finishes in round r (or is found finished at entry: r = 0) copies its column of set r into EVERY later set of the
 // launch and leaves the loop, so each GEMM behind this launch skins its last evaluation (copy_operand_column, generalised).
 // The debug clocks stamp round 0.
@@ -185,35 +186,54 @@ void k_tick_dense_multi(DevModel M, BatchDev D, const VarList* __restrict__ vls,
         for (int q = 0; q <= SFX_TICK_ROUNDS; ++q) { s_featR[q] = sets.featR[q]; s_AT[q] = sets.AT[q]; }
     }
     __syncthreads();
-    int r = 0;
-#pragma clang loop unroll(disable)
-    for (bool live = D.stage[b] <= last_stage; live && r < R; ++r) {
-        if (r) __syncthreads();
-        int t = threadIdx.x;
-        asm volatile("" : "+v"(t));                   // opaque per round: address arithmetic on it stays inside the round instead of being hoisted and spilled
-        const OperandSets ops{s_featR[r], s_featR[r + 1], s_AT[r + 1], t};
-        ClosureArgs a{};
-        a.stage_override = -2; a.use_dense_verts = 2; a.reuse_fwd = 1; a.keep_tables = r > 0; a.self_col = self_col;
+    // The optimiser tick's working set (k_tick_dense: PF) and the forward state of the pending evaluation come from global memory
+    // in round 0 alone: requested here, waited for by the entry barrier of round 0's loss / adjoint pass.  In every later round
+    // they are what the tick and the export pass of the round before left in s_pf / st and in S -- the tick writes back all it
+    // changes there, the export pass saves what it leaves, so the bytes are those a reload would bring -- and the frame's stage
+    // is the one that tick handed over in s_stage.
+    int stage_now = D.stage[b];
+    if (stage_now <= last_stage) {
         lds_fill_async16<CTK>(s_pf, D.vec + (size_t)b * NVEC * SFX_NVAR_MAX, NVEC * SFX_NVAR_MAX / 4);
         lds_fill_async16<CTK>(s_pf + NVEC * SFX_NVAR_MAX, D.X + (size_t)b * SFX_NPAR_MAX, SFX_NPAR_MAX / 4);
         lds_fill_async16<CTK>(s_pf + NVEC * SFX_NVAR_MAX + SFX_NPAR_MAX, D.Xt + (size_t)b * SFX_NPAR_MAX, SFX_NPAR_MAX / 4);
         lds_fill_async<CTK>(&st, &(reinterpret_cast<const OptState*>(D.opt) + b)->s, (int)(sizeof(OptScal) / 4));
-        if (r == 0) lds_fill_async<CTK>(s_vl, vls, (int)(2 * sizeof(VarList) / 4));
+        lds_fill_async<CTK>(s_vl, vls, (int)(2 * sizeof(VarList) / 4));
+    }
+    int r = 0;
+    const bool live_at_entry = stage_now <= last_stage;
+#pragma clang loop unroll(disable)
+    for (bool live = live_at_entry; live && r < R; ++r) {
+        if (r) __syncthreads();
+        int t = threadIdx.x;
+        asm volatile("" : "+v"(t));                   // opaque per round: address arithmetic on it stays inside the round instead of being hoisted and spilled
+        // forward state: in S from round 1 on; saved to D.fwd by the last export of the launch alone (the next launch, a
+        // single-round tick after a form change, or a compaction's export may be the reader -- never one before that)
+        const OperandSets ops{s_featR[r], s_featR[r + 1], s_AT[r + 1], t, r > 0, r + 1 == R};
+        ClosureArgs a{};
+        a.stage_override = stage_now; a.use_dense_verts = 2; a.reuse_fwd = 1; a.keep_tables = r > 0; a.self_col = self_col;
         closure_body(S, M, D, vls, sws, a, b, gflat, &fval, NoUpstream{}, ops);
         __syncthreads();
         if (t < 64)
-            lbfgs_tick_body<SFX_SETS_SMALL8, true>(M, D, s_vl, first_stage, last_stage, 0, 0, b, t, s_al, st, s_pf, &fval, gflat, &s_stage);
+            lbfgs_tick_body<SFX_SETS_SMALL8, true, false>(M, D, s_vl, first_stage, last_stage, 0, 0, b, t, s_al, st, s_pf, &fval, gflat, &s_stage, stage_now);
         __syncthreads();
         if (stamp && r == 0 && D.dbg[62] <= D.dbg[61]) { D.dbg[25] = clock64(); for (int i = 0; i < 17; ++i) D.dbg[40 + i] = D.dbg[i]; }
-        const int stage_now = s_stage;
+        stage_now = __builtin_amdgcn_readfirstlane(s_stage);
         if (stage_now > last_stage) { live = false; break; }      // finished in this round: set r holds its last evaluation
         ClosureArgs e{};
         e.stage_override = stage_now; e.export_dense = 1; e.forward_only = 2; e.keep_tables = 1;
         e.x_lds = s_pf + NVEC * SFX_NVAR_MAX + SFX_NPAR_MAX;
         closure_body(S, M, D, vls, sws, e, b, nullptr, nullptr, NoUpstream{}, ops);
+        // the tick's working set to memory, every round (the host reads it after the fit, the next launch at its entry): here, by all
+        // wavefronts next to the export's stores, whose acknowledgement the barrier at the loop's top waits for anyway -- at the
+        // tick's end the tick wavefront waited for these stores alone, on the frame's chain
+        tick_write_back<CTK>(D, b, s_pf, st, t);
         if (stamp && r == 0 && D.dbg[62] <= D.dbg[61]) D.dbg[26] = clock64();
     }
     if (r == R) return;                                  // every round exported
+    if (live_at_entry) tick_write_back<CTK>(D, b, s_pf, st, (int)threadIdx.x);      // finished in round r: its last tick's working set
+    // finished in round r > 0: the export of round r - 1 did not save its forward state (its reader was this workgroup); D.fwd is
+    // to hold the state of the frame's last exported evaluation, and S still does -- nothing after an export pass writes there
+    if (r > 0 && D.fwd) save_forward_state(S, D.fwd + (size_t)b * SFX_FWD_N, (int)threadIdx.x, false);
     const float4* const f0 = reinterpret_cast<const float4*>(s_featR[r] + (size_t)slot * SFX_KD_PAD);
     const float* const a0 = s_AT[r];
     for (int q = r + 1; q <= R; ++q) {

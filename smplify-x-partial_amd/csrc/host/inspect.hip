@@ -31,7 +31,8 @@ extern "C" int sfx_debug_phase_clocks(sfx_batch* b, int32_t stage, int64_t* out 
 //   "verts" V*3, "vposed" V*3, "pen_dverts" V*3, "pen_dfeat" 512, "pen_dA" 55*12, "pen_loss" 1,
 //   "A" 12*55 (skinning transforms, [row*4+col][joint] gathered from the GEMM operand), "feat" 512,
 //   "uvp" n_uniq*3 (blend offsets of the exported vertices as the dense GEMM wrote them), "uvp_self" n_uniq*3 (the same from
-//   closure_lds.h self_blend_offsets on the current "feat": one launch of k_uvp_self into a scratch buffer)
+//   closure_lds.h self_blend_offsets on the current "feat": one launch of k_uvp_self into a scratch buffer),
+//   "fwd" SFX_FWD_N = 6016 (rows are frames: the forward state each frame's latest export pass saved for its loss / adjoint pass)
 extern "C" int sfx_batch_debug_read(sfx_batch* b, const char* name, float* out, int64_t n_out) {
     if (!b || !name || !out) { sfx_set_error("null argument"); return -1; }
     const BatchDev& D = b->D; const int B = D.cfg.B, V = b->m->M.V;
@@ -50,6 +51,7 @@ extern "C" int sfx_batch_debug_read(sfx_batch* b, const char* name, float* out, 
     if (k == "pen_dA") return plain(D.pen_dA, (size_t)SFX_J * 12);
     if (k == "pen_loss") return plain(D.pen_loss, 1);
     if (k == "uvp") return plain(D.uvp, (size_t)b->m->M.n_uniq * 3);
+    if (k == "fwd") return plain(D.fwd, SFX_FWD_N);
     if (k == "uvp_self") {
         const size_t n = (size_t)B * b->m->M.n_uniq * 3;
         if ((int64_t)n != n_out) { sfx_set_error("'%s' holds %zu floats, caller asked for %lld", name, n, (long long)n_out); return -1; }

@@ -449,15 +449,18 @@ __device__ __forceinline__ Lane3 lb_two_loop(const float* hS, const float* hY, c
 // are LDS scratch owned by the caller.
 // PF: the caller has the working set (vectors, X, Xt in s_work, the scalar state in s_state) and both variable lists (vls
 // points to LDS copies) in place already -- k_tick_dense requests them with its entry's LDS-DMA batch, a whole loss /
-// adjoint pass before the tick wants them -- and takes the frame's stage after the tick from *stage_out.
-template <int SETS, bool PF = false>
+// adjoint pass before the tick wants them -- and takes the frame's stage after the tick from *stage_out.  stage_in (PF): the
+// frame's stage where the caller knows it -- a workgroup that ran this frame's previous tick has it from that tick's *stage_out,
+// and its working set is what that tick left in s_work / s_state (everything a tick changes there it also writes back) --; -2: D.stage.
+template <int SETS, bool PF = false, bool WB = true>
 __device__ __forceinline__ void lbfgs_tick_wave0(const DevModel& M, const BatchDev& D, const VarList* __restrict__ vls,
                                                  int first_stage, int last_stage, int init, int step_mode,
                                                  const int b, const int lane, float* s_al, OptScal& s_state, float* s_work,
-                                                 const float* f_src, const float* g_src, int* stage_out = nullptr) {
+                                                 const float* f_src, const float* g_src, int* stage_out = nullptr,
+                                                 const int stage_in = -2) {
     const BatchCfgDev& C = D.cfg;
     OptState* gst = reinterpret_cast<OptState*>(D.opt) + b;
-    int stage = D.stage[b];
+    int stage = (PF && stage_in != -2) ? stage_in : D.stage[b];
     float* Xg = D.X + (size_t)b * SFX_NPAR_MAX;          // global homes of the parameters, the trial point and the vectors;
     float* Xtg = D.Xt + (size_t)b * SFX_NPAR_MAX;        // a tick works on LDS copies (below)
     float* vecg = D.vec + (size_t)b * NVEC * SFX_NVAR_MAX;
@@ -869,12 +872,14 @@ __device__ __forceinline__ void lbfgs_tick_wave0(const DevModel& M, const BatchD
     }
     TMARK(6);
     LB_SYNC();
-    // write the working set back
+    // write the working set back (WB = false: the caller does, with tick_write_back below)
+    if constexpr (WB) {
 #pragma unroll
     for (int k = 0; k < NVEC; ++k) st3_full(vecg + k * SFX_NVAR_MAX, ld3_raw(vec, (unsigned)k * SFX_NVAR_MAX, lane), lane);
     reinterpret_cast<float4*>(Xg)[lane] = reinterpret_cast<const float4*>(X)[lane];
     reinterpret_cast<float4*>(Xtg)[lane] = reinterpret_cast<const float4*>(Xt)[lane];
     if (lane == 0) gst->s = s_state;     // ro[] and the band tables are written in place
+    }
     if (PF && lane == 0) *stage_out = stage;
     TMARK(7);
 #undef TMARK
@@ -882,14 +887,32 @@ __device__ __forceinline__ void lbfgs_tick_wave0(const DevModel& M, const BatchD
 #undef VEC
 }
 
+// The write-back of a PF tick's working set by the whole workgroup (CT threads, behind a barrier after the tick): vectors, X and Xt
+// are one run of s_work, a 16-byte store per thread; the scalar state a dword per thread.  Same bytes as the tick's own write-back.
+template <int CT>
+__device__ __forceinline__ void tick_write_back(const BatchDev& D, const int b, const float* s_work, const OptScal& s_state, const int t) {
+    constexpr int NV4 = NVEC * SFX_NVAR_MAX / 4, NX4 = SFX_NPAR_MAX / 4;
+    for (int i = t; i < NV4 + 2 * NX4; i += CT) {
+        const float4 v = reinterpret_cast<const float4*>(s_work)[i];
+        float4* dst = i < NV4 ? reinterpret_cast<float4*>(D.vec + (size_t)b * NVEC * SFX_NVAR_MAX) + i
+                    : i < NV4 + NX4 ? reinterpret_cast<float4*>(D.X + (size_t)b * SFX_NPAR_MAX) + (i - NV4)
+                                    : reinterpret_cast<float4*>(D.Xt + (size_t)b * SFX_NPAR_MAX) + (i - NV4 - NX4);
+        *dst = v;
+    }
+    int* gs = reinterpret_cast<int*>(&(reinterpret_cast<OptState*>(D.opt) + b)->s);
+    const int* ls = reinterpret_cast<const int*>(&s_state);
+    for (int i = t; i < (int)(sizeof(OptScal) / 4); i += CT) gs[i] = ls[i];
+}
+
 // Entry for a workgroup: wavefront 0 runs the state machine, the others pass through.  SETS: see lb_two_loop.
-template <int SETS, bool PF = false>
+template <int SETS, bool PF = false, bool WB = true>
 __device__ __forceinline__ void lbfgs_tick_body(const DevModel& M, const BatchDev& D, const VarList* __restrict__ vls,
                                                 int first_stage, int last_stage, int init, int step_mode,
                                                 const int b, const int tid, float* s_al, OptScal& s_state, float* s_work,
-                                                const float* f_src, const float* g_src, int* stage_out = nullptr) {
+                                                const float* f_src, const float* g_src, int* stage_out = nullptr,
+                                                const int stage_in = -2) {
     if (tid >= 64) return;
-    lbfgs_tick_wave0<SETS, PF>(M, D, vls, first_stage, last_stage, init, step_mode, b, tid, s_al, s_state, s_work, f_src, g_src, stage_out);
+    lbfgs_tick_wave0<SETS, PF, WB>(M, D, vls, first_stage, last_stage, init, step_mode, b, tid, s_al, s_state, s_work, f_src, g_src, stage_out, stage_in);
 }
 
 
