@@ -514,6 +514,55 @@ int  sfx_eval_nearest(int32_t B, int32_t Na, int32_t Nb, const float* a_dev, con
                       int32_t n_thresh, const double* thresh /* HOST */, float* dist_ab_dev, float* dist_ba_dev,
                       int32_t* count_ab_dev, int32_t* count_ba_dev, int32_t* valid_dev, void* stream);
 
+/* ---- fitted meshes drawn over their images on the device (csrc/raster.hip, csrc/host/render.hip) ------------------------
+ * A batched software rasteriser for B triangle meshes of one topology, in place of render_mesh (smplifyx/utils.py:497-538:
+ * pyrender's offscreen OpenGL).  Stateless like sfx_eval_*: device pointers, sizes, a stream; no handle, no allocation, no
+ * synchronisation; the caller supplies the scratch.  B == 0 returns 0 before any pointer is looked at.  A refusal (a NULL
+ * required pointer, n_lights outside 0 .. SFX_RENDER_MAX_LIGHTS, znear not > 0, V or F < 1, H or W < 1, H * W or B * H * W
+ * beyond int32) returns -1, sets the error text and launches nothing.
+ *
+ * Camera: the fit camera itself (camera.PerspectiveCamera.forward): p_c = R p + t, x = fx X / Z + cx, y = fy Y / Z + cy, pixel
+ * centres at (i + 0.5, j + 0.5), y down.  The reference reaches the same projection by a detour -- it rotates the mesh by 180
+ * degrees about x, negates transl[0] and hands both to an OpenGL camera that looks down -z -- which is algebraically this
+ * projection with R = I.
+ * Vertices: screen = (x, y, Z) in float32, snapped to 1/256 pixel (rint).  A vertex is unusable when Z >= znear is false, a
+ * component is not finite, or |x| or |y| exceeds 2^20 pixels.  A triangle with an unusable vertex is dropped whole (there is NO
+ * near-plane clipping) and counted in dropped[b]; one whose snapped area is zero covers nothing.
+ * Coverage: int64 edge functions on the snapped corners at the pixel centres, top-left fill rule, both windings
+ * (csrc/raster_fixed.h): exact -- a manifold mesh has no cracks and no pixel hit twice along a shared edge.
+ * Depth: perspective-correct, lambda_i = (float)e_i / (float)area2, depth = 1 / sum lambda_i / Z_i.  Visibility: the smallest
+ * (bits(depth) << 32 | triangle) per pixel, so equal depths go to the lowest triangle id and an image depends neither on the
+ * order of the work nor on the batch.
+ * Shading: smooth vertex normals in camera space (for every vertex the un-normalised cross products of its usable incident
+ * faces, summed in the order of the vertex -> face lists, then normalised; no float atomics); per pixel b_i = lambda_i depth /
+ * Z_i, n = normalize(sum b_i n_i) turned towards the camera (n . p_c <= 0), shade = min(1, (1 / pi) sum_l I_l max(0, n . d_l)),
+ * rgb = base * shade, stored as floor(255 c + 0.5).  d_l points from the surface TO light l in the camera's frame and is used
+ * as given.  A covered pixel takes the mesh colour with alpha 255, an uncovered one the background with alpha 0
+ * (utils.py:531-536).  pyrender's metallic-roughness shader is not reproduced.
+ *   vf_offsets_dev [V + 1], vf_faces_dev [3 F]   the faces of every vertex (CSR), ascending face ids
+ *   cam_rot_dev row-major R per mesh or NULL (identity); focal_dev (fx, fy), center_dev (cx, cy) per mesh
+ *   vis_scratch_dev, vnormal_scratch_dev, snapped_scratch_dev    overwritten
+ *   rgba_dev, depth_dev (+inf where empty), tri_dev (-1 where empty), screen_dev, dropped_dev    outputs, each may be NULL     */
+#define SFX_RENDER_MAX_LIGHTS 8
+typedef struct sfx_render_cfg {
+    float base_rgb[3];
+    int32_t n_lights;
+    float light_dir[SFX_RENDER_MAX_LIGHTS][3];
+    float light_intensity[SFX_RENDER_MAX_LIGHTS];
+    float znear;
+} sfx_render_cfg;
+int  sfx_render_meshes(const sfx_render_cfg* cfg, int32_t B, int32_t V, int32_t F, int32_t H, int32_t W,
+                       const float* verts_dev /* [B][V][3] */, const int32_t* faces_dev /* [F][3] */,
+                       const int32_t* vf_offsets_dev /* [V+1] */, const int32_t* vf_faces_dev /* [3F] */,
+                       const float* cam_rot_dev /* [B][9] or NULL = I */, const float* cam_t_dev /* [B][3] */,
+                       const float* focal_dev /* [B][2] */, const float* center_dev /* [B][2] */,
+                       const unsigned char* background_dev /* [B][H][W][3] or NULL = black */,
+                       unsigned long long* vis_scratch_dev /* [B][H][W] */, float* vnormal_scratch_dev /* [B][V][3] */,
+                       int32_t* snapped_scratch_dev /* [B][V][2] */,
+                       unsigned char* rgba_dev /* [B][H][W][4] or NULL */, float* depth_dev /* [B][H][W] or NULL */,
+                       int32_t* tri_dev /* [B][H][W] or NULL */, float* screen_dev /* [B][V][3] or NULL */,
+                       int32_t* dropped_dev /* [B] or NULL */, void* stream);
+
 /* Gaussian-mixture body pose prior (MaxMixturePrior, smplifyx/prior.py:100-231; body_prior_type 'gmm'):
  * used by the closure when use_vposer is off and the batch has no regression pose (fitting.py:399-401).
  * means [M][D], precisions [M][D][D], nll_weights [M] = the module's buffers; D = 63, M <= 8 (HOST). */

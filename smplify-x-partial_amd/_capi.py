@@ -113,6 +113,15 @@ class CameraInitCfg(C.Structure):
     _fields_ = [("data_weight", C.c_float), ("depth_loss_weight", C.c_float), ("use_conf", C.c_int32)]
 
 
+RENDER_MAX_LIGHTS = 8       # SFX_RENDER_MAX_LIGHTS
+
+
+class RenderCfg(C.Structure):
+    """sfx_render_cfg: base colour, directional lights (camera frame, towards the light) and the near plane of sfx_render_meshes."""
+    _fields_ = [("base_rgb", C.c_float * 3), ("n_lights", C.c_int32), ("light_dir", (C.c_float * 3) * RENDER_MAX_LIGHTS),
+                ("light_intensity", C.c_float * RENDER_MAX_LIGHTS), ("znear", C.c_float)]
+
+
 # every symbol include/sfx.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "sfx_model_create": (C.c_int, [C.POINTER(ModelDesc), C.POINTER(C.c_void_p)]),
@@ -172,6 +181,9 @@ SYMBOLS = {
     "sfx_eval_align": (C.c_int, [C.c_int32] * 3 + [C.c_void_p] * 3 + [i32p, C.c_int32] + [C.c_void_p] * 3 + [C.c_void_p]),
     # B, Na, Nb, a, b, mask_a, mask_b, n_thresh, thresh (host), dist_ab, dist_ba, count_ab, count_ba, valid, stream
     "sfx_eval_nearest": (C.c_int, [C.c_int32] * 3 + [C.c_void_p] * 4 + [C.c_int32, f64p] + [C.c_void_p] * 5 + [C.c_void_p]),
+    # cfg, B, V, F, H, W, verts, faces, vf_offsets, vf_faces, rot, t, focal, center, background, three scratch buffers,
+    # rgba, depth, tri, screen, dropped, stream
+    "sfx_render_meshes": (C.c_int, [C.POINTER(RenderCfg)] + [C.c_int32] * 5 + [C.c_void_p] * 17 + [C.c_void_p]),
     "sfx_pen_create": (C.c_int, [C.c_int32, C.c_int32, i32p, i32p, i32p, i32p, C.c_int32, C.c_int32, C.c_int32,
                                  C.POINTER(C.c_void_p)]),
     "sfx_pen_destroy": (None, [C.c_void_p]),

@@ -105,6 +105,9 @@ _TABLE = {
     "use_gender_classifier": (_b_true, False, False),
     "save_vertices": (_b_true, False, False),
     "confidence_threshold": (float, 0, False),
+    # not a key of the reference: write the fitted mesh over the input image (its out_img_fn, main.py:273) with the engine's
+    # rasteriser.  `visualize` keeps meaning the reference's pyrender / interactive output, which this engine does not have.
+    "render_overlays": (_b_true, False, False),
 }
 
 _CHOICES = {

@@ -6,6 +6,7 @@
 //   eval.hip      one evaluation: the interpenetration step, closure and gradient readers, guess_init, forward, sfx_lbs_*
 //   fit_loop.hip  DenseLoop, run_synced, run_ticks; sfx_batch_fit / step
 //   inspect.hip   debug readers, the lab build's clocks, interpenetration diagnostics, trace, stats
+//   render.hip    sfx_render_meshes: the stateless entry of the mesh rasteriser (csrc/raster.hip)
 #pragma once
 #include "../../../include/sfx.h"
 #include "../sfx_internal.h"

@@ -372,3 +372,18 @@ void launch_tick_dense_multi(const DevModel& M, const BatchDev& D, const VarList
                              int first_stage, int last_stage, const TickSets& sets, int R, hipStream_t s);
 // debug / tests: the self-served blend offsets of every column from the current D.featR, out [B][n_uniq][3] (device)
 void launch_uvp_self(const DevModel& M, const BatchDev& D, float* out, hipStream_t s);
+
+// the mesh rasteriser (raster.hip; sfx_render_meshes in host/render.hip): everything of one call, device pointers as the C ABI
+// names them.  launch_raster_stage enqueues one kernel of the pipeline for the meshes b0 .. b0 + nb - 1, nb <= RS_GRID_Y.
+struct RasterArgs {
+    int B, V, F, H, W, n_lights;
+    float base[3], light_dir[8][3], light_int[8], znear;      // (8 = SFX_RENDER_MAX_LIGHTS, asserted in raster.hip)
+    const float* verts; const int* faces; const int* vf_off; const int* vf_faces;
+    const float *rot, *trans, *focal, *center;
+    const unsigned char* background;
+    unsigned long long* vis; float* vnormal; int* snapped;
+    unsigned char* rgba; float* depth; int* tri; float* screen; int* dropped;
+};
+enum { RS_STAGE_PROJECT = 0, RS_STAGE_VNORMALS, RS_STAGE_COVER, RS_STAGE_RESOLVE, RS_STAGES };
+#define RS_GRID_Y 65535      // gridDim.y holds this many meshes
+void launch_raster_stage(const RasterArgs& A, int stage, int b0, int nb, hipStream_t s);

@@ -215,3 +215,30 @@ def fit_frames(dm, cfg, keypoints, joint_weights, H, W, focal, reg_pose=None, re
         inv[perm] = np.arange(B_all)
         res = {k: (np.asarray(v)[inv] if np.ndim(v) > 0 and np.asarray(v).shape[0] == B_all else v) for k, v in res.items()}
     return res
+
+
+def render_overlays(dm, res, images_u8, focal, centers, H, W, frames=None):
+    """The fitted meshes of a batch result over their images (engine.render_meshes through each frame's fit camera, R = I).
+    res: fit_frames' result with 'vertices' (want_vertices=True) and 'cam_translation', arrays or CUDA tensors; images_u8: uint8
+    [n, H, W, 3] (array or CUDA tensor) or None (black); focal: a number or [n]; centers: [n, 2] or None (the image centre, as
+    fit_frames assumes without a camera prior); frames: the n rows of `res` to draw (default: all).  Returns a uint8 CUDA
+    tensor [n, H, W, 4]: the mesh colour with alpha 255 where the mesh is, the image with alpha 0 elsewhere."""
+    import torch
+    if "vertices" not in res:
+        raise ValueError("render_overlays: the result holds no 'vertices' (fit_frames(..., want_vertices=True))")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    rows = np.arange(len(res["cam_translation"])) if frames is None else np.asarray(frames, np.int64).reshape(-1)
+    n = len(rows)
+
+    def up(a, shape, dtype=torch.float32):
+        if torch.is_tensor(a):
+            return a.to(device=dev, dtype=dtype).reshape(shape).contiguous()
+        return torch.as_tensor(np.ascontiguousarray(np.asarray(a)), device=dev).to(dtype).reshape(shape).contiguous()
+    take = (lambda a: a[torch.as_tensor(rows, device=a.device)] if torch.is_tensor(a) else np.asarray(a)[rows])
+    verts = up(take(res["vertices"]), (n, dm.V, 3))
+    transl = up(take(res["cam_translation"]), (n, 3))
+    if centers is None:
+        centers = np.tile(np.array([W, H], np.float32) * 0.5, (n, 1))
+    foc = up(np.broadcast_to(np.asarray(focal, np.float32), (n,)).copy() if not torch.is_tensor(focal) else focal, (n,))
+    bg = None if images_u8 is None else up(images_u8, (n, H, W, 3), torch.uint8)
+    return engine.render_meshes(verts, dm.faces, transl, foc, up(centers, (n, 2)), H, W, background=bg)["rgba"]

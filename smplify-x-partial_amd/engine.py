@@ -1016,6 +1016,182 @@ def nearest_distances(a, b, thresholds=(), mask_a=None, mask_b=None, return_dist
     return out
 
 
+# ---- fitted meshes over their images (sfx_render_meshes, csrc/raster.hip) -----------------------------------------------------
+RENDER_MAX_LIGHTS = capi.RENDER_MAX_LIGHTS
+RENDER_BASE_RGB = (0.4, 0.4, 0.7)                                       # utils.py:499 vertex_colors
+# The reference's scene in the fit camera's frame, as (direction towards the light, intensity): the three "raymond" lights of
+# utils.py:467-495 (theta = pi / 6, phi = 0, 2 pi / 3, 4 pi / 3; they shine along -z of their own frame) and the light that
+# scene.add(light) puts at the origin (utils.py:519-521), all of intensity 1.  The OpenGL camera looks down -z with y up; the
+# fit camera looks down +z with y down, so y and z change sign.
+RENDER_LIGHTS = tuple(((0.5 * np.cos(phi), -0.5 * np.sin(phi), -np.cos(np.pi / 6.0)), 1.0)
+                      for phi in (0.0, 2.0 * np.pi / 3.0, 4.0 * np.pi / 3.0)) + (((0.0, 0.0, -1.0), 1.0),)
+RENDER_MAX_PIXELS = 1 << 26     # pixels of one launch: the visibility buffer takes 8 bytes each (512 MB)
+RENDER_WANT = ("rgba", "depth", "tri", "screen", "dropped")
+_RENDER_CACHE_SIZE = 8
+_render_cache = collections.OrderedDict()       # (topology, device) -> the topology's device arrays and the scratch of its calls
+
+
+def vertex_face_csr(faces, V):
+    """The faces of every vertex of a triangle mesh, on the host: (offsets int32 [V + 1], face ids int32 [offsets[V]]) with the
+    faces of vertex v at offsets[v] .. offsets[v + 1] - 1 in ascending face id, each face once (also one that names the vertex
+    twice).  Deterministic: the order in which sfx_render_meshes sums a vertex's face normals."""
+    f = np.asarray(faces)
+    if f.ndim != 2 or f.shape[1] != 3 or f.shape[0] < 1 or f.dtype.kind not in "iu":
+        raise ValueError("faces: an integer array of shape (F, 3) with F >= 1 is needed, got %s %s" % (f.dtype, f.shape))
+    f = f.astype(np.int64)
+    V = int(V)
+    if V < 1 or f.min() < 0 or f.max() >= V:
+        raise ValueError("faces: vertex ids %d..%d outside the %d vertices" % (f.min(), f.max(), V))
+    F = f.shape[0]
+    pairs = np.unique(f.reshape(-1) * F + np.repeat(np.arange(F, dtype=np.int64), 3))      # (vertex, face), sorted, each once
+    offsets = np.zeros(V + 1, np.int64)
+    np.cumsum(np.bincount(pairs // F, minlength=V), out=offsets[1:])
+    return offsets.astype(np.int32), (pairs % F).astype(np.int32)
+
+
+def _render_topology(faces, V, dev):
+    """The cache entry of a topology on a device: faces and CSR as device tensors, plus the scratch tensors of its calls.  A
+    tensor is recognised by its storage and version (the entry keeps it alive, so the address cannot be handed out again),
+    anything else by its contents."""
+    import hashlib
+    import torch
+    if torch.is_tensor(faces):
+        if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+            raise ValueError("faces: shape %s, expected (F, 3) with F >= 1" % (tuple(faces.shape),))
+        if faces.dtype not in (torch.int32, torch.int64):
+            raise ValueError("faces: torch.int32 or torch.int64 is needed, got %s" % faces.dtype)
+        key = ("tensor", faces.data_ptr(), faces._version, tuple(faces.shape), tuple(faces.stride()), faces.dtype, V, dev)
+    else:
+        host = np.ascontiguousarray(np.asarray(faces))
+        key = ("host", hashlib.sha1(host.tobytes()).hexdigest(), host.shape, host.dtype.str, V, dev)
+    ent = _render_cache.get(key)
+    if ent is None:
+        host = faces.detach().cpu().numpy() if torch.is_tensor(faces) else host
+        off, vf = vertex_face_csr(host, V)
+        F = int(host.shape[0])
+        vf_pad = np.zeros(3 * F, np.int32)                             # (the C ABI's [3F])
+        vf_pad[:vf.size] = vf
+        ent = dict(keep=faces, F=F, scratch={},
+                   faces=torch.as_tensor(capi.i32(host.astype(np.int64)), device=dev),
+                   off=torch.as_tensor(off, device=dev), vf=torch.as_tensor(vf_pad, device=dev))
+        _render_cache[key] = ent
+        while len(_render_cache) > _RENDER_CACHE_SIZE:
+            _render_cache.popitem(last=False)
+    else:
+        _render_cache.move_to_end(key)
+    return ent
+
+
+def _render_scratch(ent, n, V, HW, dev):
+    """vis int64 [n * HW], vnormal float32 [n, V, 3], snapped int32 [n, V, 2] of a topology's calls, grown on demand."""
+    import torch
+    sc = ent["scratch"]
+    if sc.get("n_v", 0) < n:
+        sc["vnormal"] = torch.empty([n, V, 3], dtype=torch.float32, device=dev)
+        sc["snapped"] = torch.empty([n, V, 2], dtype=torch.int32, device=dev)
+        sc["n_v"] = n
+    if sc.get("n_px", 0) < n * HW:
+        sc["vis"] = None                                               # (released before its replacement is asked for)
+        sc["vis"] = torch.empty([n * HW], dtype=torch.int64, device=dev)
+        sc["n_px"] = n * HW
+    return sc
+
+
+def render_cfg(base_rgb=RENDER_BASE_RGB, lights=RENDER_LIGHTS, znear=0.05):
+    """sfx_render_cfg from a base colour, ((direction, intensity), ...) and the near plane; refuses what the library would."""
+    lights = list(lights)
+    if len(lights) > RENDER_MAX_LIGHTS:
+        raise ValueError("lights: %d given, at most %d" % (len(lights), RENDER_MAX_LIGHTS))
+    if not float(znear) > 0.0:
+        raise ValueError("znear: %r, must be > 0" % (znear,))
+    cfg = capi.RenderCfg()
+    base = capi.f32(base_rgb).reshape(-1)
+    if base.size != 3:
+        raise ValueError("base_rgb: three values are needed, got %d" % base.size)
+    cfg.base_rgb[:] = base.tolist()
+    cfg.n_lights = len(lights)
+    for l, (d, inten) in enumerate(lights):
+        d = capi.f32(d).reshape(-1)
+        if d.size != 3:
+            raise ValueError("lights[%d]: a direction of three values is needed" % l)
+        cfg.light_dir[l][:] = d.tolist()
+        cfg.light_intensity[l] = float(inten)
+    cfg.znear = float(znear)
+    return cfg
+
+
+def render_meshes(vertices, faces, translation, focal, center, H, W, rotation=None, background=None, want=("rgba",),
+                  base_rgb=RENDER_BASE_RGB, lights=RENDER_LIGHTS, znear=0.05, max_pixels=RENDER_MAX_PIXELS, stream=None):
+    """B meshes of one topology drawn through their fit cameras (sfx_render_meshes; the contract is in include/sfx.h): exact
+    integer coverage with the top-left rule, perspective-correct depth, the nearest triangle per pixel (ties to the lowest id),
+    smooth normals, Lambert shading by directional lights, composited over `background`.
+      vertices [B, V, 3], translation [B, 3], center [B, 2]     float32 contiguous CUDA tensors
+      focal          [B, 2] (fx, fy), [B], or a number
+      faces          [F, 3] integers: a CUDA / CPU tensor or an array; its vertex -> face lists and device copies are cached per
+                     (topology, device) together with the scratch buffers, so calls of one topology belong on one stream
+      rotation       [B, 3, 3] or None (identity);  background uint8 [B, H, W, 3] or None (black)
+      want           any of 'rgba' uint8 [B, H, W, 4] (alpha 255 on the mesh, 0 elsewhere), 'depth' float32 [B, H, W] (+inf where
+                     empty), 'tri' int32 [B, H, W] (-1 where empty), 'screen' float32 [B, V, 3] (x, y, Z), 'dropped' int32 [B]
+                     (triangles left out for a vertex behind znear, non-finite or beyond 2^20 pixels; there is no clipping)
+      lights         ((direction towards the light in the camera frame, intensity), ...), at most 8
+      max_pixels     the batch is walked in chunks of at most max_pixels // (H * W) meshes (at least one): the visibility buffer
+                     takes 8 bytes per pixel.  An image does not depend on the chunking.
+    Returns a dict of device tensors.  Only enqueues on the current (or the given) stream."""
+    import torch
+    want = tuple(want)
+    bad = [w for w in want if w not in RENDER_WANT]
+    if bad or not want:
+        raise ValueError("want: some of %s, got %r" % (RENDER_WANT, want))
+    cfg = render_cfg(base_rgb, lights, znear)
+    H, W = int(H), int(W)
+    if H < 1 or W < 1 or H * W > 2 ** 31 - 1:
+        raise ValueError("H, W: %d x %d, both >= 1 and H * W within int32 are needed" % (H, W))
+    B, V = _points("vertices", vertices)
+    vertices = A.tensor("vertices", vertices, (B, V, 3))
+    dev = vertices.device
+    translation = A.tensor("translation", translation, (B, 3), device=dev, holder="vertices")
+    center = A.tensor("center", center, (B, 2), device=dev, holder="vertices")
+    if torch.is_tensor(focal):
+        if focal.dim() == 1:
+            focal = A.tensor("focal", focal, (B,), device=dev, holder="vertices").unsqueeze(1).expand(B, 2).contiguous()
+        else:
+            focal = A.tensor("focal", focal, (B, 2), device=dev, holder="vertices")
+    else:
+        focal = torch.full([B, 2], float(focal), dtype=torch.float32, device=dev)
+    rotation = A.tensor("rotation", rotation, (B, 3, 3), device=dev, optional=True, holder="vertices")
+    background = A.tensor("background", background, (B, H, W, 3), device=dev, dtype=torch.uint8, optional=True, holder="vertices")
+    ent = _render_topology(faces, V, dev)
+    out = {}
+    if "rgba" in want:
+        out["rgba"] = torch.empty([B, H, W, 4], dtype=torch.uint8, device=dev)
+    if "depth" in want:
+        out["depth"] = torch.empty([B, H, W], dtype=torch.float32, device=dev)
+    if "tri" in want:
+        out["tri"] = torch.empty([B, H, W], dtype=torch.int32, device=dev)
+    if "screen" in want:
+        out["screen"] = torch.empty([B, V, 3], dtype=torch.float32, device=dev)
+    if "dropped" in want:
+        out["dropped"] = torch.empty([B], dtype=torch.int32, device=dev)
+    if B == 0:
+        return out
+    chunk = max(1, min(B, int(max_pixels) // (H * W), (2 ** 31 - 1) // (H * W)))
+    sc = _render_scratch(ent, chunk, V, H * W, dev)
+    lib = capi.load()
+
+    def part(t, b0, b1):
+        return None if t is None else A.ptr(t[b0:b1])
+    with torch.cuda.device(dev):
+        for b0 in range(0, B, chunk):
+            b1 = min(B, b0 + chunk)
+            capi.check(lib.sfx_render_meshes(
+                C.byref(cfg), b1 - b0, V, ent["F"], H, W, part(vertices, b0, b1), A.ptr(ent["faces"]), A.ptr(ent["off"]),
+                A.ptr(ent["vf"]), part(rotation, b0, b1), part(translation, b0, b1), part(focal, b0, b1), part(center, b0, b1),
+                part(background, b0, b1), A.ptr(sc["vis"]), A.ptr(sc["vnormal"]), A.ptr(sc["snapped"]),
+                part(out.get("rgba"), b0, b1), part(out.get("depth"), b0, b1), part(out.get("tri"), b0, b1),
+                part(out.get("screen"), b0, b1), part(out.get("dropped"), b0, b1), A.stream(stream, dev)))
+    return out
+
+
 def prof_enable(on=True, every=1):
     """HIP-event timing of the named kernel launches; `every` = N times only every N-th launch of
     each name (an event pair costs two queue packets per launch)."""

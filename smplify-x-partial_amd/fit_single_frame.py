@@ -1,7 +1,8 @@
 """Drop-in for smplifyx/fit_single_frame.py:59-677 -- same signature, same result pickle
 (keys and order of :644-657, protocol 2), same optional vertices.ply -- with the whole
 optimisation executed by the MI355X engine (driver.fit_frames with a batch of one).
-Not reproduced: visualisation (`visualize=True`).  `interpenetration=True` runs the penetration
+Not reproduced: visualisation (`visualize=True`: pyrender windows and per-stage images); `render_overlays=True` writes the
+fitted mesh over the image to `out_img_fn` (main.py:273) with the engine's rasteriser.  `interpenetration=True` runs the penetration
 term of csrc/collide.hip in the stages with coll_loss_weight > 0 (always through the dense path).
 `vposer.encode(prior).sample()` (:245, random in the reference) uses the posterior mean unless
 `vposer_sample_seed` is given.  kwargs['lbs_mode'] = 'dense' evaluates all 10475 vertices in
@@ -52,7 +53,8 @@ def fit_single_frame(img, keypoints, body_model, camera, joint_weights, body_pos
                      use_joints_conf=False, interactive=True, visualize=False, degrees=None, batch_size=1,
                      dtype=torch.float32, ign_part_pairs=None, left_shoulder_idx=2, right_shoulder_idx=5,
                      result_folder=".", img_name="", pixie_results=None, expose_results=None, pare_results=None,
-                     regression_prior=None, format="coco25", smplx_path="", curr_img_folder=".", **kwargs):
+                     regression_prior=None, format="coco25", smplx_path="", curr_img_folder=".", out_img_fn=None,
+                     render_overlays=False, **kwargs):
     assert batch_size == 1, "fit_single_frame handles one frame; use driver.fit_frames for batches"
     if visualize:      # (every shipped cfg sets it) rendering is outside the fitting path: the fit runs, nothing is drawn
         warnings.warn("visualize=True: no images are rendered by this engine; the fit itself is unaffected")
@@ -112,7 +114,7 @@ def fit_single_frame(img, keypoints, body_model, camera, joint_weights, body_pos
     res = driver.fit_frames(dm, cfg, kp, jw.reshape(1, -1), H, W, focal_length, reg_pose=reg_pose, reg_global=reg_glob,
                             cam_prior_t=cam_t, cam_prior_center=cam_c,
                             lbs_mode="dense" if interpenetration else kwargs.get("lbs_mode", "rows"),
-                            reuse_entry_eval=True, want_vertices=want_v,
+                            reuse_entry_eval=True, want_vertices=want_v or bool(render_overlays),
                             body_pose_prior=body_pose_prior if hasattr(body_pose_prior, "get_mean") else None)
     # write the fitted values back into the caller's modules, as the reference leaves them
     with torch.no_grad():
@@ -132,6 +134,11 @@ def fit_single_frame(img, keypoints, body_model, camera, joint_weights, body_pos
     result["body_pose"] = res["body_pose"]
     with open(result_fn, "wb") as fh:
         pickle.dump(result, fh, protocol=2)
+    if render_overlays and out_img_fn:
+        from PIL import Image
+        rgba = driver.render_overlays(dm, res, utils._image_u8(img)[None], focal_length,
+                                      None if cam_c is None else np.asarray(cam_c, np.float32).reshape(1, 2), H, W)
+        Image.fromarray(rgba[0, :, :, :3].cpu().numpy()).save(out_img_fn)
     if want_v:
         _write_ply(os.path.join(result_folder, "vertices.ply"), res["vertices"][0])
     return result, float(res["final_loss"][0])

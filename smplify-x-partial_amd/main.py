@@ -10,6 +10,7 @@ schedule of all of them runs on the GPU at once -- and the same files are writte
     <output_folder>/<result_folder>/<fn>/vertices.ply          (save_vertices)
     <output_folder>/<mesh_folder>/<fn>/                        (created, as in the reference)
     <output_folder>/images/<fn>/<person:03d>/                  (created, as in the reference)
+    <output_folder>/images/<fn>/<person:03d>/output.png        (render_overlays: the fitted mesh over the image, main.py:273)
 
 With torch.distributed initialised (one process per GPU), rank r takes the frames
 dist.shard_by_cost gives it (known stragglers dealt round-robin); there is no collective in the data path (each rank writes its own
@@ -70,6 +71,25 @@ def _camera_prior(regression_prior, focal_length, pixie, expose, pare):
     raise ValueError("unknown regression prior %r" % regression_prior)
 
 
+OVERLAY_CHUNK = 16       # frames rendered, copied to the host and written as PNG at a time
+
+
+def write_overlays(dm, res, its, focal, centers, H, W, output_folder):
+    """<output_folder>/images/<fn>/<person:03d>/output.png (the reference's out_img_fn, main.py:273) for every frame of a fitted
+    group: the images are read again by path, OVERLAY_CHUNK at a time, drawn over on the device (driver.render_overlays) and
+    written with PIL."""
+    from PIL import Image
+    from .data_parser import read_image
+    for b0 in range(0, len(its), OVERLAY_CHUNK):
+        rows = list(range(b0, min(len(its), b0 + OVERLAY_CHUNK)))
+        imgs = np.stack([utils._image_u8(read_image(its[b]["img_path"])) for b in rows])
+        rgba = driver.render_overlays(dm, res, imgs, focal, None if centers is None else np.asarray(centers)[rows], H, W,
+                                      frames=rows).cpu().numpy()
+        for k, b in enumerate(rows):
+            Image.fromarray(rgba[k, :, :, :3]).save(osp.join(output_folder, "images", its[b]["fn"],
+                                                             "{:03d}".format(its[b]["person"]), "output.png"))
+
+
 def rank_share(items, cfg, joint_weights, rank, world):
     """This rank's frames of a multi-GPU job: the frames known to be long before the fit (driver.predicted_cost: side views,
     under-determined cameras) are dealt over the ranks back and forth (dist.shard_by_cost) -- a contiguous block
@@ -118,6 +138,7 @@ def main(**args):
         warnings.warn("visualize / interactive: rendering and progress output are outside the fitting path; the fit itself "
                       "is unaffected")
     args["visualize"] = False
+    render_overlays = bool(args.pop("render_overlays", False))      # (not a key of the reference: cmd_parser._TABLE)
     if not args.get("use_joints_conf", False):
         raise NameError("name 'joints_conf' is not defined")   # the reference fails here (fit_single_frame.py:286)
 
@@ -143,7 +164,7 @@ def main(**args):
             if (person_id >= max_persons and max_persons > 0) or person_id > 0:      # main.py:244-247
                 continue
             img_name = data["img_path"].split("images")[-1].split(".")[0].lstrip("/\\")
-            items.append(dict(fn=data["fn"], person=person_id, H=H_, W=W_, img_name=img_name,
+            items.append(dict(fn=data["fn"], person=person_id, H=H_, W=W_, img_name=img_name, img_path=data["img_path"],
                               keypoints=keypoints[person_id], gender=input_gender))
     items = rank_share(items, args, joint_weights, rank, world)
     groups = {}
@@ -192,7 +213,7 @@ def main(**args):
         res = driver.fit_frames(dm, cfg, kp, joint_weights, H_, W_, focal, reg_pose=reg_pose, reg_global=reg_glob,
                                 cam_prior_t=cam_t, cam_prior_center=cam_c,
                                 lbs_mode="dense" if interpenetration else args.get("lbs_mode", "rows"),
-                                reuse_entry_eval=True, want_vertices=bool(args.get("save_vertices")))
+                                reuse_entry_eval=True, want_vertices=bool(args.get("save_vertices")) or render_overlays)
         names = [n for n, _ in bm.named_parameters()]
         for b, it in enumerate(its):
             curr_result_folder = osp.join(result_folder, it["fn"])
@@ -210,6 +231,8 @@ def main(**args):
             if args.get("save_vertices"):
                 _write_ply(osp.join(curr_result_folder, "vertices.ply"), res["vertices"][b])
             n_done += 1
+        if render_overlays:
+            write_overlays(dm, res, its, focal, cam_c, H_, W_, output_folder)
     elapsed = time.time() - start
     print("Processing the data took: {}".format(time.strftime("%H hours, %M minutes, %S seconds", time.gmtime(elapsed))))
     return n_done

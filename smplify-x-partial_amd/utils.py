@@ -1,7 +1,8 @@
 """Host-side helpers of the fitting path -- mirror of the reference's `utils` names that
 the hot path touches (smplifyx/utils.py:60-95 rel_change/JointMapper/GMoF, :98-250
-smpl_to_annotation, :306-436 _compute_euler_from_matrix).  Index tables are data; the
-euler conversion is a closed form, not the reference's generic scipy-style routine.
+smpl_to_annotation, :306-436 _compute_euler_from_matrix, :438-538 optimization_visualization / render_mesh).  Index tables are
+data; the euler conversion is a closed form, not the reference's generic scipy-style routine; the overlay is drawn by the
+engine's rasteriser (csrc/raster.hip), not by pyrender.
 """
 import numpy as np
 import torch
@@ -140,3 +141,61 @@ def regression_prior_pose(regression_prior, expose=None, pixie=None, pare=None):
     else:
         raise ValueError("Unknown regression prior: {}".format(regression_prior))
     return pose.reshape(-1).astype(np.float32), glob.astype(np.float32)
+
+
+# ---- the fitted mesh over its image (utils.py:438-538) -------------------------------------------------------------------------
+def _image_u8(img):
+    """An image as uint8 [H, W, 3]: uint8 as it is, a float image in 0..1 rounded (floor(255 c + 0.5), so an image that came
+    from uint8 / 255 gets its own bytes back; the reference truncates, which can lose a level)."""
+    img = np.asarray(img)
+    if img.dtype == np.uint8:
+        return np.ascontiguousarray(img[..., :3])
+    return np.floor(np.clip(img[..., :3].astype(np.float64), 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)
+
+
+def render_mesh(img, mesh_trimesh, camera_center, camera_transl, focal_length, img_width, img_height):
+    """render_mesh of the reference (utils.py:497-538) with its signature and conventions, drawn by engine.render_meshes:
+    `mesh_trimesh` is any object with .vertices [V, 3] and .faces [F, 3] ALREADY rotated by 180 degrees about x, `camera_transl`
+    has its x NEGATED (both as optimization_visualization hands them over, utils.py:454-460), `img` is a float image in 0..1
+    (or uint8).  The two conventions place an OpenGL camera that looks down -z; together they are the fit camera's projection
+    with R = I, so both are undone here and the engine is asked.  Returns uint8 [H, W, 3]: the mesh colour where the mesh
+    covers a pixel, the image elsewhere (utils.py:531-536).  The shading is the engine's Lambert model under the reference's
+    lights, not pyrender's metallic-roughness shader."""
+    from . import engine
+    dev = torch.device("cuda", torch.cuda.current_device())
+    verts = np.asarray(mesh_trimesh.vertices, np.float32) * np.array([1.0, -1.0, -1.0], np.float32)
+    transl = np.asarray(camera_transl, np.float32).reshape(3) * np.array([-1.0, 1.0, 1.0], np.float32)
+    H, W = int(img_height), int(img_width)
+    bg = _image_u8(img)
+    if bg.shape != (H, W, 3):
+        raise ValueError("img: shape %s, expected (%d, %d, 3)" % (bg.shape, H, W))
+    out = engine.render_meshes(torch.as_tensor(verts[None], device=dev), np.asarray(mesh_trimesh.faces),
+                               torch.as_tensor(transl[None], device=dev), float(focal_length),
+                               torch.as_tensor(np.asarray(camera_center, np.float32).reshape(1, 2), device=dev), H, W,
+                               background=torch.as_tensor(bg[None], device=dev))
+    return out["rgba"][0, :, :, :3].cpu().numpy()
+
+
+class _Mesh(object):
+    """The two attributes render_mesh reads (trimesh is not a dependency of this engine)."""
+
+    def __init__(self, vertices, faces):
+        self.vertices, self.faces = vertices, faces
+
+
+def optimization_visualization(img, smplx_path, pose_embedding, body_model, camera, focal_length, W, H, out_img_save_path,
+                               vposer_rendered_img_save_path, use_cuda, mesh_fn, **kwargs):
+    """optimization_visualization of the reference (utils.py:438-465): the body model's current mesh over `img`, written to
+    `out_img_save_path` with PIL.  As there, the model is evaluated with body_pose = `pose_embedding`, the mesh is rotated by 180
+    degrees about x and the camera's translation gets its x negated before render_mesh sees them.  Not drawn: the VPoser pose
+    thumbnail (`vposer_rendered_img_save_path`: human_body_prior's renderer); not written: `mesh_fn` (trimesh's exporter)."""
+    if not out_img_save_path:
+        return
+    from PIL import Image
+    with torch.no_grad():
+        vertices = body_model(return_verts=True, body_pose=pose_embedding).vertices.detach().cpu().numpy().squeeze()
+        mesh = _Mesh(vertices * np.array([1.0, -1.0, -1.0]), body_model.faces)       # rotation by pi about x
+        camera_center = camera.center.detach().cpu().numpy().squeeze().copy()
+        camera_transl = camera.translation.detach().cpu().numpy().squeeze().copy()
+        camera_transl[0] *= -1.0
+        Image.fromarray(render_mesh(img, mesh, camera_center, camera_transl, focal_length, W, H)).save(out_img_save_path)
