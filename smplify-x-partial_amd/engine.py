@@ -401,16 +401,26 @@ _F32 = _Mode(np.float32, capi.f32, capi.fptr, "")
 _F64 = _Mode(np.float64, capi.f64, capi.dptr, "_f64")
 
 
+def _focal_pairs(focal, B, dtype):
+    """[B][2] = (fx, fy) of every frame from `focal`: a number or [B] (fx = fy), or [B, 2] = (fx, fy) per frame."""
+    f = np.asarray(focal, dtype)
+    if f.ndim == 0 or f.shape == (B,):
+        return np.broadcast_to(f.reshape(-1, 1), (B, 2))
+    if f.shape == (B, 2):
+        return f
+    raise ValueError("focal must be a number, [B] or [B, 2] = (fx, fy) with B = %d, got shape %r" % (B, tuple(f.shape)))
+
+
 def _pack_frames(m, B, K, keypoints, joint_weights, cam_init_mask, focal, center, data_weight, est_tz=None, cam_rot=None):
     """The five arrays of sfx_batch_set_frames in mode `m`: keypoints [B][K][3], joint weights and camera-init mask [B][K] (one
     frame's are broadcast), the camera record [B][6] = (fx, fy, cx, cy, data_weight, est_tz or 0) and the rotation [B][9]
-    (None = identity).  The data -- keypoints, weights, masks, rotation -- are fp32 numbers, widened in float64 mode; the
-    camera record is made in the mode's own dtype."""
+    (None = identity).  `focal`: a number or [B] (fx = fy), or [B, 2] = (fx, fy).  The data -- keypoints, weights, masks,
+    rotation -- are fp32 numbers, widened in float64 mode; the camera record is made in the mode's own dtype."""
     kp = m.cast(capi.f32(keypoints)).reshape(B, K, 3)
     jw = m.cast(np.broadcast_to(np.asarray(joint_weights, np.float32), (B, K)))
     cm = m.cast(np.broadcast_to(np.asarray(cam_init_mask, np.float32), (B, K)))
     cam = np.zeros((B, 6), m.dtype)
-    cam[:, 0] = cam[:, 1] = np.asarray(focal, m.dtype)
+    cam[:, 0:2] = _focal_pairs(focal, B, m.dtype)
     cam[:, 2:4] = np.asarray(center, m.dtype).reshape(-1, 2)
     cam[:, 4] = np.asarray(data_weight, m.dtype)
     if est_tz is not None:
@@ -515,6 +525,8 @@ class FrameBatch(capi.Handle):
 
     def set_frames(self, keypoints, joint_weights, cam_init_mask, focal, center, data_weight, est_tz=None,
                    cam_rot=None):
+        """Per-frame data (_pack_frames).  focal: a number or [B] (fx = fy), or [B, 2] = (fx, fy) per frame; center [B, 2];
+        data_weight and est_tz a number or [B]; cam_rot [B, 3, 3] row-major (None: identity)."""
         arrays = _pack_frames(self._mode, self.B, self.K, keypoints, joint_weights, cam_init_mask, focal, center, data_weight,
                               est_tz, cam_rot)
         self._call("set_frames", *[self._mode.ptr(a) for a in arrays])

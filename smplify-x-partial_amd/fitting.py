@@ -580,7 +580,8 @@ class EngineClosure(object):
             cmask = np.zeros((1, K), np.float32)
             est = np.zeros(1, np.float32)
         kp = np.concatenate([gt, conf[..., None]], -1)
-        fb.set_frames(kp, jwts, cmask, _np(cam.focal_length_x), _np(cam.center), float(loss.data_weight), est_tz=est,
+        focal = np.stack([_np(cam.focal_length_x).reshape(1), _np(cam.focal_length_y).reshape(1)], 1)      # [1, 2]: (fx, fy)
+        fb.set_frames(kp, jwts, cmask, focal, _np(cam.center), float(loss.data_weight), est_tz=est,
                       cam_rot=_np(cam.rotation).reshape(1, 9))
         self._fb, self._fb_stage = fb, stage
         self._stepped = False

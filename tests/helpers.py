@@ -237,6 +237,7 @@ def check_closure(label, stage, loss, lo, grad, go, loss_tol=CLOSURE_LOSS_TOL, g
     le, ge = closure_errors(loss, lo, grad, go)
     e = PARITY_LOG.setdefault((label, int(stage)), [0.0, 0.0, 0, loss_tol, grad_tol])
     e[0] = max(e[0], le); e[1] = max(e[1], ge); e[2] += 1
+    e[3] = max(e[3], loss_tol); e[4] = max(e[4], grad_tol)         # (callers whose bound follows the frame: the loosest one applied)
     assert le <= loss_tol, ("closure loss", label, stage, float(loss), float(lo), le, loss_tol)
     assert ge <= grad_tol, ("closure gradient", label, stage, ge, grad_tol)
     return le, ge

@@ -211,6 +211,33 @@ def test_pack_frames_float64_widens_the_data_and_keeps_the_camera():
 
 
 @pytest.mark.parametrize("mode", ("_F32", "_F64"))
+def test_pack_frames_focal_is_a_number_one_per_frame_or_a_pair_per_frame(mode):
+    """focal: a number or [B] fills fx = fy; [B, 2] = (fx, fy) fills cam[:, 0] and cam[:, 1] separately; the mode's own dtype
+    (float64 keeps a value that is no fp32 number); any other shape is refused by name, nothing is broadcast silently."""
+    from smplifyx_amd import engine
+    m = getattr(engine, mode)
+    fx, fy = np.array([1000.1, 2400.3]), np.array([950.7, 2400.9])
+    rnd = (lambda v: np.asarray(v, np.float64)) if mode == "_F64" else (lambda v: np.asarray(v, np.float32))
+    assert mode == "_F32" or np.float64(np.float32(fx[0])) != fx[0]
+    cam = _frames(m, focal=np.stack([fx, fy], 1))[3]
+    assert cam.dtype == m.dtype and cam.shape == (B, 6)
+    assert np.array_equal(cam[:, 0], rnd(fx)) and np.array_equal(cam[:, 1], rnd(fy)) and not np.array_equal(cam[:, 0], cam[:, 1])
+    assert np.array_equal(cam[:, 2:4], np.tile(rnd(CENTER), (B, 1))) and (cam[:, 4] == 1.0).all() and (cam[:, 5] == 0).all()
+    cam = _frames(m, focal=fx)[3]                                                                # [B]: one focal per frame
+    assert np.array_equal(cam[:, 0], rnd(fx)) and np.array_equal(cam[:, 1], rnd(fx))
+    for scalar in (FOCAL, np.float64(FOCAL), np.array(FOCAL)):
+        cam = _frames(m, focal=scalar)[3]
+        assert (cam[:, 0] == rnd(FOCAL)).all() and (cam[:, 1] == rnd(FOCAL)).all()
+    cam = _frames(m, focal=[[5.0, 6.0], [7.0, 8.0]])[3]                                          # (a list of pairs is an array)
+    assert cam[:, :2].tolist() == [[5.0, 6.0], [7.0, 8.0]]
+    for bad in (np.ones(1), np.ones(B + 1), np.ones((1, 2)), np.ones((B, 1)), np.ones((B, 3)), np.ones((2, B, 2)), np.ones((B + 1, 2)),
+                np.ones(0)):
+        with pytest.raises(ValueError, match=r"focal must be a number, \[B\] or \[B, 2\] = \(fx, fy\) with B = 2, got shape "
+                                             + str(tuple(bad.shape)).replace("(", r"\(").replace(")", r"\)")):
+            _frames(m, focal=bad)
+
+
+@pytest.mark.parametrize("mode", ("_F32", "_F64"))
 def test_pack_params_broadcasts_and_rounds_only_what_it_did(mode):
     from smplifyx_amd import engine
     m = getattr(engine, mode)

@@ -85,7 +85,12 @@ def _oracle_closure(model, cfg, frames, i, params, stage, dtype=torch.float64):
 
 def _oracle_closure_ff(model, cfg, frames, i, params, stage, dtype):
     """_oracle_closure's pair and the oracle.fit_frame.FrameFit it was evaluated on."""
-    ff = H.oracle_frame_fit(model, cfg, frames, i, dtype=dtype)
+    return _oracle_closure_at(H.oracle_frame_fit(model, cfg, frames, i, dtype=dtype), i, params, stage, dtype)
+
+
+def _oracle_closure_at(ff, i, params, stage, dtype):
+    """(loss, flat gradient, ff) of the oracle.fit_frame.FrameFit `ff` at row i of `params` -- what _oracle_closure_ff evaluates,
+    for callers that prepare the FrameFit themselves (another camera: tests/camera_common.py)."""
     bm = ff.bm
     with torch.no_grad():
         for k, v in params.items():
