@@ -80,7 +80,7 @@ extern "C" int sfx_batch_debug_read(sfx_batch* b, const char* name, float* out, 
     return -1;
 }
 
-// Stand-alone operator: the direction the device's blocked two-loop recursion (lbfgs_body.h lb_two_loop) computes from a history of `count`
+// Stand-alone operator: the direction the device's blocked two-loop recursion (lbfgs_two_loop.h lb_two_loop) computes from a history of `count`
 // curvature pairs pushed in order (rows of SFX_NVAR_MAX = 192 floats, zero padded; the window keeps the last history_size,
 // <= 0: 100) and a gradient g: d = -H g with H_diag = y.s / y.y of the last pair (lbfgs_ls.py:312-341).  Host pointers.
 extern "C" int sfx_lbfgs_two_loop(const float* S, const float* Y, int32_t count, int32_t history_size, const float* g, float* d_out) {

@@ -20,7 +20,7 @@ void launch_lbfgs_tick(const DevModel& M, const BatchDev& D, const VarList* vl_d
                        step_mode);
 }
 
-// ---- debug: the blocked recursion on a history given by the caller (tests/test_gpu_optimizer_steps.py)
+// ---- debug: the blocked recursion (lbfgs_two_loop.h alone) on a history given by the caller (tests/test_gpu_optimizer_steps.py)
 __global__ __launch_bounds__(64)
 void k_debug_two_loop(OptState* gst, float* hist, const float* S_in, const float* Y_in, int cnt, int hist_cap, const float* g_in, float* d_out) {
     __shared__ float s_al[SFX_HIST_MAX + 2 * LB_BS];

@@ -4,9 +4,10 @@
 //   FittingMonitor.run_fitting          smplifyx/fitting.py:147-217            (mode 0)
 //   LBFGS.step                          smplifyx/optimizers/lbfgs_ls.py:256-445 (mode 1)
 //   _strong_Wolfe / _cubic_interpolate  smplifyx/optimizers/lbfgs_ls.py:11-167
-// The state machine is lbfgs_tick_wave0 itself, instantiated over a BatchDev that holds one "stage" (0), an identity variable
-// list and none of the model's buffers: one wavefront per problem consumes one evaluation per launch and leaves the next point
-// to evaluate in the caller's buffer.  Specification: oracle/lbfgs_machine.py (x_trial, feed(f, g), done, records).
+// The state machine is lbfgs_tick_wave0 itself without the fit's stage sequencing (FIT = false), over a BatchDev that holds one
+// "stage" (0), an identity variable list and none of the model's buffers: one wavefront per problem consumes one evaluation
+// per launch and leaves the next point to evaluate in the caller's buffer.
+// Specification: oracle/lbfgs_machine.py (x_trial, feed(f, g), done, records).
 #include "../../include/sfx.h"
 #include "lbfgs_body.h"
 
@@ -23,7 +24,7 @@ void k_opt_tick(BatchDev D, const VarList* __restrict__ vls, int init, int step_
     __shared__ __align__(16) float s_work[2048];
     __shared__ __align__(16) float s_g[SFX_NVAR_MAX];
     const int b = blockIdx.x, lane = threadIdx.x;
-    const DevModel M{};           // the tick reads the model only for the side-view test, which this handle never enables
+    const DevModel M{};           // (FIT = false: not read)
     float* Xg = D.X + (size_t)b * SFX_NPAR_MAX;
     const float* Xtg = D.Xt + (size_t)b * SFX_NPAR_MAX;
     float* xt_out = x_trial + (size_t)b * N;
@@ -34,7 +35,7 @@ void k_opt_tick(BatchDev D, const VarList* __restrict__ vls, int init, int step_
             if (b == 0) *D.n_active = D.cfg.B;      // (no problem ends in this launch: nothing counts down yet)
         }
         LB_SYNC();
-        lbfgs_tick_wave0<3>(M, D, vls, 0, 0, init, step_mode, b, lane, s_al, s_state, s_work, loss, s_g);
+        lbfgs_tick_wave0<3, /* PF */ false, /* WB */ true, /* FIT */ false>(M, D, vls, 0, 0, init, step_mode, b, lane, s_al, s_state, s_work, loss, s_g);
         LB_SYNC();
         for (int i = lane; i < N; i += 64) xt_out[i] = Xtg[i];
         return;
@@ -47,7 +48,7 @@ void k_opt_tick(BatchDev D, const VarList* __restrict__ vls, int init, int step_
     st3_full(D.g + (size_t)b * SFX_NVAR_MAX, g, lane);
     if (lane == 0) evals[b] += 1;
     LB_SYNC();
-    lbfgs_tick_wave0<3>(M, D, vls, 0, 0, 0, step_mode, b, lane, s_al, s_state, s_work, loss + b, s_g);
+    lbfgs_tick_wave0<3, /* PF */ false, /* WB */ true, /* FIT */ false>(M, D, vls, 0, 0, 0, step_mode, b, lane, s_al, s_state, s_work, loss + b, s_g);
     LB_SYNC();
     for (int i = lane; i < N; i += 64) xt_out[i] = Xtg[i];
     if (lane == 0 && D.stage[b] > 0) atomicSub(D.n_active, 1);
@@ -124,11 +125,8 @@ extern "C" int sfx_opt_create(const sfx_opt_cfg* c, sfx_opt** out) {
     D.hist = h->mem.zeros<float>((size_t)B * 2 * (C.hist_ring + 8) * SFX_NVAR_MAX);
     D.n_active = h->mem.zeros<int>(4);
     D.stage_loss = h->mem.zeros<float>(B * ns);
-    D.stage_loss2 = h->mem.zeros<float>(B * ns);
     D.stage_evals = h->mem.zeros<int>(B * ns);
     D.stage_ref_evals = h->mem.zeros<int>(B * ns);
-    D.try_both = h->mem.zeros<int>(B);
-    D.orient_pass = h->mem.zeros<int>(B);
     h->evals = h->mem.zeros<int>(B);
     if (h->mem.failed) {
         sfx_set_error("sfx_opt_create: device memory for %d problems: %s", B, hipGetErrorString(hipGetLastError()));

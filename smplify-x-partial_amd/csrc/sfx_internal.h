@@ -30,10 +30,10 @@
 #define SFX_MAX_LEVELS 16
 #define SFX_HIST 100        // L-BFGS history (optim_factory 'lbfgsls' default): slots of the ring unless history_size asks for more
 #ifndef SFX_HIST_MAX
-#define SFX_HIST_MAX 400    // largest history_size (the alphas of the two-loop recursion live in LDS: lbfgs_body.h s_al)
+#define SFX_HIST_MAX 400    // largest history_size (the alphas of the two-loop recursion live in LDS: lbfgs_two_loop.h s_al)
 #endif
 #define SFX_HROWS (SFX_HIST + 8)   // ring of R slots + rows R..R+7 mirroring slots 0..7: any 8 consecutive members of the
-#define SFX_HROWS_MAX (SFX_HIST_MAX + 8)   // window are 8 consecutive rows (lbfgs_body.h lb_load); R = BatchCfgDev::hist_ring
+#define SFX_HROWS_MAX (SFX_HIST_MAX + 8)   // window are 8 consecutive rows (lbfgs_two_loop.h lb_load); R = BatchCfgDev::hist_ring
 #define SFX_NVAR_MAX 192    // optimiser vector length (182 / 88 / 6), padded to 3*64
 #define SFX_FWD_N 6016      // floats per frame of saved forward state (FrameLDS prefix incl. the fp64 transforms + 96 + VPoser 1280)
 #define SFX_NPAR_MAX 256    // canonical per-frame parameter block (182 with 12 hand components; 248 with all 45: forward only)

@@ -1,7 +1,7 @@
 """Drop-in handle for smplifyx/optimizers/lbfgs_ls.py's LBFGS (strong-Wolfe).  The algorithm
 itself -- two-loop recursion over the last history_size pairs, first-step scaling min(1, 1/|g|_1) * lr, bracket
 and zoom phases of the strong-Wolfe search, all stopping rules -- runs on the GPU in
-csrc/lbfgs.hip (specification: oracle/lbfgs_machine.py).  This object carries the hyper-
+csrc/lbfgs_body.h (specification: oracle/lbfgs_machine.py).  This object carries the hyper-
 parameters and forwards `.step(closure)` to the engine batch bound to the closure.
 
 With any other callable -- a closure the caller wrote on torch tensors, as the reference's LBFGS takes it (lbfgs_ls.py:256-445:

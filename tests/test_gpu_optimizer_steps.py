@@ -1,4 +1,4 @@
-"""Step-level parity of the on-device optimiser (csrc/lbfgs_body.h) with its specification
+"""Step-level parity of the on-device optimiser (csrc/lbfgs_body.h, lbfgs_two_loop.h) with its specification
 oracle/lbfgs_machine.py -- which tests/golden/lbfgs.npz pins to the reference's
 FittingMonitor.run_fitting (smplifyx/fitting.py:147-217), LBFGS.step (optimizers/lbfgs_ls.py:256-445) and
 _strong_Wolfe / _cubic_interpolate (:11-167) evaluation by evaluation.
