@@ -38,9 +38,11 @@
 extern "C" {
 #endif
 
-/* debug: elapsed 100 MHz wall-clock ticks at the end of k_pen_grid's seven steps (triangle boxes,
- * frame box, part boxes, part culling, grid histogram, scan, scatter; [7..9] unused) of the most
- * recent evaluation, then the number of grid entries: HOST [B][11].                               */
+/* debug: the clock window of the stats rows of the most recent evaluation's first B meshes, HOST [B][11]
+ * (PenClockCol, csrc/collide_slots.h): [3..6] PEN_CLK_LIST, _EVAL, _SUMS, _VERTS = 100 MHz wall-clock ticks
+ * from k_pen_narrow's start to the ends of its phases D-G (0 in form 0 and for a mesh handed over);
+ * [9] PEN_CLK_WALKS_CUT = bucket walks cut short, [10] PEN_CLK_ENTRIES = grid entries (counts, not ticks);
+ * [0..2] and [7..8] have no writer and read 0.                                                     */
 int  sfx_pen_phase_clocks(sfx_pen* h, int32_t B, int32_t* clocks_host);
 
 

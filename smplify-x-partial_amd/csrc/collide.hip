@@ -24,8 +24,8 @@
 //   k_pen_list /  offsets and ranks turn the partner lists (appended in scheduling order) into the
 //   k_pen_rank    frame's pair list -- triangles ascending, partners ascending -- which fixes every
 //                 later summation order.
-//   k_pen_eval    one lane per ORDERED pair of that list: conic distance field evaluated with
-//                 forward-mode dual numbers -- the lane differentiates with respect to the OWNER's 9
+//   k_pen_eval    one lane per ORDERED pair of that list: conic distance field and its adjoint, written out in
+//                 reverse mode (collide_field.h) -- the lane differentiates with respect to the OWNER's 9
 //                 coordinates only, once as receiver geometry and once as intruding points -- so
 //                 every number has one owner: no atomics in the arithmetic, results independent of
 //                 scheduling and of batch composition, and the work is balanced over the chip however
@@ -33,12 +33,14 @@
 //   k_pen_facesum / k_pen_gather   per-triangle sums over the pair ranges; vertex gradient = fixed-order
 //                 sum over the incident triangle corners (CSR); frame loss = triangles in index order; for a fitting batch
 //                 the same lane writes d v_posed = T^T g, the operand of the adjoint GEMM (lbs_adjoint.hip).
-// Ten launches per evaluation (twelve + two memsets until round 4: the accumulators of the grid build are left empty by
-// k_pen_g3 for the next evaluation instead of by a kernel of their own, and the per-column "wanted" flags are kept by the
-// fitting loop's tick kernel).
+// Ten launches per evaluation (pen_eval_cols: g1, g2, g3, walk, walk2, list, rank, eval, facesum, gather; nine beyond
+// PEN_FLAT_MAXB meshes, where no chunks are queued for k_pen_walk2).  Twelve + two memsets until round 4: the accumulators of the
+// grid build are left empty by k_pen_g3 for the next evaluation instead of by a kernel of their own, and the per-column "wanted"
+// flags are kept by the fitting loop's tick kernel.  The layout of the diagnostics (P.stats, P.work): collide_slots.h.
 #include "../../include/sfx.h"
 #include "sfx_internal.h"
 #include "collide_host.h"
+#include "collide_slots.h"
 #include "wave_ops.h"
 
 #include <algorithm>
@@ -51,11 +53,6 @@
 #define PEN_GRID_INTS ((((PEN_CELLS + 1) + 3) / 4) * 4)
 #define PEN_SPAN 8              // cells per axis one triangle may be entered in (a sane triangle spans 1-3; an exploded
                                 // mesh -- diverged fit, NaN / huge coordinates -- must not turn into 10^9 cell visits)
-#ifdef PEN_COUNT
-#define PEN_STATS 32      // diagnostic build: room for the walk counters
-#else
-#define PEN_STATS 16
-#endif
 #define PEN_MAX_WALK 2048        // entries an entry looks ahead in its bucket before it gives up (crowded cells of a sane mesh hold hundreds:
                                 // 418 on the synthetic surface).  A diverged fit folds the mesh into a few cells of 10^4 entries; walking
                                 // them out took 7-8 ms per evaluation and held up the whole batch (3 % of the launches of a 256-frame fit,
@@ -92,7 +89,6 @@ struct PenDev {
     int2* entries;             // [B][ent_cap] (triangle | part << 24 | lz << 30, packed cell coordinates | lx << 30 | ly << 31), sorted by bucket;
                                //              lx, ly, lz: the cell holds the low corner of the triangle's box on that axis
     int2* cand;                // [B][ent_cap] (round 4) one record per (surviving triangle, cell its box touches), any order: the entry record k_pen_g3 sorts
-    int4* tlist;               // [B][F] (unused since round 4: k_pen_g2 emits the candidate records itself)
     int* tcount;               // [B][16] (one cache line each) number of survivors (k_pen_g3 leaves 0 behind, k_pen_g2 reserves ranges)
     int* pbox;                 // [B][64][6] bounding box of every part, order-preserving ints (k_pen_g1; reset per evaluation)
     float* gpart;              // [B][PEN_GW][8] per workgroup of k_pen_g1: frame box lo / hi, extent sum
@@ -112,7 +108,7 @@ struct PenDev {
     int* ptotal;               // [B] ordered pairs in the list
     int* cells;                // [B][PEN_CELLS + 1] bucket END offsets into entries ([PEN_CELLS] = number of entries)
     float* gridp;              // [B][4] low corner of the frame's box, 1 / cell size
-    int* stats;                // [B][PEN_STATS]: pairs (ordered), dropped partners, overflow of entries, cells, phase clocks
+    int* stats;                // [B][PEN_STATS] diagnostics of the mesh's latest evaluation: the slots of PenStat (collide_slots.h)
     int2* wq;                  // [B][wq_cap] chunks of the pair tests beyond a block's first 64 steps: (first entry of the block, chunk k)
     int* wqn;                  // [B] chunks queued (k_pen_g3 -> 0, k_pen_walk appends, k_pen_walk2 consumes)
     int wq_cap;
@@ -126,8 +122,6 @@ struct PenDev {
     int* heavy;                // [B] 1 = this evaluation of the column goes through the general kernels (crowded grid / too many pairs for one workgroup's LDS)
     int* hlist;                // [B] the heavy columns of this evaluation, any order
     int* nheavy;               // [1] their number (k_pen_g1 -> 0, k_pen_narrow appends)
-    float* wbox;               // [B][n_clus][6] boxes of the clusters of 64 consecutive triangles (k_pen_g1: one DPP reduction per wavefront)
-    const unsigned long long* cpm;   // [n_clus] parts present in a cluster, one bit each (static)
     int n_clus;                // (F + 63) / 64
     int* rb;                   // [B][n_clus] the blocks of 64 consecutive triangles of a column that have partners, ascending (k_pen_list -> k_pen_rank)
     int* nrb;                  // [B] their number
@@ -139,8 +133,7 @@ struct PenDev {
     int2* pbuf;                // [B][pf_cap] accepted pairs of a frame on the fast path, any order (the partner-list buffer: unused there)
     int pf_cap;                // min(PEN_FP, F * pcap / 2)
     int fast_ok;               // the mesh fits the per-frame kernel's LDS layout (F^2 < 2^32: 32-bit sort keys; bit sets and vertex list in 64 KB)
-    unsigned long long* work;  // [6] process-wide counts since sfx_pen_work_reset: grid entries, ordered pairs, column evaluations, surviving triangles,
-                               //     triangles with more partners than the lists hold (2 x max_collisions: arrival order decides there), bucket walks cut short
+    unsigned long long* work;  // [PEN_WORK_SLOTS] process-wide counts since sfx_pen_work_reset: the slots of PenWork (collide_slots.h)
 };
 
 // Which columns a kernel of the general path works on.  hlist == NULL (the ten-kernel form, SFX / sfx_debug_pen_form 0): column
@@ -160,32 +153,45 @@ __device__ __forceinline__ int pen_sel_first(const PenSel& s, const int row) { r
 #include "collide_pairs.h"
 #include "collide_eval.h"
 
+// ---- launching: LDS sizes, reservations, the point2plane instance of a kernel
+#define PEN_LIST_LDS_MAX (160 * 1024 - 8192)      // k_pen_list stages a mesh's counts and "has pairs" bits: (F + hasp_words) ints
+#define PEN_P2P(kernel, P) ((P).p2p ? kernel<true> : kernel<false>)
+static size_t pen_g3_lds() { return (size_t)(PEN_GRID_INTS + PEN_CELLS) * sizeof(int); }
+static size_t pen_narrow_lds(const PenDev& P) { return (size_t)(2 * PEN_FP + 2 * P.hasp_words + (P.V + 31) / 32 + P.V) * sizeof(int); }
+// dynamic LDS beyond 64 KB has to be reserved per kernel and device: once per handle, on the device it is created on
+static bool pen_reserve_lds() {
+    const auto ok = [](const void* k, size_t bytes) { return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess; };
+    return ok((const void*)k_pen_list, PEN_LIST_LDS_MAX) && ok((const void*)k_pen_g3, pen_g3_lds()) &&
+           ok((const void*)k_pen_narrow<false>, 150 * 1024) && ok((const void*)k_pen_narrow<true>, 150 * 1024);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Work actually done by the term since the last reset, counted on the device (one atomic per column evaluation): what the
 // benchmark's byte model of the step is computed from (bench.py roofline_pen) instead of "typical" constants.
-static unsigned long long* g_pen_work = nullptr;      // device [4], process-wide (shared by every handle)
+static unsigned long long* g_pen_work = nullptr;      // device [PEN_WORK_SLOTS], process-wide (shared by every handle)
 static unsigned long long* pen_work_buffer() {
     if (!g_pen_work) {
-        if (hipMalloc((void**)&g_pen_work, 16 * sizeof(unsigned long long)) != hipSuccess) { g_pen_work = nullptr; return nullptr; }
-        hipMemset(g_pen_work, 0, 16 * sizeof(unsigned long long));
+        if (hipMalloc((void**)&g_pen_work, PEN_WORK_SLOTS * sizeof(unsigned long long)) != hipSuccess) { g_pen_work = nullptr; return nullptr; }
+        if (hipMemset(g_pen_work, 0, PEN_WORK_SLOTS * sizeof(unsigned long long)) != hipSuccess) { (void)hipFree(g_pen_work); g_pen_work = nullptr; }
     }
     return g_pen_work;
 }
+// n counters from slot `first` on -> host (zeros while no handle has made the buffer)
+static int pen_work_read(int first, int n, int64_t* out) {
+    if (!out) { sfx_set_error("null argument"); return -1; }
+    for (int i = 0; i < n; ++i) out[i] = 0;
+    if (!g_pen_work) return 0;
+    unsigned long long h[PEN_WORK_SLOTS];
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(h, g_pen_work + first, (size_t)n * sizeof(h[0]), hipMemcpyDeviceToHost) != hipSuccess) { sfx_set_error("device error"); return -4; }
+    for (int i = 0; i < n; ++i) out[i] = (int64_t)h[i];
+    return 0;
+}
 extern "C" int sfx_pen_work_reset(void) {
     if (!pen_work_buffer()) { sfx_set_error("out of device memory"); return -2; }
-    if (hipDeviceSynchronize() != hipSuccess || hipMemset(g_pen_work, 0, 16 * sizeof(unsigned long long)) != hipSuccess) { sfx_set_error("device error"); return -4; }
+    if (hipDeviceSynchronize() != hipSuccess || hipMemset(g_pen_work, 0, PEN_WORK_SLOTS * sizeof(unsigned long long)) != hipSuccess) { sfx_set_error("device error"); return -4; }
     return 0;
 }
-extern "C" int sfx_pen_work_get(int64_t* out /* [6] */) {
-    if (!out) { sfx_set_error("null argument"); return -1; }
-    for (int i = 0; i < 6; ++i) out[i] = 0;
-    if (!g_pen_work) return 0;
-    if (hipDeviceSynchronize() != hipSuccess) { sfx_set_error("device error"); return -4; }
-    unsigned long long h[6];
-    if (hipMemcpy(h, g_pen_work, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) { sfx_set_error("device error"); return -4; }
-    for (int i = 0; i < 6; ++i) out[i] = (int64_t)h[i];
-    return 0;
-}
+extern "C" int sfx_pen_work_get(int64_t* out /* [PEN_WORK_PUBLIC] */) { return pen_work_read(0, PEN_WORK_PUBLIC, out); }
 
 #ifndef PEN_SEL_ROWS
 #define PEN_SEL_ROWS 64            // rows of the launches that loop over the list of wanted columns
@@ -208,6 +214,7 @@ extern "C" int sfx_pen_create(int32_t V, int32_t F, const int32_t* faces, const 
     if (!faces || !out || V < 3 || F < 1 || max_batch < 1 || max_collisions < 1) { sfx_set_error("bad arguments"); return -1; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { sfx_set_error("no HIP device: libsfx has no CPU fallback"); return -3; }
+    if (!pen_reserve_lds()) { sfx_set_error("cannot reserve LDS for k_pen_list / k_pen_g3 / k_pen_narrow"); return -2; }
     std::unique_ptr<sfx_pen> h(new sfx_pen());      // (a refusal below releases it, device memory included)
     PenDev& P = h->P;
     P.V = V; P.F = F; P.cap = max_collisions; h->Bmax = max_batch;
@@ -246,7 +253,7 @@ extern "C" int sfx_pen_create(int32_t V, int32_t F, const int32_t* faces, const 
     const size_t B = max_batch;
     P.ent_cap = F * 32;
     P.aabb = h->mem.zeros<float>(B * F * 6); P.entries = h->mem.zeros<int2>(B * P.ent_cap);
-    P.tlist = nullptr; P.tcount = h->mem.zeros<int>(B * 16);
+    P.tcount = h->mem.zeros<int>(B * 16);
     P.cand = h->mem.zeros<int2>(B * (size_t)P.ent_cap);
     {   // part boxes start EMPTY (k_pen_g3 leaves them empty again after every evaluation)
         std::vector<int> pb(B * 64 * 6);
@@ -268,7 +275,6 @@ extern "C" int sfx_pen_create(int32_t V, int32_t F, const int32_t* faces, const 
     h->form = g_pen_form;
 #endif
     P.n_clus = (F + 63) / 64;
-    P.cpm = nullptr; P.wbox = nullptr;        // (cluster boxes: only round 5's k_pen_frame read them)
     P.heavy = h->mem.zeros<int>(B); P.hlist = h->mem.zeros<int>(B); P.nheavy = h->mem.zeros<int>(1); P.pcnt = h->mem.zeros<int>(B);
     P.wl = h->mem.zeros<int>(B); P.nw = h->mem.zeros<int>(1); P.rb = h->mem.zeros<int>((size_t)B * P.n_clus); P.nrb = h->mem.zeros<int>(B); P.lq = h->mem.zeros<int>((size_t)B * F); P.nlq = h->mem.zeros<int>(B);
     P.pbuf = reinterpret_cast<int2*>(P.partners);         // (the partner lists are unused on the fast path)
@@ -305,14 +311,7 @@ extern "C" void sfx_pen_destroy(sfx_pen* h) {
 // the kernels of one evaluation for the columns [0, B) of the view P0 (the handle's buffers, or a branch's share of them: pen_view)
 static int pen_eval_cols(sfx_pen* h, const PenDev& P0, int32_t B, const float* verts_dev, float sigma, int32_t penalize_outside,
                          float* loss_dev, float* dverts_dev, const int* want_dev, const PenAdjPrep* prep, int* over_dev, hipStream_t s) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)k_pen_list, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8192) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_pen_g3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((PEN_GRID_INTS + PEN_CELLS) * sizeof(int))) != hipSuccess) {
-            sfx_set_error("cannot reserve LDS for k_pen_list / k_pen_g3"); return -2; }
-        attr_set = true;
-    }
-    if ((size_t)(P0.F + P0.hasp_words) * sizeof(int) > 160 * 1024 - 8192) { sfx_set_error("mesh of %d faces: k_pen_list stages the counts in LDS (<= 38 k faces)", P0.F); return -1; }
+    if ((size_t)(P0.F + P0.hasp_words) * sizeof(int) > PEN_LIST_LDS_MAX) { sfx_set_error("mesh of %d faces: k_pen_list stages the counts in LDS (<= 38 k faces)", P0.F); return -1; }
     PenAdjPrep ap{};
     if (prep) ap = *prep;
 #ifdef SFX_LAB       // A/B measurement switches of the lab build (same pair set, same numbers either way): include/sfx_lab.h
@@ -342,7 +341,7 @@ static int pen_eval_cols(sfx_pen* h, const PenDev& P0, int32_t B, const float* v
     // grid build (the cross-workgroup accumulators -- part boxes, survivor counts -- are left empty by k_pen_g3 of the previous evaluation)
     hipLaunchKernelGGL(k_pen_g1, dim3(PEN_GW, (B + 7) & ~7), dim3(PEN_T), 0, s, P0, verts_dev, want_dev, (float*)nullptr, (float*)nullptr, 0, B, listed ? loss_dev : (float*)nullptr);
     hipLaunchKernelGGL(k_pen_g2, dim3(PEN_GW, (B + 7) & ~7), dim3(PEN_T), 0, s, P0, want_dev, B);
-    hipLaunchKernelGGL(k_pen_g3, dim3(B), dim3(PEN_T), (size_t)(PEN_GRID_INTS + PEN_CELLS) * sizeof(int), s, P0, want_dev);
+    hipLaunchKernelGGL(k_pen_g3, dim3(B), dim3(PEN_T), pen_g3_lds(), s, P0, want_dev);
     {
         PenDev Pw = P0;
         const bool queued = B <= PEN_FLAT_MAXB && !chunks_off;
@@ -357,11 +356,8 @@ static int pen_eval_cols(sfx_pen* h, const PenDev& P0, int32_t B, const float* v
         hipLaunchKernelGGL(k_pen_rank, dim3(PEN_RANK_FLAT + PEN_RANK_HELPERS), dim3(256), rank_lds + (size_t)(B + 1) * sizeof(int), s, P0, all, cap_pad, B);
     else hipLaunchKernelGGL(k_pen_rank, dim3(rank_rows, RY), dim3(256), rank_lds, s, P0, cw, cap_pad, 0);
     if (B <= PEN_FLAT_MAXB && !flat_off)
-        { if (P0.p2p) hipLaunchKernelGGL(k_pen_eval<true>, dim3(PEN_FLAT_BLOCKS), dim3(256), (size_t)(B + 1) * sizeof(int), s, P0, verts_dev, sigma, penalize_outside, B, 1, all);
-          else hipLaunchKernelGGL(k_pen_eval<false>, dim3(PEN_FLAT_BLOCKS), dim3(256), (size_t)(B + 1) * sizeof(int), s, P0, verts_dev, sigma, penalize_outside, B, 1, all); }
-    else
-        { if (P0.p2p) hipLaunchKernelGGL(k_pen_eval<true>, dim3(PEN_EVAL_BLOCKS, B), dim3(256), 0, s, P0, verts_dev, sigma, penalize_outside, B, 0, all);
-          else hipLaunchKernelGGL(k_pen_eval<false>, dim3(PEN_EVAL_BLOCKS, B), dim3(256), 0, s, P0, verts_dev, sigma, penalize_outside, B, 0, all); }
+        hipLaunchKernelGGL(PEN_P2P(k_pen_eval, P0), dim3(PEN_FLAT_BLOCKS), dim3(256), (size_t)(B + 1) * sizeof(int), s, P0, verts_dev, sigma, penalize_outside, B, 1, all);
+    else hipLaunchKernelGGL(PEN_P2P(k_pen_eval, P0), dim3(PEN_EVAL_BLOCKS, B), dim3(256), 0, s, P0, verts_dev, sigma, penalize_outside, B, 0, all);
     hipLaunchKernelGGL(k_pen_facesum, dim3(PEN_EVAL_BLOCKS, RY), dim3(256), 0, s, P0, cw);
     // (the gather keeps a row per column: 41 workgroups per column leave few to be turned away, and rows that loop cost it its p90 --
     //  48 -> 64 us where most columns carry the term)
@@ -435,16 +431,11 @@ extern "C" int sfx_pen_eval_pairs(sfx_pen* h, int32_t B, const float* verts_dev,
     if (!h->P.fast_ok) { sfx_set_error("mesh too large for the stand-alone pair evaluation (one workgroup holds a mesh's bit sets and vertex list in LDS: V + F / 16 <= %d; F < 65536)", PEN_GRID_INTS); return -1; }
     h->last_B = B;
     hipStream_t s = (hipStream_t)stream;
-    const size_t narrow_lds = (size_t)(2 * PEN_FP + 2 * h->P.hasp_words + (h->P.V + 31) / 32 + h->P.V) * sizeof(int);
-    if (hipFuncSetAttribute((const void*)k_pen_narrow<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_pen_narrow<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) {
-        sfx_set_error("cannot reserve LDS for k_pen_narrow"); return -2; }
     PenDev Pl = h->P;
     Pl.over = nullptr;
     hipLaunchKernelGGL(k_pen_pairs_in, dim3(B), dim3(PEN_T), 0, s, h->P, pairs_dev, n_pairs, dverts_dev, dtri_dev);
     PenAdjPrep ap{};
-    if (h->P.p2p) hipLaunchKernelGGL(k_pen_narrow<true>, dim3(B), dim3(PEN_T), narrow_lds, s, Pl, verts_dev, sigma, penalize_outside, dverts_dev, loss_dev, (const int*)nullptr, ap, 0);
-    else hipLaunchKernelGGL(k_pen_narrow<false>, dim3(B), dim3(PEN_T), narrow_lds, s, Pl, verts_dev, sigma, penalize_outside, dverts_dev, loss_dev, (const int*)nullptr, ap, 0);
+    hipLaunchKernelGGL(PEN_P2P(k_pen_narrow, Pl), dim3(B), dim3(PEN_T), pen_narrow_lds(Pl), s, Pl, verts_dev, sigma, penalize_outside, dverts_dev, loss_dev, (const int*)nullptr, ap, 0);
     if (dtri_dev) hipLaunchKernelGGL(k_pen_dtri_out, dim3(32, B), dim3(256), 0, s, h->P, dtri_dev);
     if (hipGetLastError() != hipSuccess) { sfx_set_error("penetration kernels failed to launch"); return -4; }
     int nh = 0;
@@ -458,13 +449,7 @@ int sfx_pen_stats_from(const int* stats_dev, int n, int32_t* stats_host) {
     if (hipDeviceSynchronize() != hipSuccess) { sfx_set_error("device error"); return -4; }
     std::vector<int> st((size_t)n * PEN_STATS);
     if (hipMemcpy(st.data(), stats_dev, st.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { sfx_set_error("device error"); return -4; }
-    for (int i = 0; i < n; ++i) {
-        const int* r = &st[(size_t)i * PEN_STATS];
-        // r[15]: ordered pairs in the list that only one of the two triangles kept (max_collisions cut the other's list):
-        // they contribute nothing and count as dropped
-        stats_host[i * 4 + 0] = r[0] - r[15]; stats_host[i * 4 + 1] = r[1] + r[15];
-        stats_host[i * 4 + 2] = r[2]; stats_host[i * 4 + 3] = r[13];      // [3]: walks cut short at PEN_MAX_WALK entries (0 on a sane mesh)
-    }
+    for (int i = 0; i < n; ++i) pen_public_stats(&st[(size_t)i * PEN_STATS], stats_host + i * 4);
     return 0;
 }
 int sfx_pen_stats_stride(void) { return PEN_STATS; }

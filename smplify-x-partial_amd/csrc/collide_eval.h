@@ -149,7 +149,7 @@ void k_pen_eval(PenDev P, const float* __restrict__ verts, float sigma, int pena
         }
         {   // pairs kept by one side only: counted as dropped (stats), contribute nothing
             const unsigned long long dead = __ballot(valid && !sym);
-            if (dead && lane == 0) atomicAdd(&P.stats[b * PEN_STATS + 15], __popcll(dead));
+            if (dead && lane == 0) atomicAdd(&P.stats[b * PEN_STATS + PEN_ST_ONE_SIDED], __popcll(dead));
         }
         float v[10];
         pen_pair_eval<P2P>(P, vb, f, g, sym, sigma, penalize_outside, v);
@@ -409,11 +409,13 @@ __device__ __forceinline__ void pen_narrow(const PenDev& P, const int b, const i
         T_ = ptot;
 #pragma unroll
         for (int u = 0; u < 16; ++u) if (u < per && kp[u]) keys[pos++] = kk[u];
-        if (t == 0) { P.ptotal[b] = T_; st[0] = T_; st[1] = (int)cut_all; if (P.over) P.over[b] = st[13] > 0 ? 1 : 0;      // (a cut bucket walk: pairs missing, order dependent)
-                      if (P.work) { atomicAdd(&P.work[1], (unsigned long long)T_); if (st[13] > 0) atomicAdd(&P.work[5], (unsigned long long)st[13]); } }
+        if (t == 0) { P.ptotal[b] = T_; st[PEN_ST_PAIRS] = T_; st[PEN_ST_DROPPED] = (int)cut_all;
+                      if (P.over) P.over[b] = st[PEN_ST_WALKS_CUT] > 0 ? 1 : 0;      // (a cut bucket walk: pairs missing, order dependent)
+                      if (P.work) { atomicAdd(&P.work[PEN_WK_PAIRS], (unsigned long long)T_);
+                                    if (st[PEN_ST_WALKS_CUT] > 0) atomicAdd(&P.work[PEN_WK_WALKS_CUT], (unsigned long long)st[PEN_ST_WALKS_CUT]); } }
     }
     __syncthreads();
-    mark();                                     // [7] D: pair list
+    mark();                                     // PEN_CLK_LIST: D, pair list
     const int T = T_;
     {   // the list as the diagnostics read it (sfx_pen_pairs)
         int* pown = P.pown + (size_t)b * P.pair_cap; int* plist = P.plist + (size_t)b * P.pair_cap;
@@ -445,8 +447,8 @@ __device__ __forceinline__ void pen_narrow(const PenDev& P, const int b, const i
     }
     __threadfence_block();
     __syncthreads();
-    if (t == 0) st[15] = (*L.dead);
-    mark();                                     // [8] E: pair evaluation
+    if (t == 0) st[PEN_ST_ONE_SIDED] = (*L.dead);
+    mark();                                     // PEN_CLK_EVAL: E, pair evaluation
     // ---------------------------------------------------------------- F: per-triangle sums; which triangles / vertices carry a gradient
     for (int i = t; i < T; i += PEN_T) {
         const unsigned k = keys[i];
@@ -462,7 +464,7 @@ __device__ __forceinline__ void pen_narrow(const PenDev& P, const int b, const i
     }
     __threadfence_block();
     __syncthreads();
-    mark();                                     // [9] F: per-triangle sums
+    mark();                                     // PEN_CLK_SUMS: F, per-triangle sums
     // ---------------------------------------------------------------- G: vertex gradients, d v_posed, the frame's loss
     {
         int nv = 0;
@@ -484,7 +486,7 @@ __device__ __forceinline__ void pen_narrow(const PenDev& P, const int b, const i
         __syncthreads();
         if (t == 0) loss_out[b] = ((red[0] + red[1]) + red[2]) + red[3];
     }
-    mark();                                     // [10] G: vertices, loss
+    mark();                                     // PEN_CLK_VERTS: G, vertices, loss
 }
 
 // Round 5's default form: the grid build and the pair tests stay spread over the chip (k_pen_g1 / g2 / g3, k_pen_walk / walk2 --
@@ -503,29 +505,38 @@ void k_pen_narrow(PenDev P, const float* __restrict__ verts, const float sigma, 
     __shared__ int s_dead;
     const int b = blockIdx.x, t = threadIdx.x;
     int* st = P.stats + b * PEN_STATS;
+#ifdef SFX_LAB      // the stamps of phases D-G and their sums have lab readers only (sfx_pen_phase_clocks, sfx_debug_pen_phase_ticks)
     const long long t_start = wall_clock64();
-    int n_mark = 3;                             // (stats[7..10]: the stamps of phases D-G)
-    auto mark = [&]() { if (t == 0) st[4 + n_mark] = (int)(wall_clock64() - t_start); ++n_mark; };
-    const int wanted = want ? want[b] : 1, npairs = P.pcnt[b], overflow = st[2], cut = st[13];
+    int n_mark = PEN_CLK_LIST;                  // (clock columns PEN_CLK_LIST .. PEN_CLK_VERTS)
+    auto mark = [&]() { if (t == 0) st[PEN_ST_CLOCK0 + n_mark] = (int)(wall_clock64() - t_start); ++n_mark; };
+#else
+    auto mark = []() {};
+#endif
+    const int wanted = want ? want[b] : 1, npairs = P.pcnt[b], overflow = st[PEN_ST_OVERFLOW], cut = st[PEN_ST_WALKS_CUT];
     if (t == 0) { P.heavy[b] = 0; P.wqn[b] = 0; s_dead = 0; }      // (the chunk queue is consumed: the general kernels start from an empty one)
     if (!wanted || overflow != 0) {             // no collision weight in this column's stage / grid overflow (reported): no pairs
         if (t == 0) { loss_out[b] = 0.f; if (P.over) P.over[b] = 0; }
         return;
     }
     if (force_heavy || !P.fast_ok || npairs > P.pf_cap) {
-        if (t == 0) { P.heavy[b] = 1; P.hlist[atomicAdd(P.nheavy, 1)] = b; st[13] = 0; }      // (the general kernels count the cut walks of their own pass)
+        if (t == 0) { P.heavy[b] = 1; P.hlist[atomicAdd(P.nheavy, 1)] = b; st[PEN_ST_WALKS_CUT] = 0; }      // (the general kernels count the cut walks of their own pass)
         return;
     }
     (void)cut;
     __syncthreads();
+#ifdef SFX_LAB
     const int t_entry = (int)(wall_clock64() - t_start);
+#endif
     pen_narrow<P2P>(P, b, npairs, PenNarrowLds{reinterpret_cast<unsigned*>(lds), reinterpret_cast<unsigned*>(lds + 2 * PEN_FP), slice, red, &s_dead},
                     verts, sigma, penalize_outside, dverts, loss_out, ap, mark);
+#ifdef SFX_LAB
     if (t == 0 && P.work) {                     // (debug: sfx_debug_pen_phase_ticks)
-        const int s7 = st[7], s8 = st[8], s9 = st[9], s10 = st[10];
-        atomicAdd(&P.work[8], (unsigned long long)t_entry); atomicAdd(&P.work[9], (unsigned long long)(s7 - t_entry));
-        atomicAdd(&P.work[10], (unsigned long long)(s8 - s7)); atomicAdd(&P.work[11], (unsigned long long)(s9 - s8));
-        atomicAdd(&P.work[12], (unsigned long long)(s10 - s9)); atomicAdd(&P.work[13], 1ull); atomicAdd(&P.work[14], (unsigned long long)st[0]);
+        const int* ck = st + PEN_ST_CLOCK0;
+        const int sd = ck[PEN_CLK_LIST], se = ck[PEN_CLK_EVAL], sf = ck[PEN_CLK_SUMS], sg = ck[PEN_CLK_VERTS];
+        atomicAdd(&P.work[PEN_WKN_ENTRY], (unsigned long long)t_entry); atomicAdd(&P.work[PEN_WKN_LIST], (unsigned long long)(sd - t_entry));
+        atomicAdd(&P.work[PEN_WKN_EVAL], (unsigned long long)(se - sd)); atomicAdd(&P.work[PEN_WKN_SUMS], (unsigned long long)(sf - se));
+        atomicAdd(&P.work[PEN_WKN_VERTS], (unsigned long long)(sg - sf)); atomicAdd(&P.work[PEN_WKN_EVALS], 1ull); atomicAdd(&P.work[PEN_WKN_PAIRS], (unsigned long long)st[PEN_ST_PAIRS]);
     }
+#endif
 }
 

@@ -106,17 +106,13 @@ void k_pen_g1(PenDev P, const float* __restrict__ verts, const int* __restrict__
             }
             if (valid) ext_sum += fmaxf(fmaxf(c[0] - a[0], c[1] - a[1]), c[2] - a[2]);
             // part boxes: consecutive triangles mostly belong to one part -- a complete wavefront of one part reduces its 64
-            // boxes on DPP and one lane updates the part's box.  The wavefront's own box -- a cluster of 64 consecutive triangles --
-            // was kept as well in round 5 (k_pen_frame culled whole clusters against the part boxes; P.wbox is NULL since round 6).
+            // boxes on DPP and one lane updates the part's box.
             const int s0 = __builtin_amdgcn_readfirstlane(seg[u]);
             const bool one_part = __ballot(!valid || seg[u] == s0) == ~0ull;
 #pragma unroll
             for (int e = 0; e < 3; ++e) {
                 const float wl = -wave_max_dpp(-a[e]), wh = wave_max_dpp(c[e]);
-                if ((t & 63) == 0) {
-                    if (P.wbox) { float* wb = P.wbox + ((size_t)b * P.n_clus + (f >> 6)) * 6; wb[e] = wl; wb[3 + e] = wh; }
-                    if (one_part) { atomicMin(&pbox[s0 * 6 + e], pen_ford(wl)); atomicMax(&pbox[s0 * 6 + 3 + e], pen_ford(wh)); }
-                }
+                if ((t & 63) == 0 && one_part) { atomicMin(&pbox[s0 * 6 + e], pen_ford(wl)); atomicMax(&pbox[s0 * 6 + 3 + e], pen_ford(wh)); }
                 if (!one_part && valid) { atomicMin(&pbox[seg[u] * 6 + e], pen_ford(a[e])); atomicMax(&pbox[seg[u] * 6 + 3 + e], pen_ford(c[e])); }
             }
         }
@@ -133,7 +129,7 @@ void k_pen_g1(PenDev P, const float* __restrict__ verts, const int* __restrict__
     if (t < 7) P.gpart[((size_t)b * PEN_GW + w) * 8 + t] = r[t];
 }
 
-// frame box, cell size, skip / near masks: what every workgroup of g2 / g3 / g5 needs (recomputed per workgroup, fixed order)
+// frame box, cell size, skip / near masks: what every workgroup of g2 / g3 needs (recomputed per workgroup, fixed order)
 struct PenGridCtx { float glo[3], ih; };
 __device__ __forceinline__ PenGridCtx pen_grid_ctx(const PenDev& P, const int b) {
     PenGridCtx c;
@@ -374,7 +370,7 @@ void k_pen_g3(PenDev P, const int* __restrict__ want) {
     int* cells = P.cells + (size_t)b * (PEN_CELLS + 1);
     if (t == 0) { P.wqn[b] = 0; P.pcnt[b] = 0; }      // (the pair tests' chunk queue and pair list of this mesh start empty)
     if (want && !want[b]) {                     // the frame's stage carries no collision weight: nothing to do
-        if (t == 0) { P.ptotal[b] = 0; cells[PEN_CELLS] = 0; st[0] = st[1] = st[2] = st[3] = 0; st[13] = 0; st[15] = 0; }
+        if (t == 0) { P.ptotal[b] = 0; cells[PEN_CELLS] = 0; st[PEN_ST_PAIRS] = st[PEN_ST_DROPPED] = st[PEN_ST_OVERFLOW] = st[PEN_ST_CELLS] = 0; st[PEN_ST_WALKS_CUT] = 0; st[PEN_ST_ONE_SIDED] = 0; }
         return;
     }
     const int F = P.F;
@@ -383,7 +379,7 @@ void k_pen_g3(PenDev P, const int* __restrict__ want) {
     const int NC_raw = P.tcount[b * 16 + 1];              // (triangle, cell) records k_pen_g2 listed
     const int NC = min(NC_raw, P.ent_cap);
     unsigned* pmask = reinterpret_cast<unsigned*>(cell_cnt + PEN_GRID_INTS);
-#ifdef PEN_COUNT    // diagnostic build: shader clocks at the phase boundaries -> stats[24..30] (cycles per phase, thread 0)
+#ifdef PEN_COUNT    // diagnostic build: shader clocks at the phase boundaries -> stats[PEN_ST_G3_CYCLES0 ...] (cycles per phase, thread 0)
     long long g3c[8]; int g3n = 0;
 #define G3MARK() do { g3c[g3n++] = clock64(); } while (0)
 #else
@@ -446,11 +442,12 @@ void k_pen_g3(PenDev P, const int* __restrict__ want) {
     G3MARK();
     int2* ent = P.entries + (size_t)b * P.ent_cap;
     const bool ent_ok = s_total <= P.ent_cap - 4 && NC_raw <= P.ent_cap;
-    if (t == 0) { st[2] = ent_ok ? 0 : max(s_total, NC_raw); st[3] = PEN_CELLS; st[13] = 0; st[14] = s_total; st[15] = 0; for (int q = 4; q < 13; ++q) st[q] = 0;
-                  for (int q = 16; q < PEN_STATS; ++q) st[q] = 0;
-                  if (P.work) { atomicAdd(&P.work[0], (unsigned long long)s_total); atomicAdd(&P.work[2], 1ull); atomicAdd(&P.work[3], (unsigned long long)NT); } }
+    if (t == 0) { st[PEN_ST_OVERFLOW] = ent_ok ? 0 : max(s_total, NC_raw); st[PEN_ST_CELLS] = PEN_CELLS; st[PEN_ST_WALKS_CUT] = 0; st[PEN_ST_ENTRIES] = s_total; st[PEN_ST_ONE_SIDED] = 0;
+                  for (int q = PEN_ST_CLOCK0; q < PEN_ST_WALKS_CUT; ++q) st[q] = 0;      // (the clock window below its two counts)
+                  for (int q = PEN_ST_CNT_WALKED; q < PEN_STATS; ++q) st[q] = 0;         // (PEN_COUNT's slots)
+                  if (P.work) { atomicAdd(&P.work[PEN_WK_ENTRIES], (unsigned long long)s_total); atomicAdd(&P.work[PEN_WK_COLUMNS], 1ull); atomicAdd(&P.work[PEN_WK_SURVIVORS], (unsigned long long)NT); } }
     if (!ent_ok) {       // grid too crowded for the entry buffer: report, produce no pairs
-        if (t == 0) { st[0] = 0; st[1] = 0; P.ptotal[b] = 0; cells[PEN_CELLS] = 0; }
+        if (t == 0) { st[PEN_ST_PAIRS] = 0; st[PEN_ST_DROPPED] = 0; P.ptotal[b] = 0; cells[PEN_CELLS] = 0; }
         return;
     }
     // scatter: the start offsets double as cursors, so bucket c ends up holding its END offset
@@ -471,7 +468,7 @@ void k_pen_g3(PenDev P, const int* __restrict__ want) {
     for (int c = t; c <= PEN_CELLS; c += PEN_T) cells[c] = cell_cnt[c];
     G3MARK();
 #ifdef PEN_COUNT
-    if (t == 0) for (int q = 1; q < g3n; ++q) st[23 + q] = (int)(g3c[q] - g3c[q - 1]);      // [24] init, [25] part masks, [26] histogram, [27] scan, [28] scatter, [29] copy
+    if (t == 0) for (int q = 1; q < g3n; ++q) st[PEN_ST_G3_CYCLES0 + q - 1] = (int)(g3c[q] - g3c[q - 1]);      // init, part masks, histogram, scan, scatter, copy
 #endif
 #undef G3MARK
 }

@@ -211,12 +211,12 @@ __device__ __forceinline__ void pen_walk_chunk(const PenDev& P, const int b, con
         const bool box = (O.ai[0] <= kh0) & (kl0 <= O.ai[3]) & (O.ai[1] <= kh1) & (kl1 <= O.ai[4]) & (O.ai[2] <= kh2) & (kl2 <= O.ai[5]);
         const unsigned klow = ((unsigned)h0.y >> 30) | (((unsigned)h0.x >> 28) & 4u);
         const bool own = (O.need & ~klow) == 0u;
-#ifdef PEN_COUNT    // diagnostic build: where do the candidates die?  stats[16..19] = walked, same cell, part mask passed, boxes overlap
+#ifdef PEN_COUNT    // diagnostic build: where do the candidates die?  stats[PEN_ST_CNT_*] = walked, same cell, part mask passed, boxes overlap
         {
             int* st = P.stats + b * PEN_STATS;
             const unsigned long long m0 = __ballot(act), m1 = __ballot(act & same), m2 = __ballot(act & same & coll), m3 = __ballot(act & same & coll & box);
-            if (lane == 0) { atomicAdd(&st[16], __popcll(m0)); atomicAdd(&st[17], __popcll(m1)); atomicAdd(&st[18], __popcll(m2)); atomicAdd(&st[19], __popcll(m3));
-                             atomicAdd(&st[20], 1); }      // [20] wavefront steps
+            if (lane == 0) { atomicAdd(&st[PEN_ST_CNT_WALKED], __popcll(m0)); atomicAdd(&st[PEN_ST_CNT_CELL], __popcll(m1)); atomicAdd(&st[PEN_ST_CNT_PARTS], __popcll(m2));
+                             atomicAdd(&st[PEN_ST_CNT_BOXES], __popcll(m3)); atomicAdd(&st[PEN_ST_CNT_STEPS], 1); }
         }
 #endif
         return act & same & coll & box & own;
@@ -280,7 +280,7 @@ void k_pen_walk(PenDev P, PenSel sel, int to_pbuf, int flatB) {
             int kmax = (dmax - 1) >> 6;                    // last chunk with a live step
             if (kmax >= PEN_MAX_CHUNK) {                   // a bucket of thousands of entries: a mesh that has collapsed into a few cells
                 kmax = PEN_MAX_CHUNK - 1;
-                if (lane == 0) atomicAdd(&P.stats[b * PEN_STATS + 13], 1);      // (reported: sfx_pen_stats, "walks cut short")
+                if (lane == 0) atomicAdd(&P.stats[b * PEN_STATS + PEN_ST_WALKS_CUT], 1);      // (reported: sfx_pen_stats, "walks cut short")
             }
             int pos = 0;
             if (lane == 0) pos = atomicAdd(&P.wqn[b], kmax);
@@ -376,7 +376,7 @@ void k_pen_list(PenDev P, PenSel sel) {
     __syncthreads();                                 // (the previous column's reads of the staging arrays are done)
     int* st = P.stats + b * PEN_STATS;
     unsigned* hasp = P.hasp + (size_t)b * P.hasp_words;
-    if (!pen_sel_on(sel, b) || st[2] != 0) {         // skipped frame / grid overflow: the grid build has zeroed the totals
+    if (!pen_sel_on(sel, b) || st[PEN_ST_OVERFLOW] != 0) {         // skipped frame / grid overflow: the grid build has zeroed the totals
         for (int w = t; w < P.hasp_words; w += PEN_T) hasp[w] = 0u;
         if (P.over && t == 0) P.over[b] = 0;
         if (t == 0) { P.nrb[b] = 0; P.nlq[b] = 0; }
@@ -458,17 +458,17 @@ void k_pen_list(PenDev P, PenSel sel) {
         }
         const float to = block_sum_fixed((float)n_over, red);
         const float ta = block_sum_fixed((float)n_arr, red);
-        if (t == 0) { const int tot = min(ptot, P.pair_cap); P.ptotal[b] = tot; st[0] = tot; st[1] = (int)to;
+        if (t == 0) { const int tot = min(ptot, P.pair_cap); P.ptotal[b] = tot; st[PEN_ST_PAIRS] = tot; st[PEN_ST_DROPPED] = (int)to;
                       // a mesh with thousands of such triangles has collapsed onto itself (a diverged fit on its way to NaN): looking at
                       // each of them again would cost milliseconds per evaluation for a term that means nothing there -- such a mesh
                       // keeps its first arrivals, as every overflowing list did until round 4, and is reported as order dependent
                       const bool rewalk = pen_can_rewalk(P) && ta <= (float)PEN_REWALK_MAX;
                       if (!rewalk) P.ovn[b * 2] = 0;
                       else if (ta > 0.f) P.ovm[1 + atomicAdd(&P.ovm[0], 1)] = b;      // (k_pen_rank drains the queues of the meshes listed here)
-                      if (P.over) P.over[b] = ((ta > 0.f && !rewalk) || st[13] > 0) ? 1 : 0;      // (lists beyond pcap are re-derived by k_pen_rank: pen_rewalk)
-                      if (P.work) { atomicAdd(&P.work[1], (unsigned long long)tot);
-                                    if (ta > 0.f) atomicAdd(&P.work[4], (unsigned long long)ta);
-                                    if (st[13] > 0) atomicAdd(&P.work[5], (unsigned long long)st[13]); } }
+                      if (P.over) P.over[b] = ((ta > 0.f && !rewalk) || st[PEN_ST_WALKS_CUT] > 0) ? 1 : 0;      // (lists beyond pcap are re-derived by k_pen_rank: pen_rewalk)
+                      if (P.work) { atomicAdd(&P.work[PEN_WK_PAIRS], (unsigned long long)tot);
+                                    if (ta > 0.f) atomicAdd(&P.work[PEN_WK_LONG], (unsigned long long)ta);
+                                    if (st[PEN_ST_WALKS_CUT] > 0) atomicAdd(&P.work[PEN_WK_WALKS_CUT], (unsigned long long)st[PEN_ST_WALKS_CUT]); } }
     }
     __syncthreads();
     for (int f = t; f < F; f += PEN_T) poff[f] = s_cnt[f];
@@ -851,9 +851,9 @@ void k_pen_rank(PenDev P, PenSel sel, int cap_pad, int flatB) {
     auto rank_report = [&]() {
         const long long rt2 = wall_clock64();
         if (lane == 0 && P.work && rt2 - rt0 > 4000) {      // wavefronts that took more than 40 us
-            atomicAdd(&P.work[8], 1ull); atomicAdd(&P.work[9], (unsigned long long)(rt1 - rt0)); atomicAdd(&P.work[10], (unsigned long long)rt_long);
-            atomicAdd(&P.work[11], (unsigned long long)(rt2 - rt1)); atomicAdd(&P.work[12], (unsigned long long)n_long); atomicAdd(&P.work[13], (unsigned long long)n_rew);
-            atomicAdd(&P.work[14], (unsigned long long)rt_ld); atomicAdd(&P.work[15], (unsigned long long)rt_short);
+            atomicAdd(&P.work[PEN_WKR_WAVES], 1ull); atomicAdd(&P.work[PEN_WKR_T_RANK], (unsigned long long)(rt1 - rt0)); atomicAdd(&P.work[PEN_WKR_T_LONG], (unsigned long long)rt_long);
+            atomicAdd(&P.work[PEN_WKR_T_REWALK], (unsigned long long)(rt2 - rt1)); atomicAdd(&P.work[PEN_WKR_N_LONG], (unsigned long long)n_long); atomicAdd(&P.work[PEN_WKR_N_REWALK], (unsigned long long)n_rew);
+            atomicAdd(&P.work[PEN_WKR_T_LOAD], (unsigned long long)rt_ld); atomicAdd(&P.work[PEN_WKR_T_SHORT], (unsigned long long)rt_short);
         }
     };
     __syncthreads();

@@ -1345,10 +1345,13 @@ class Penetration(capi.Handle):
         return _read_pairs(lambda cap, buf, n: self._lib.sfx_pen_pairs(self._h, int(mesh), cap, buf, n))
 
     def phase_clocks(self, B):
-        """Debug (LAB build): microseconds at the end of the broad phase's ten steps, grid entries (see sfx_pen_phase_clocks)."""
+        """Debug (LAB build): the clock window of the first B meshes' stats rows, [B, 11] (sfx_pen_phase_clocks; PenClockCol in
+        csrc/collide_slots.h).  Columns 3-6 (PEN_CLK_LIST, _EVAL, _SUMS, _VERTS): microseconds from k_pen_narrow's start to the
+        ends of its phases D-G -- 0 in form 0 and for a mesh handed to the general kernels.  Column 9 (PEN_CLK_WALKS_CUT) and
+        column 10 (PEN_CLK_ENTRIES) are counts, returned as they are.  Columns 0-2 and 7-8 have no writer: 0."""
         capi.need_lab("phase_clocks")
         out = np.zeros((B, 11), np.int32)
         capi.check(self._lib.sfx_pen_phase_clocks(self._h, int(B), capi.iptr(out)))
         res = out / 100.0
-        res[:, 10] = out[:, 10]
+        res[:, 9:] = out[:, 9:]
         return res

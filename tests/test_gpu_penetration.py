@@ -636,6 +636,32 @@ print(json.dumps({"loss": [float(x).hex() for x in loss.cpu().numpy()], "pairs":
     assert a == b, (a, b)
 
 
+@H.requires_lab()
+def test_phase_clocks_columns_are_the_documented_slots():
+    """The read-out of sfx_pen_phase_clocks as csrc/collide_slots.h documents it (PenClockCol): only k_pen_narrow stamps -- the
+    ends of its phases D-G in columns 3-6 -- columns 0-2 and 7-8 have no writer, column 9 is the count of cut walks sfx_pen_stats
+    reports and column 10 the grid entries the work counters sum.  Two overlapping spheres (offset 0.13, as in
+    test_two_spheres_loss_and_gradient: a few hundred pairs per mesh, which form 1 keeps in its per-column workgroup), B = 2."""
+    verts, faces, segm, parents = _two_spheres(0.13)
+    B = 2
+    vb = np.stack([verts + [0.01 * b, 0, 0] for b in range(B)]).astype(np.float32)
+    prev = engine.pen_form(1)
+    try:
+        pen = engine.Penetration(len(verts), faces, segm, parents, max_collisions=64, max_batch=B)
+        engine.pen_work_reset()
+        pen.eval(torch.tensor(vb, device="cuda"), 0.5, True)
+        pc, st, work = pen.phase_clocks(B), pen.stats(B), engine.pen_work_get()
+        pen.close()
+    finally:
+        engine.pen_form(prev)
+    print("phase clocks (us | counts):", pc.tolist(), "pairs", st["pairs"].tolist(), "entries", work["entries"])
+    assert pc.shape == (B, 11) and np.all(st["pairs"] > 100)
+    assert np.all(pc[:, [0, 1, 2, 7, 8]] == 0)
+    assert np.all(np.diff(pc[:, 3:7], axis=1) >= 0) and np.all(pc[:, 6] > 0)
+    assert np.array_equal(pc[:, 9], st["walks_cut"])
+    assert pc[:, 10].sum() == work["entries"] and work["entries"] > 0
+
+
 def test_operator_matches_the_reference_lines_golden():
     """The device operator against numbers the REFERENCE's own lines produced: tests/golden/objective_pen.npz holds
     SMPLifyLoss.forward's total with the collision weight at 0 and at 0.1 (fitting.py:437-455 over the CPU stand-ins of the absent

@@ -1,4 +1,6 @@
-import sys; sys.path.insert(0,'/root/repo')
+import os, sys
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 import numpy as np, torch, time
 from smplifyx_amd import engine, synthetic
 m = synthetic.make_synthetic_model(0, surface=("soup" not in sys.argv))

@@ -29,5 +29,6 @@ for scale in (0.0, 0.5, 1.0):
     st = pen.stats(B)
     print("pose scale %.1f: %.0f us/eval; pairs/frame mean %.0f max %d; %s; loss mean %.3g" % (
         scale, dt * 1e6, st["pairs"].mean(), st["pairs"].max(), {k: (int(v_.max()) if hasattr(v_, "max") else v_) for k, v_ in st.items()}, float(loss.mean())))
-    print("   broad-phase steps end at (us, frame 0 / max):", pen.phase_clocks(B)[0], pen.phase_clocks(B).max(0))
+    pc = pen.phase_clocks(B)      # (lab build; columns: PenClockCol in csrc/collide_slots.h)
+    print("   k_pen_narrow's phases D-G end at (us; 0 in form 0), walks cut, grid entries -- frame 0 / max:", pc[0, [3, 4, 5, 6, 9, 10]], pc[:, [3, 4, 5, 6, 9, 10]].max(0))
     pen.close()

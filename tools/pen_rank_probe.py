@@ -1,5 +1,6 @@
 import sys, os
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/tools')
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np, ctypes as C
 import _frames as TF
 from smplifyx_amd import engine, synthetic, driver, _capi

@@ -1,5 +1,6 @@
-import sys, numpy as np, torch, time
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/tests')
+import os, sys, numpy as np, torch, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 from smplifyx_amd import synthetic
 from oracle import penetration as OP
 m = synthetic.make_synthetic_model(0)

@@ -1,5 +1,6 @@
 import sys, os, numpy as np
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/tests'); sys.path.insert(0,'/root/repo/tools')
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "tools"))
 import bench as BB, _frames as FR
 from smplifyx_amd import synthetic, driver
 cfg = BB.build_cfg("body"); m = synthetic.make_synthetic_model(0)
