@@ -391,6 +391,44 @@ int  sfx_opt_get(sfx_opt* h, float* x_dev, float* grad_dev, float* result_host, 
 int  sfx_opt_trace(sfx_opt* h, int32_t capacity);
 int  sfx_opt_get_trace(sfx_opt* h, float* records, int32_t* counts);
 
+/* ---- the same optimiser for problems of up to 32768 variables (csrc/opt_wide.hip, csrc/lbfgs_wide.h) ---------
+ * B independent problems of N <= 32768 float32 variables each: the state machine of sfx_opt_* on a vector layer one workgroup
+ * (1024 threads) wide, one workgroup per problem, one evaluation per launch; dot products accumulated in float64 and rounded
+ * once, no atomics, a problem's bits depend on its own inputs only.  What a loss that couples frames needs -- one shape over
+ * a clip, a temporal smoothness term, per-vertex offsets -- and what the reference's LBFGS (lbfgs_ls.py:256-445), which has no
+ * size limit, takes as it is.  The contracts are those of sfx_opt_*, word for word.                                          */
+typedef struct sfx_opt_wide sfx_opt_wide;
+typedef struct sfx_opt_wide_cfg {
+    int32_t B, N;
+    int32_t n_groups; const int32_t* group_len; /* HOST, n_groups <= 256 lengths (read by sfx_opt_wide_create only): the tensors
+                                                  of `params`, as sfx_opt_cfg.group_len; 0 groups = one group of N */
+    int32_t maxiters; double ftol, gtol;       /* run_fitting (fitting.py:147-217); maxiters >= 1 */
+    float   lr;
+    double  tolerance_grad, tolerance_change;  /* negative = default 1e-5 / 1e-9; 0 is passed through */
+    int32_t max_iter, max_eval, history_size;  /* 0 = defaults: maxiters, max_iter * 5 / 4, 100 */
+    int32_t reuse_entry_eval;                  /* as sfx_opt_cfg.reuse_entry_eval (mode 0) */
+} sfx_opt_wide_cfg;
+/* Refused before any device memory is touched (-1): N outside 1..32768, B < 1, more than 256 groups, group lengths that do not
+ * sum to N, history_size outside 0..400.  -3: no HIP device.  -2: out of device memory (nothing stays allocated).  Device
+ * memory: 2 (history_size + 1) + 11 rows of N floats per problem (27.9 MB at N = 32768, history 100).                   */
+int  sfx_opt_wide_create(const sfx_opt_wide_cfg* cfg, sfx_opt_wide** out);
+void sfx_opt_wide_destroy(sfx_opt_wide* h);
+/* As sfx_opt_begin: mode 0 the whole run_fitting loop, mode 1 ONE LBFGS.step; resume = 1 continues the optimiser of the previous
+ * mode-1 run, 0 starts a fresh one and empties the trace.  x0_dev, x_trial_dev [B][N] (DEVICE, packed).  Enqueues only.   */
+int  sfx_opt_wide_begin(sfx_opt_wide* h, int32_t mode, int32_t resume, const float* x0_dev, float* x_trial_dev, void* stream);
+/* As sfx_opt_tell: consume loss_dev [B] and grad_dev [B][N] (DEVICE, packed) taken at the current trial points, write the next
+ * ones to x_trial_dev.  A problem that has finished is left alone: its loss and gradient are not read, its row of x_trial_dev
+ * -- its accepted point -- is not written.  Enqueues only, allocates nothing.                                              */
+int  sfx_opt_wide_tell(sfx_opt_wide* h, const float* loss_dev, const float* grad_dev, float* x_trial_dev, void* stream);
+/* Problems still running (HOST).  One readback of B status words; synchronises the stream.                                */
+int  sfx_opt_wide_active(sfx_opt_wide* h, int32_t* n_active_host, void* stream);
+/* As sfx_opt_get: accepted point x_dev [B][N] and gradient of the most recent consumed evaluation grad_dev [B][N] (DEVICE, may
+ * be NULL); per problem (HOST, may be NULL) result, evaluations consumed since the last fresh begin, status.  Synchronises. */
+int  sfx_opt_wide_get(sfx_opt_wide* h, float* x_dev, float* grad_dev, float* result_host, int32_t* evals_host, int32_t* status_host);
+/* As sfx_opt_trace / sfx_opt_get_trace: records of types 0, 1, 2.                                                         */
+int  sfx_opt_wide_trace(sfx_opt_wide* h, int32_t capacity);
+int  sfx_opt_wide_get_trace(sfx_opt_wide* h, float* records, int32_t* counts);
+
 /* ---- the objective on tensors the CALLER supplies (csrc/objective_ext.hip) -----------------------------------
  * Replaces `loss(body_model_output, camera=..., gt_joints=..., ...)` of the reference's closure (fitting.py:251-259) and what
  * `total_loss.backward()` walks behind it down to the loss's inputs, for B frames at once and for joints that came from

@@ -81,6 +81,16 @@ class OptCfg(C.Structure):
     ]
 
 
+class OptWideCfg(C.Structure):
+    """sfx_opt_wide_cfg: as OptCfg, with the group lengths behind a HOST pointer (up to 256 of them)."""
+    _fields_ = [
+        ("B", C.c_int32), ("N", C.c_int32), ("n_groups", C.c_int32), ("group_len", C.POINTER(C.c_int32)),
+        ("maxiters", C.c_int32), ("ftol", C.c_double), ("gtol", C.c_double), ("lr", C.c_float),
+        ("tolerance_grad", C.c_double), ("tolerance_change", C.c_double),
+        ("max_iter", C.c_int32), ("max_eval", C.c_int32), ("history_size", C.c_int32), ("reuse_entry_eval", C.c_int32),
+    ]
+
+
 class ObjectiveCfg(C.Structure):
     """sfx_objective_cfg: weights, flags and pose-prior form of SMPLifyLoss for sfx_objective_eval (pointers: DEVICE)."""
     _fields_ = [
@@ -173,6 +183,15 @@ SYMBOLS = {
     "sfx_opt_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, f32p, i32p, i32p]),
     "sfx_opt_trace": (C.c_int, [C.c_void_p, C.c_int32]),
     "sfx_opt_get_trace": (C.c_int, [C.c_void_p, f32p, i32p]),
+    # the same eight for problems of up to 32768 variables (csrc/opt_wide.hip): the same signatures but for the configuration
+    "sfx_opt_wide_create": (C.c_int, [C.POINTER(OptWideCfg), C.POINTER(C.c_void_p)]),
+    "sfx_opt_wide_destroy": (None, [C.c_void_p]),
+    "sfx_opt_wide_begin": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sfx_opt_wide_tell": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sfx_opt_wide_active": (C.c_int, [C.c_void_p, i32p, C.c_void_p]),
+    "sfx_opt_wide_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, f32p, i32p, i32p]),
+    "sfx_opt_wide_trace": (C.c_int, [C.c_void_p, C.c_int32]),
+    "sfx_opt_wide_get_trace": (C.c_int, [C.c_void_p, f32p, i32p]),
     # cfg, in, grads (or NULL), loss, stream
     "sfx_objective_eval": (C.c_int, [C.POINTER(ObjectiveCfg), C.POINTER(ObjectiveIn), C.POINTER(ObjectiveGrads), C.c_void_p, C.c_void_p]),
     # cfg, B, K, joints, rotation, translation, focal x / y, center, gt, init_count, conf, est_tz, loss, three gradients, stream

@@ -682,6 +682,7 @@ class BatchOptimizer(capi.Handle):
     history_size, tolerance_grad, tolerance_change (lbfgs_ls.LBFGS; defaults of oracle/lbfgs_machine.StageMachine, whose
     spellings history / tol_grad / tol_change are accepted too), reuse_entry_eval.  There is no CPU fallback."""
 
+    _PREFIX = "sfx_opt_"                    # the handle's symbols: _PREFIX + create / begin / tell / active / get / trace / get_trace
     _destroy = "sfx_opt_destroy"
     _ALIASES = dict(history="history_size", tol_grad="tolerance_grad", tol_change="tolerance_change")
     _STATE = "the optimiser's state"        # what lives on self.device, for the message that refuses a tensor elsewhere
@@ -692,30 +693,39 @@ class BatchOptimizer(capi.Handle):
         for k, v in hyper.items():
             k = self._ALIASES.get(k, k)
             if k not in h:
-                raise TypeError("BatchOptimizer: unknown hyper-parameter %r (known: %s)" % (k, ", ".join(sorted(h))))
+                raise TypeError("%s: unknown hyper-parameter %r (known: %s)" % (type(self).__name__, k, ", ".join(sorted(h))))
             h[k] = v
         lib = capi.load()
         groups = [int(n) for n in groups] if groups is not None else []
-        c = capi.OptCfg()
+        c = self._cfg(groups)
         c.B, c.N, c.n_groups = int(B), int(N), len(groups)
-        for i, n in enumerate(groups[:12]):      # (a longer list is refused by the library through n_groups)
-            c.group_len[i] = n
         c.maxiters, c.ftol, c.gtol, c.lr = int(h["maxiters"]), float(h["ftol"]), float(h["gtol"]), float(h["lr"])
         c.tolerance_grad, c.tolerance_change = float(h["tolerance_grad"]), float(h["tolerance_change"])
         c.max_iter = int(h["max_iter"]) if h["max_iter"] is not None else 0
         c.max_eval = int(h["max_eval"]) if h["max_eval"] is not None else 0
         if c.max_iter < 0 or c.max_eval < 0 or (h["max_iter"] is not None and c.max_iter == 0) or (h["max_eval"] is not None and c.max_eval == 0):
-            raise ValueError("BatchOptimizer: max_iter / max_eval must be positive (None = the reference's defaults)")
+            raise ValueError("%s: max_iter / max_eval must be positive (None = the reference's defaults)" % type(self).__name__)
         c.history_size = int(h["history_size"]) if int(h["history_size"]) >= 1 else -1      # (0 is the C structure's "default": not offered here)
         c.reuse_entry_eval = int(bool(h["reuse_entry_eval"]))
         hnd = C.c_void_p()
-        capi.check(lib.sfx_opt_create(C.byref(c), C.byref(hnd)))
+        capi.check(getattr(lib, self._PREFIX + "create")(C.byref(c), C.byref(hnd)))
         import torch
         self._h, self._lib = hnd, lib
         self.B, self.N, self.hyper = int(B), int(N), h
         self.device = _cuda(torch.cuda.current_device())      # where the state lives: every tensor of a call must be there
         self.x_trial = None
         self._trace_cap = 0
+
+    @staticmethod
+    def _cfg(groups):
+        """The configuration structure with the tensors' lengths in place."""
+        c = capi.OptCfg()
+        for i, n in enumerate(groups[:12]):      # (a longer list is refused by the library through n_groups)
+            c.group_len[i] = n
+        return c
+
+    def _call(self, name, *args):
+        capi.check(getattr(self._lib, self._PREFIX + name)(self._h, *args))
 
     def begin(self, x0, mode="fit", resume=False, stream=None):
         """Start at x0 [B][N].  mode "fit": the whole run_fitting loop; "step": ONE LBFGS.step (resume=True continues the
@@ -727,23 +737,22 @@ class BatchOptimizer(capi.Handle):
         x0 = A.tensor("x0", x0, (self.B, self.N), self.device, holder=self._STATE)
         if self.x_trial is None:
             self.x_trial = torch.empty((self.B, self.N), dtype=torch.float32, device=self.device)
-        capi.check(self._lib.sfx_opt_begin(self._h, 0 if mode == "fit" else 1, int(bool(resume)), A.ptr(x0), A.ptr(self.x_trial),
-                                           A.stream(stream, self.device)))
+        self._call("begin", 0 if mode == "fit" else 1, int(bool(resume)), A.ptr(x0), A.ptr(self.x_trial), A.stream(stream, self.device))
         return self.x_trial
 
     def tell(self, loss, grad, stream=None):
         """loss [B] and grad [B][N] at x_trial -> x_trial holds the next points.  Enqueues only.  Problems that have finished
         ignore their entries, so calling this more often than needed is harmless."""
         if self.x_trial is None:
-            raise RuntimeError("BatchOptimizer.tell before begin")
+            raise RuntimeError("%s.tell before begin" % type(self).__name__)
         loss = A.tensor("loss", loss, (self.B,), self.device, holder=self._STATE)
         grad = A.tensor("grad", grad, (self.B, self.N), self.device, holder=self._STATE)
-        capi.check(self._lib.sfx_opt_tell(self._h, A.ptr(loss), A.ptr(grad), A.ptr(self.x_trial), A.stream(stream, self.device)))
+        self._call("tell", A.ptr(loss), A.ptr(grad), A.ptr(self.x_trial), A.stream(stream, self.device))
 
     def active(self, stream=None):
         """Problems still running.  Waits for the stream: the one host synchronisation of a loop."""
         n = C.c_int32(0)
-        capi.check(self._lib.sfx_opt_active(self._h, C.byref(n), A.stream(stream, self.device)))
+        self._call("active", C.byref(n), A.stream(stream, self.device))
         return int(n.value)
 
     def result(self):
@@ -755,12 +764,12 @@ class BatchOptimizer(capi.Handle):
         res = np.zeros(self.B, np.float32)
         ev = np.zeros(self.B, np.int32)
         st = np.zeros(self.B, np.int32)
-        capi.check(self._lib.sfx_opt_get(self._h, A.ptr(x), A.ptr(g), capi.fptr(res), capi.iptr(ev), capi.iptr(st)))
+        self._call("get", A.ptr(x), A.ptr(g), capi.fptr(res), capi.iptr(ev), capi.iptr(st))
         return dict(x=x, grad=g, result=res, evals=ev, status=st)
 
     def trace(self, capacity):
         """Attach (capacity > 0 records per problem) or detach (0) the optimiser trace (sfx_opt_trace); a fresh begin empties it."""
-        capi.check(self._lib.sfx_opt_trace(self._h, int(capacity)))
+        self._call("trace", int(capacity))
         self._trace_cap = int(capacity)
 
     def get_trace(self):
@@ -769,10 +778,28 @@ class BatchOptimizer(capi.Handle):
         cap = self._trace_cap
         rec = np.zeros((self.B, cap, 4), np.float32)
         cnt = np.zeros(self.B, np.int32)
-        capi.check(self._lib.sfx_opt_get_trace(self._h, capi.fptr(rec), capi.iptr(cnt)))
+        self._call("get_trace", capi.fptr(rec), capi.iptr(cnt))
         if (cnt > cap).any():
             raise RuntimeError("optimiser trace overflowed: %d records, capacity %d" % (cnt.max(), cap))
         return [rec[i, :cnt[i]].copy() for i in range(self.B)]
+
+
+class WideOptimizer(BatchOptimizer):
+    """BatchOptimizer for problems of up to 32768 variables in up to 256 tensors (sfx_opt_wide_*, csrc/opt_wide.hip): the same
+    state machine on a vector layer one workgroup wide -- one workgroup of 1024 threads per problem, the working vectors and
+    the history in device memory, dot products accumulated in float64.  The same methods, hyper-parameters and contracts; what
+    a loss that couples frames needs (one shape over a clip, a temporal smoothness term, per-vertex offsets)."""
+
+    _PREFIX = "sfx_opt_wide_"
+    _destroy = "sfx_opt_wide_destroy"
+    NMAX, MAX_GROUPS = 32768, 256           # SFX_WIDE_NMAX, SFX_WIDE_MAX_GROUPS
+
+    @staticmethod
+    def _cfg(groups):
+        c = capi.OptWideCfg()
+        c._lens = (C.c_int32 * max(1, len(groups)))(*groups)      # (read by sfx_opt_wide_create only; kept with the structure)
+        c.group_len = C.cast(c._lens, C.POINTER(C.c_int32))
+        return c
 
 
 # ---- the objective on tensors the caller supplies (sfx_objective_eval / sfx_camera_init_eval, csrc/objective_ext.hip) --------

@@ -7,15 +7,20 @@ parameters and forwards `.step(closure)` to the engine batch bound to the closur
 With any other callable -- a closure the caller wrote on torch tensors, as the reference's LBFGS takes it (lbfgs_ls.py:256-445:
 it zeroes the gradients, calls backward and returns the loss) -- `.step` runs the same device state machine on the caller's
 evaluations (engine.BatchOptimizer, csrc/opt_ext.hip): after every evaluation the next trial point is written into the parameters.
-`per_sample=True` makes every row of the parameters' leading dimension a problem of its own, with its own line search."""
+`per_sample=True` makes every row of the parameters' leading dimension a problem of its own, with its own line search.
+`wide=True` lifts the device optimiser's limits of 192 elements and 12 tensors per problem to 32768 and 256 (engine.WideOptimizer,
+csrc/opt_wide.hip: one workgroup per problem instead of one wavefront); a problem within the narrow limits takes the narrow path
+with unchanged bits either way."""
 
 EXT_NVAR_MAX = 192      # SFX_NVAR_MAX: variables per problem of the device optimiser
 EXT_MAX_TENSORS = 12    # SFX_MAX_GROUPS
+WIDE_NVAR_MAX = 32768   # SFX_WIDE_NMAX: with wide=True
+WIDE_MAX_TENSORS = 256  # SFX_WIDE_MAX_GROUPS
 
 
 class LBFGS(object):
     def __init__(self, params, lr=1, max_iter=20, max_eval=None, tolerance_grad=1e-5, tolerance_change=1e-9,
-                 history_size=100, line_search_fn=None, per_sample=False, poll_every=1):
+                 history_size=100, line_search_fn=None, per_sample=False, poll_every=1, wide=False):
         if line_search_fn != "strong_Wolfe":
             raise RuntimeError("only 'strong_Wolfe' is supported")
         if history_size > 400 or history_size < 1:
@@ -33,6 +38,7 @@ class LBFGS(object):
         # synchronisation -- is read after every k-th evaluation; the evaluations in between that nobody needed are ignored
         self.per_sample, self.poll_every = bool(per_sample), max(1, int(poll_every))
         self._ext, self._ext_key = None, None
+        self.wide = bool(wide)
 
     def _bind(self, engine_closure):
         self._closure = engine_closure
@@ -61,9 +67,11 @@ class LBFGS(object):
         ps = self._params
         if not ps:
             raise ValueError("LBFGS: no parameters")
-        if len(ps) > EXT_MAX_TENSORS:
+        nvar_max, max_tensors = (WIDE_NVAR_MAX, WIDE_MAX_TENSORS) if self.wide else (EXT_NVAR_MAX, EXT_MAX_TENSORS)
+        hint = "" if self.wide else "; LBFGS(..., wide=True) takes up to %d elements in up to %d tensors" % (WIDE_NVAR_MAX, WIDE_MAX_TENSORS)
+        if len(ps) > max_tensors:
             raise ValueError("LBFGS.step with a caller-written closure: %d parameter tensors, the device optimiser takes at "
-                             "most %d (concatenate some)" % (len(ps), EXT_MAX_TENSORS))
+                             "most %d (concatenate some)%s" % (len(ps), max_tensors, hint))
         for i, p in enumerate(ps):
             if not torch.is_tensor(p):
                 raise TypeError("LBFGS: parameter %d is a %s, not a tensor" % (i, type(p).__name__))
@@ -76,9 +84,10 @@ class LBFGS(object):
             if B < 1:
                 raise ValueError("LBFGS(per_sample=True): empty batch")
         lens = [p.numel() // B for p in ps]
-        if sum(lens) > EXT_NVAR_MAX or min(lens) < 1:
+        if sum(lens) > nvar_max or min(lens) < 1:
+            shown = lens if len(lens) <= 16 else lens[:16] + ["..."]
             raise ValueError("LBFGS.step with a caller-written closure: %d elements%s in tensors of %s, the device optimiser "
-                             "takes 1..%d with no empty tensor" % (sum(lens), " per sample" if self.per_sample else "", lens, EXT_NVAR_MAX))
+                             "takes 1..%d with no empty tensor%s" % (sum(lens), " per sample" if self.per_sample else "", shown, nvar_max, hint))
         for i, p in enumerate(ps):
             if p.device.type != "cuda":
                 raise ValueError("LBFGS.step with a caller-written closure: parameter %d is on %s; the optimiser runs on the GPU "
@@ -102,9 +111,12 @@ class LBFGS(object):
                 if self._ext is not None:
                     self._ext.close()
                 # (run_fitting's own rules -- maxiters, ftol, gtol -- play no part in ONE step)
-                self._ext = engine.BatchOptimizer(B, N, groups=lens, maxiters=1, ftol=0.0, gtol=0.0, lr=self.lr, max_iter=self.max_iter,
-                                                  max_eval=self.max_eval, history_size=self.history_size,
-                                                  tolerance_grad=self.tolerance_grad, tolerance_change=self.tolerance_change)
+                # (within the narrow limits a wide optimiser takes the narrow path: the same bits as without the flag)
+                narrow = N <= EXT_NVAR_MAX and len(lens) <= EXT_MAX_TENSORS
+                handle = engine.BatchOptimizer if narrow else engine.WideOptimizer
+                self._ext = handle(B, N, groups=lens, maxiters=1, ftol=0.0, gtol=0.0, lr=self.lr, max_iter=self.max_iter,
+                                   max_eval=self.max_eval, history_size=self.history_size,
+                                   tolerance_grad=self.tolerance_grad, tolerance_change=self.tolerance_change)
                 self._ext_key = key
             opt = self._ext
             flat = lambda ts: torch.cat([t.detach().reshape(B, -1) for t in ts], 1).contiguous()

@@ -159,6 +159,35 @@ def gen_lbfgs():
     _save("lbfgs", **out)
 
 
+def gen_lbfgs_wide():
+    """Reference run_fitting + LBFGS('lbfgsls') float32 trajectories beyond 192 variables (tests/golden/lbfgs_wide.npz): the
+    objective family of tests/opt_ext_common.py, problem 0 -- a_i = ((i mod 10) + 1)^2, target 0.3.  Points (float32) and losses
+    only: the tests recompute the gradients with CPU torch at the stored points."""
+    out = {}
+    for N in (193, 1000):
+        x0 = np.random.RandomState(N).uniform(-1, 1, N).astype(np.float32)
+        x = torch.tensor(x0, dtype=torch.float32, requires_grad=True)
+        a = ((torch.arange(N) % 10 + 1) ** 2).to(torch.float32)
+        opt, _ = ref.optim_factory.create_optimizer([x], optim_type="lbfgsls", lr=1.0, maxiters=30)
+        pts, losses = [], []
+
+        def closure(stage=0):
+            opt.zero_grad()
+            l = 0.5 * (a * (x - 0.3) ** 2).sum() + 0.1 * torch.sin(3 * x).sum()
+            l.backward()
+            pts.append(x.detach().numpy().copy()); losses.append(np.float32(l.item()))
+            return l
+        mon = ref.fitting.FittingMonitor(maxiters=30, ftol=1e-9, gtol=1e-9)
+        with mon:
+            res = mon.run_fitting(opt, closure, [x], None, 0, use_vposer=False)
+        out["%d_x0" % N] = x0
+        out["%d_points" % N] = np.stack(pts).astype(np.float32)
+        out["%d_losses" % N] = np.asarray(losses, np.float32)
+        out["%d_res" % N] = np.array(np.nan if res is None else res, np.float32)
+        out["%d_xf" % N] = x.detach().numpy().astype(np.float32)
+    _save("lbfgs_wide", **out)
+
+
 def gen_euler():
     import joblib
     out = {}
@@ -957,7 +986,7 @@ def gen_smplx_topology():
 if __name__ == "__main__":
     todo = sys.argv[1:] or ["tables", "euler", "objective", "lbfgs", "e2e", "demo", "e2e_vposer"]
     for w in todo:
-        {"objective": gen_objective, "lbfgs": gen_lbfgs, "euler": gen_euler, "tables": gen_tables,
+        {"objective": gen_objective, "lbfgs": gen_lbfgs, "lbfgs_wide": gen_lbfgs_wide, "euler": gen_euler, "tables": gen_tables,
          "e2e": gen_e2e, "demo": gen_demo, "e2e_vposer": gen_e2e_vposer, "parser": gen_parser, "eval": gen_eval,
          "gmm": gen_gmm, "e2e_full": gen_e2e_full, "e2e_full_set": gen_e2e_full_set, "e2e_vposer_set": gen_e2e_vposer_set, "e2e_side": gen_e2e_side, "e2e_bench": gen_e2e_bench,
          "gmm_unmerged": gen_gmm_unmerged, "e2e_pen_set": gen_e2e_pen_set, "objective_pen": gen_objective_pen, "cubic_overflow": gen_cubic_overflow, "e2e_bench_raw_delta": gen_e2e_bench_raw_delta, "smplx_topology": gen_smplx_topology}[w]()
