@@ -552,6 +552,57 @@ int  sfx_eval_nearest(int32_t B, int32_t Na, int32_t Nb, const float* a_dev, con
                       int32_t n_thresh, const double* thresh /* HOST */, float* dist_ab_dev, float* dist_ba_dev,
                       int32_t* count_ab_dev, int32_t* count_ba_dev, int32_t* valid_dev, void* stream);
 
+/* ---- differentiable nearest-point (chamfer) term between point sets (csrc/chamfer.hip, csrc/chamfer_math.h) ---------------
+ * The 3D data term of a fit to a scan, a depth map or a reconstruction, for B pairs of point sets a [B][Na][3] and
+ * b [B][Nb][3], float32 (by convention a is the mesh and b the cloud; nothing depends on that).  Both entries are stateless like
+ * sfx_eval_*: device pointers, sizes, a stream; no handle, no allocation, no synchronisation; the caller supplies the scratch,
+ * whose size the two macros below give.  B == 0 returns 0 before any pointer is looked at.  A refusal (a NULL required
+ * pointer, Na or Nb outside 1 .. SFX_CHAMFER_MAX_POINTS, rho < 0 or not finite, scratch too small) returns -1, sets the error
+ * text and launches nothing.
+ *   mask_a_dev [B][Na], mask_b_dev [B][Nb]       uint8 or NULL (every point valid); 0 takes the point out as a query AND as a target
+ *   weight_a_dev [B][Na], weight_b_dev [B][Nb]   float32 or NULL (1): scales the point's own query term, has no effect on the
+ *                                                point as a target; a constant (no gradient)
+ * Nearest target: j(i) = argmin over the valid j of s(i, j) = ((dx dx + dy dy) + dz dz), in float32 from the coordinate
+ * differences, in exactly this association and with no fused multiply-add; ties go to the lowest index.  Index and squared
+ * distance equal numpy's float32 argmin / min of the same expression bit for bit.
+ * Direction a -> b: L_ab = sum over the valid i of w_a[i] rho(s_i);  rho(s) = s when rho == 0, rho^2 s / (s + rho^2) when
+ * rho > 0 (the GMoF of smplifyx/utils.py:92-95 on the squared distance).  L_ba: the same with the roles swapped.
+ * The per-point value w rho(s) is formed in float64 from the float32 s and stored as float32; a mesh's sum of a direction is
+ * float64 in a fixed order (a thread's points in index order, the lanes of a wave, the waves in wave order) and is rounded to
+ * float32 once.  No float atomics anywhere: a mesh's bits depend on its own points only, from run to run and in any batch.
+ * A masked query has index -1, squared distance 0, value 0 and gradient 0.  A direction whose target set has no valid point
+ * has every index -1 and loss 0.  Otherwise a query that finds no target nearer than +inf -- a non-finite coordinate, or
+ * coordinates so far apart that s overflows -- has index -1, squared distance NaN, gradient 0 and makes that mesh's loss of
+ * that direction NaN.
+ *   idx_ab_dev [B][Na], idx_ba_dev [B][Nb]       int32: the nearest valid point of the other set, or -1
+ *   dist2_ab_dev, dist2_ba_dev                   float32 or NULL: s at that point
+ *   loss_dev [B][2]                              L_ab, L_ba
+ *   valid_dev [B][2]                             int32 or NULL: valid (unmasked) points of a and of b
+ * Gradient: d L_ab / d a_i = g_ab w_a[i] rho'(s_i) 2 (a_i - b_j(i)), and d L_ab / d b_j the negative of that summed over every i
+ * with j(i) = j; rho'(s) = 1 when rho == 0, rho^4 / (s + rho^2)^2 when rho > 0; L_ba gives the same two terms with the roles
+ * swapped.  s is formed again from the points (the same bits as the forward's).  The scatter goes through an inverted index
+ * built per call from integers (counts, an exclusive scan, a fill, every entry moved to its rank): for every row the list of
+ * the queries that chose it, in ascending query index.  A row is its gather term plus its list, in float64: the list is cut
+ * into segments (one up to 32 entries, else 64 of equal length), each summed from 0 in list order, the segment sums added to
+ * the gather term in segment order, rounded to float32 once (csrc/chamfer_math.h states the rule).  An index outside
+ * 0 .. targets - 1 counts as -1.
+ *   grad_dev [B][2]                              upstream d / d L_ab, d / d L_ba
+ *   da_dev [B][Na][3], db_dev [B][Nb][3]         or NULL: not computed
+ * Known limit: both directions are point-to-POINT; against a mesh that is point-to-vertex, not point-to-triangle.             */
+#define SFX_CHAMFER_MAX_POINTS (1 << 26)
+#define SFX_CHAMFER_FORWARD_SCRATCH_BYTES(B, Na, Nb)  ((int64_t)4 * (int64_t)(B) * ((int64_t)(Na) + (int64_t)(Nb)))
+#define SFX_CHAMFER_BACKWARD_SCRATCH_BYTES(B, Na, Nb) ((int64_t)4 * (int64_t)(B) * (4 * ((int64_t)(Na) + (int64_t)(Nb)) + 2))
+int  sfx_chamfer_forward(int32_t B, int32_t Na, int32_t Nb, const float* a_dev, const float* b_dev,
+                         const unsigned char* mask_a_dev, const unsigned char* mask_b_dev,
+                         const float* weight_a_dev, const float* weight_b_dev, float rho,
+                         int32_t* idx_ab_dev, int32_t* idx_ba_dev, float* dist2_ab_dev, float* dist2_ba_dev,
+                         float* loss_dev, int32_t* valid_dev, void* scratch_dev, int64_t scratch_bytes, void* stream);
+int  sfx_chamfer_backward(int32_t B, int32_t Na, int32_t Nb, const float* a_dev, const float* b_dev,
+                          const unsigned char* mask_a_dev, const unsigned char* mask_b_dev,
+                          const float* weight_a_dev, const float* weight_b_dev, float rho,
+                          const int32_t* idx_ab_dev, const int32_t* idx_ba_dev, const float* grad_dev,
+                          float* da_dev, float* db_dev, void* scratch_dev, int64_t scratch_bytes, void* stream);
+
 /* ---- fitted meshes drawn over their images on the device (csrc/raster.hip, csrc/host/render.hip) ------------------------
  * A batched software rasteriser for B triangle meshes of one topology, in place of render_mesh (smplifyx/utils.py:497-538:
  * pyrender's offscreen OpenGL).  Stateless like sfx_eval_*: device pointers, sizes, a stream; no handle, no allocation, no

@@ -200,6 +200,11 @@ SYMBOLS = {
     "sfx_eval_align": (C.c_int, [C.c_int32] * 3 + [C.c_void_p] * 3 + [i32p, C.c_int32] + [C.c_void_p] * 3 + [C.c_void_p]),
     # B, Na, Nb, a, b, mask_a, mask_b, n_thresh, thresh (host), dist_ab, dist_ba, count_ab, count_ba, valid, stream
     "sfx_eval_nearest": (C.c_int, [C.c_int32] * 3 + [C.c_void_p] * 4 + [C.c_int32, f64p] + [C.c_void_p] * 5 + [C.c_void_p]),
+    # B, Na, Nb, a, b, mask_a, mask_b, weight_a, weight_b, rho, idx_ab, idx_ba, dist2_ab, dist2_ba, loss, valid, scratch,
+    # scratch_bytes, stream
+    "sfx_chamfer_forward": (C.c_int, [C.c_int32] * 3 + [C.c_void_p] * 6 + [C.c_float] + [C.c_void_p] * 7 + [C.c_int64, C.c_void_p]),
+    # B, Na, Nb, a, b, mask_a, mask_b, weight_a, weight_b, rho, idx_ab, idx_ba, grad, da, db, scratch, scratch_bytes, stream
+    "sfx_chamfer_backward": (C.c_int, [C.c_int32] * 3 + [C.c_void_p] * 6 + [C.c_float] + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p]),
     # cfg, B, V, F, H, W, verts, faces, vf_offsets, vf_faces, rot, t, focal, center, background, three scratch buffers,
     # rgba, depth, tri, screen, dropped, stream
     "sfx_render_meshes": (C.c_int, [C.POINTER(RenderCfg)] + [C.c_int32] * 5 + [C.c_void_p] * 17 + [C.c_void_p]),

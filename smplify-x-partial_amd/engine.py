@@ -1055,6 +1055,133 @@ def nearest_distances(a, b, thresholds=(), mask_a=None, mask_b=None, return_dist
     return out
 
 
+# ---- differentiable nearest-point term between point sets (sfx_chamfer_forward / _backward, csrc/chamfer.hip) ---------------
+CHAMFER_MAX_POINTS = 1 << 26                                            # SFX_CHAMFER_MAX_POINTS
+_CHAMFER_CACHE_SIZE = 8
+_chamfer_cache = collections.OrderedDict()      # (device, B, Na, Nb) -> the scratch tensors of calls of that size
+
+
+def chamfer_forward_scratch_bytes(B, Na, Nb):
+    """SFX_CHAMFER_FORWARD_SCRATCH_BYTES of include/sfx.h."""
+    return 4 * B * (Na + Nb)
+
+
+def chamfer_backward_scratch_bytes(B, Na, Nb):
+    """SFX_CHAMFER_BACKWARD_SCRATCH_BYTES of include/sfx.h."""
+    return 4 * B * (4 * (Na + Nb) + 2)
+
+
+def _chamfer_scratch(which, nbytes, B, Na, Nb, dev):
+    """The scratch of sfx_chamfer_forward ('fwd') or _backward ('bwd') for calls of one size on one device: made once and kept
+    (the last few sizes), so calls of one size belong on one stream."""
+    import torch
+    key = (dev, B, Na, Nb)
+    ent = _chamfer_cache.get(key)
+    if ent is None:
+        ent = _chamfer_cache[key] = {}
+        while len(_chamfer_cache) > _CHAMFER_CACHE_SIZE:
+            _chamfer_cache.popitem(last=False)
+    else:
+        _chamfer_cache.move_to_end(key)
+    if which not in ent:
+        ent[which] = torch.empty([max(1, nbytes // 4)], dtype=torch.int32, device=dev)
+    return ent[which]
+
+
+def _chamfer_args(a, b, mask_a, mask_b, weight_a, weight_b, rho):
+    """The checked inputs both chamfer calls share: sizes, tensors as the library reads them, rho."""
+    import torch
+    B, Na = _points("a", a)
+    Nb = _points("b", b)[1]
+    rho = float(rho)
+    if not (np.isfinite(rho) and rho >= 0.0):
+        raise ValueError("rho: %r, a finite value >= 0 is needed" % (rho,))
+    if Na > CHAMFER_MAX_POINTS or Nb > CHAMFER_MAX_POINTS:
+        raise ValueError("a, b: %d and %d points, at most %d each" % (Na, Nb, CHAMFER_MAX_POINTS))
+    _expect_shape("b", b, (B, Nb, 3))
+    _expect_shape("mask_a", mask_a, (B, Na))
+    _expect_shape("mask_b", mask_b, (B, Nb))
+    for name, w, n in (("weight_a", weight_a, Na), ("weight_b", weight_b, Nb)):
+        if w is not None:
+            if not torch.is_tensor(w):
+                raise TypeError("%s: a torch tensor is needed, got %s" % (name, type(w).__name__))
+            if tuple(w.shape) != (B, n):
+                raise ValueError("%s: shape %s, expected %s" % (name, tuple(w.shape), (B, n)))
+    a = A.tensor("a", a, (B, Na, 3))
+    dev = a.device
+    b = A.tensor("b", b, (B, Nb, 3), device=dev, holder="a")
+    mask_a = _point_mask("mask_a", mask_a, (B, Na), dev, "a")
+    mask_b = _point_mask("mask_b", mask_b, (B, Nb), dev, "a")
+    weight_a = A.tensor("weight_a", weight_a, (B, Na), device=dev, optional=True, holder="a")
+    weight_b = A.tensor("weight_b", weight_b, (B, Nb), device=dev, optional=True, holder="a")
+    return B, Na, Nb, dev, a, b, mask_a, mask_b, weight_a, weight_b, rho
+
+
+def chamfer_eval(a, b, mask_a=None, mask_b=None, weight_a=None, weight_b=None, rho=0.0, return_dist2=True, stream=None):
+    """The nearest-point (chamfer) term of B pairs of point sets in both directions (sfx_chamfer_forward; the contract is in
+    include/sfx.h): a [B, Na, 3], b [B, Nb, 3] float32 contiguous CUDA tensors; masks [B, Na] / [B, Nb] torch.bool / torch.uint8
+    or None (a masked point is neither a query nor a target); weights [B, Na] / [B, Nb] float32 or None (a weight scales the
+    point's own query term only); rho = 0: squared distances, rho > 0: the GMoF rho^2 s / (s + rho^2) of the squared distance.
+    Returns a dict of device tensors:
+      loss [B, 2]                          sum over a's points of w rho(s) to the nearest point of b, and the same for b against a
+      idx_ab [B, Na], idx_ba [B, Nb]       int32: that nearest point (the lowest index of a tie), -1 at a masked point or where
+                                           there is no target
+      dist2_ab, dist2_ba                   its squared distance, float32 (with return_dist2)
+      valid [B, 2]                         int32: valid points of a and of b
+    Index and squared distance are numpy's float32 argmin / min bit for bit; a mesh's bits depend on its own points only.  Only
+    enqueues on the current (or the given) stream; the scratch of a size is cached, so calls of one size belong on one stream."""
+    import torch
+    B, Na, Nb, dev, a, b, mask_a, mask_b, weight_a, weight_b, rho = _chamfer_args(a, b, mask_a, mask_b, weight_a, weight_b, rho)
+    out = dict(loss=torch.empty([B, 2], dtype=torch.float32, device=dev),
+               idx_ab=torch.empty([B, Na], dtype=torch.int32, device=dev), idx_ba=torch.empty([B, Nb], dtype=torch.int32, device=dev),
+               valid=torch.empty([B, 2], dtype=torch.int32, device=dev))
+    if return_dist2:
+        out["dist2_ab"] = torch.empty([B, Na], dtype=torch.float32, device=dev)
+        out["dist2_ba"] = torch.empty([B, Nb], dtype=torch.float32, device=dev)
+    if B > 0:
+        nbytes = chamfer_forward_scratch_bytes(B, Na, Nb)
+        scratch = _chamfer_scratch("fwd", nbytes, B, Na, Nb, dev)
+        with torch.cuda.device(dev):
+            capi.check(capi.load().sfx_chamfer_forward(
+                B, Na, Nb, A.ptr(a), A.ptr(b), A.ptr(mask_a), A.ptr(mask_b), A.ptr(weight_a), A.ptr(weight_b), rho,
+                A.ptr(out["idx_ab"]), A.ptr(out["idx_ba"]), A.ptr(out.get("dist2_ab")), A.ptr(out.get("dist2_ba")),
+                A.ptr(out["loss"]), A.ptr(out["valid"]), A.ptr(scratch), nbytes, A.stream(stream, dev)))
+    return out
+
+
+def chamfer_backward(a, b, fwd, grad, want=("a", "b"), mask_a=None, mask_b=None, weight_a=None, weight_b=None, rho=0.0,
+                     stream=None):
+    """Gradient of the chamfer term with respect to the points (sfx_chamfer_backward): `fwd` is what chamfer_eval returned for
+    the same inputs (its idx_ab and idx_ba are read), grad [B, 2] the upstream of loss; masks, weights and rho as in that call.
+    want: which of 'a', 'b' to compute.  Returns (da [B, Na, 3] or None, db [B, Nb, 3] or None).  Every row is its own term plus
+    the terms of the points that chose it, summed in float64 in ascending index through an inverted index built on the device:
+    no float atomics, the same bits in every run and in any batch.  Only enqueues on the current (or the given) stream."""
+    import torch
+    want = tuple(want)
+    if not want or [w for w in want if w not in ("a", "b")]:
+        raise ValueError("want: some of ('a', 'b'), got %r" % (want,))
+    B, Na, Nb, dev, a, b, mask_a, mask_b, weight_a, weight_b, rho = _chamfer_args(a, b, mask_a, mask_b, weight_a, weight_b, rho)
+    if not isinstance(fwd, dict) or "idx_ab" not in fwd or "idx_ba" not in fwd:
+        raise TypeError("fwd: the dict chamfer_eval returned is needed (idx_ab, idx_ba)")
+    if not torch.is_tensor(grad):
+        raise TypeError("grad: a torch tensor is needed, got %s" % type(grad).__name__)
+    if tuple(grad.shape) != (B, 2):
+        raise ValueError("grad: shape %s, expected %s" % (tuple(grad.shape), (B, 2)))
+    idx_ab = A.tensor("fwd['idx_ab']", fwd["idx_ab"], (B, Na), device=dev, dtype=torch.int32, holder="a")
+    idx_ba = A.tensor("fwd['idx_ba']", fwd["idx_ba"], (B, Nb), device=dev, dtype=torch.int32, holder="a")
+    grad = A.tensor("grad", grad, (B, 2), device=dev, holder="a")
+    da = torch.empty([B, Na, 3], dtype=torch.float32, device=dev) if "a" in want else None
+    db = torch.empty([B, Nb, 3], dtype=torch.float32, device=dev) if "b" in want else None
+    if B > 0:
+        nbytes = chamfer_backward_scratch_bytes(B, Na, Nb)
+        scratch = _chamfer_scratch("bwd", nbytes, B, Na, Nb, dev)
+        with torch.cuda.device(dev):
+            capi.check(capi.load().sfx_chamfer_backward(
+                B, Na, Nb, A.ptr(a), A.ptr(b), A.ptr(mask_a), A.ptr(mask_b), A.ptr(weight_a), A.ptr(weight_b), rho,
+                A.ptr(idx_ab), A.ptr(idx_ba), A.ptr(grad), A.ptr(da), A.ptr(db), A.ptr(scratch), nbytes, A.stream(stream, dev)))
+    return da, db
+
+
 # ---- fitted meshes over their images (sfx_render_meshes, csrc/raster.hip) -----------------------------------------------------
 RENDER_MAX_LIGHTS = capi.RENDER_MAX_LIGHTS
 RENDER_BASE_RGB = (0.4, 0.4, 0.7)                                       # utils.py:499 vertex_colors
