@@ -588,7 +588,8 @@ int  sfx_eval_nearest(int32_t B, int32_t Na, int32_t Nb, const float* a_dev, con
  * 0 .. targets - 1 counts as -1.
  *   grad_dev [B][2]                              upstream d / d L_ab, d / d L_ba
  *   da_dev [B][Na][3], db_dev [B][Nb][3]         or NULL: not computed
- * Known limit: both directions are point-to-POINT; against a mesh that is point-to-vertex, not point-to-triangle.             */
+ * Known limit: both directions are point-to-POINT; against a mesh that is point-to-vertex, not point-to-triangle
+ * (sfx_p2m_forward below is the point-to-triangle term of the cloud -> surface direction).                                     */
 #define SFX_CHAMFER_MAX_POINTS (1 << 26)
 #define SFX_CHAMFER_FORWARD_SCRATCH_BYTES(B, Na, Nb)  ((int64_t)4 * (int64_t)(B) * ((int64_t)(Na) + (int64_t)(Nb)))
 #define SFX_CHAMFER_BACKWARD_SCRATCH_BYTES(B, Na, Nb) ((int64_t)4 * (int64_t)(B) * (4 * ((int64_t)(Na) + (int64_t)(Nb)) + 2))
@@ -602,6 +603,60 @@ int  sfx_chamfer_backward(int32_t B, int32_t Na, int32_t Nb, const float* a_dev,
                           const float* weight_a_dev, const float* weight_b_dev, float rho,
                           const int32_t* idx_ab_dev, const int32_t* idx_ba_dev, const float* grad_dev,
                           float* da_dev, float* db_dev, void* scratch_dev, int64_t scratch_bytes, void* stream);
+
+/* ---- differentiable point-to-triangle term from point clouds to mesh surfaces (csrc/p2m.hip, csrc/p2m_math.h) ------------
+ * The point-to-SURFACE residual of a fit to a scan or a depth map: for B clouds p [B][Np][3] and B meshes v [B][Nv][3] of one
+ * topology faces [F][3] (int32), float32, every cloud point against the nearest point of its mesh's triangles.  Only the cloud ->
+ * surface direction; mesh -> cloud of a two-sided term is L_ab of sfx_chamfer_forward, and the caller adds the two.  Stateless
+ * like sfx_chamfer_*: device pointers, sizes, a stream; no handle, no allocation, no synchronisation; the caller supplies the
+ * scratch, whose size the two macros below give.  B == 0 returns 0 before any pointer is looked at.  A refusal (a NULL required
+ * pointer, Np, Nv or F outside 1 .. SFX_P2M_MAX_POINTS, rho < 0 or not finite, scratch too small) returns -1, sets the error
+ * text and launches nothing.
+ *   mask_p_dev [B][Np]       uint8 or NULL: 0 takes the point out
+ *   mask_f_dev [B][F]        uint8 or NULL: 0 takes the face out; a face that names a vertex outside 0 .. Nv - 1 is out as well
+ *   weight_p_dev [B][Np]     float32 or NULL (1): scales the point's term; a constant (no gradient)
+ * Closest point of triangle abc to p: the region test of Ericson, Real-Time Collision Detection 5.1.5, in float32 with no fused
+ * multiply-add and the correctly rounded division, in exactly this association (csrc/p2m_math.h restates it):
+ * dot(x, y) = (x0 y0 + x1 y1) + x2 y2;  ab = b - a, ac = c - a, ap = p - a, bp = p - b, cp = p - c;  d1 = ab.ap, d2 = ac.ap,
+ * d3 = ab.bp, d4 = ac.bp, d5 = ab.cp, d6 = ac.cp;  vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4.  The first
+ * condition that holds decides (v, w):  d1 <= 0 and d2 <= 0: (0, 0);  d3 >= 0 and d4 <= d3: (1, 0);  vc <= 0, d1 >= 0 and
+ * d3 <= 0: (d1 / (d1 - d3), 0);  d6 >= 0 and d5 <= d6: (0, 1);  vb <= 0, d2 >= 0 and d6 <= 0: (0, d2 / (d2 - d6));  va <= 0,
+ * d4 - d3 >= 0 and d5 - d6 >= 0: w = (d4 - d3) / ((d4 - d3) + (d5 - d6)), v = 1 - w;  otherwise den = 1 / ((va + vb) + vc),
+ * v = vb den, w = vc den.  u = (1 - v) - w;  q = (a + v ab) + w ac;  d = p - q;  s = dot(d, d).  A degenerate face can give a NaN
+ * s; a NaN never wins.  Nearest face: the argmin of s over the candidate faces, replaced on strict <, so ties go to the lowest
+ * face index.  face, s and the barycentrics equal a float32 numpy restatement of the above bit for bit.
+ * L = sum over the valid points of w rho(s), rho as in sfx_chamfer_forward (rho == 0: s; rho > 0: the GMoF rho^2 s / (s + rho^2),
+ * smplifyx/utils.py:92-95).  The per-point value is float64 from the float32 s, stored as float32; a mesh's sum is float64 in
+ * the fixed order of sfx_chamfer_forward and is rounded to float32 once.  No float atomics anywhere.
+ * A masked point has face -1, barycentrics 0, squared distance 0, value 0 and gradient 0.  A mesh with no candidate face at all
+ * has every face -1 and loss 0.  Otherwise a point that finds no face nearer than +inf has face -1, barycentrics and squared
+ * distance NaN, gradient 0 and makes that mesh's loss NaN.
+ *   face_dev [B][Np]         int32: the nearest candidate face, or -1
+ *   bary_dev [B][Np][3]      float32 or NULL: (u, v, w) of the closest point on it
+ *   dist2_dev [B][Np]        float32 or NULL: s
+ *   loss_dev [B]             L
+ *   valid_dev [B]            int32 or NULL: valid (unmasked) points
+ * Gradient at the faces given: with c = ((g w) rho'(s)) 2 in float64, d L / d p_i = c (p_i - q_i), the difference in float64
+ * from the float32 p and q, and corner k of the face receives -(c bary_k)(p_i - q_i): the barycentrics minimise, so they carry
+ * no derivative (envelope theorem).  s, q and the barycentrics are formed again from the points (the same bits as the forward's).
+ * The scatter goes through the inverted index of sfx_chamfer_backward over the 3 Np entries e = 3 i + k and the Nv rows: for
+ * every vertex its entries in ascending e, cut into segments (one up to 32 entries, else 64 of equal length), each summed from
+ * 0 in list order, the segment sums added in segment order, float64, rounded to float32 once.  A point whose face is outside
+ * 0 .. F - 1, or names a vertex outside the mesh, has no term.
+ *   grad_dev [B]             upstream d / d L
+ *   dp_dev [B][Np][3], dv_dev [B][Nv][3]         or NULL: not computed
+ * Not built: point-to-plane, a spatial index or pruning (the search is brute force), a float64 kernel.                         */
+#define SFX_P2M_MAX_POINTS (1 << 26)
+#define SFX_P2M_FORWARD_SCRATCH_BYTES(B, Np, Nv)  ((int64_t)4 * (int64_t)(B) * (int64_t)(Np))
+#define SFX_P2M_BACKWARD_SCRATCH_BYTES(B, Np, Nv) ((int64_t)4 * (int64_t)(B) * (9 * (int64_t)(Np) + 2 * (int64_t)(Nv) + 1))
+int  sfx_p2m_forward(int32_t B, int32_t Np, int32_t Nv, int32_t F, const float* p_dev, const float* v_dev,
+                     const int32_t* faces_dev, const unsigned char* mask_p_dev, const unsigned char* mask_f_dev,
+                     const float* weight_p_dev, float rho, int32_t* face_dev, float* bary_dev, float* dist2_dev,
+                     float* loss_dev, int32_t* valid_dev, void* scratch_dev, int64_t scratch_bytes, void* stream);
+int  sfx_p2m_backward(int32_t B, int32_t Np, int32_t Nv, int32_t F, const float* p_dev, const float* v_dev,
+                      const int32_t* faces_dev, const unsigned char* mask_p_dev, const float* weight_p_dev, float rho,
+                      const int32_t* face_dev, const float* grad_dev, float* dp_dev, float* dv_dev,
+                      void* scratch_dev, int64_t scratch_bytes, void* stream);
 
 /* ---- fitted meshes drawn over their images on the device (csrc/raster.hip, csrc/host/render.hip) ------------------------
  * A batched software rasteriser for B triangle meshes of one topology, in place of render_mesh (smplifyx/utils.py:497-538:

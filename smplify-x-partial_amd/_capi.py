@@ -205,6 +205,10 @@ SYMBOLS = {
     "sfx_chamfer_forward": (C.c_int, [C.c_int32] * 3 + [C.c_void_p] * 6 + [C.c_float] + [C.c_void_p] * 7 + [C.c_int64, C.c_void_p]),
     # B, Na, Nb, a, b, mask_a, mask_b, weight_a, weight_b, rho, idx_ab, idx_ba, grad, da, db, scratch, scratch_bytes, stream
     "sfx_chamfer_backward": (C.c_int, [C.c_int32] * 3 + [C.c_void_p] * 6 + [C.c_float] + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p]),
+    # B, Np, Nv, F, p, v, faces, mask_p, mask_f, weight_p, rho, face, bary, dist2, loss, valid, scratch, scratch_bytes, stream
+    "sfx_p2m_forward": (C.c_int, [C.c_int32] * 4 + [C.c_void_p] * 6 + [C.c_float] + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p]),
+    # B, Np, Nv, F, p, v, faces, mask_p, weight_p, rho, face, grad, dp, dv, scratch, scratch_bytes, stream
+    "sfx_p2m_backward": (C.c_int, [C.c_int32] * 4 + [C.c_void_p] * 5 + [C.c_float] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]),
     # cfg, B, V, F, H, W, verts, faces, vf_offsets, vf_faces, rot, t, focal, center, background, three scratch buffers,
     # rgba, depth, tri, screen, dropped, stream
     "sfx_render_meshes": (C.c_int, [C.POINTER(RenderCfg)] + [C.c_int32] * 5 + [C.c_void_p] * 17 + [C.c_void_p]),

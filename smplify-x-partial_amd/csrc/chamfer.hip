@@ -22,21 +22,19 @@
 //   k_chamfer_rows      one thread per output row: its gather term, then its list.  Up to CH_SERIAL_MAX entries the thread walks
 //                       them; a longer list is cut into 64 segments summed by the 64 lanes of the row's wave and added in segment
 //                       order (ch_seg_len).  Every sum is float64 in a fixed order and is rounded to float32 once.
-// No kernel uses a float atomic; a mesh's bits depend on its own points only.
+// No kernel uses a float atomic; a mesh's bits depend on its own points only.  The bodies of the reduce and of the four index
+// steps are in csrc/chamfer_index.h, which csrc/p2m.hip (the point-to-triangle term) uses too.
 #include "../../include/sfx.h"
 #include "sfx_internal.h"
 #include "wave_ops.h"
 #include "chamfer_math.h"
+#include "chamfer_index.h"
 
 #include <cmath>
 
 #define CH_NN_THREADS 256
 #define CH_NN_QPT 2
 #define CH_NN_TILE 1024
-#define CH_RED_THREADS 1024
-#define CH_RED_WAVES (CH_RED_THREADS / 64)
-#define CH_ROW_THREADS 256
-#define CH_GRID_Y 65535
 
 typedef float ch_f2 __attribute__((ext_vector_type(2)));
 static_assert(CH_NN_QPT == 2, "k_chamfer_nearest packs the two queries of a thread");
@@ -139,30 +137,13 @@ void k_chamfer_nearest(const ChamferArgs A) {
 
 __global__ __launch_bounds__(CH_RED_THREADS)
 void k_chamfer_reduce(const ChamferArgs A) {
-    __shared__ double red[CH_RED_WAVES];
-    __shared__ int redn[CH_RED_WAVES];
-    const int dir = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int dir = blockIdx.x;
     const size_t mesh = (size_t)A.b0 + blockIdx.y;
     const int Nq = dir ? A.Nb : A.Na;
     const float* val = A.val + mesh * ((size_t)A.Na + A.Nb) + (dir ? A.Na : 0);
     const unsigned char* mq = dir ? A.mb : A.ma;
     if (mq) mq += mesh * Nq;
-    double acc = 0.0; int n = 0;
-    for (int i = tid; i < Nq; i += CH_RED_THREADS) {
-        acc += (double)val[i];
-        n += (!mq || mq[i]) ? 1 : 0;
-    }
-    const double s = wave_sum_dpp(acc);
-    const int c = wave_incl_scan_dpp(n);
-    if (lane == 0) red[w] = s;
-    if (lane == 63) redn[w] = c;
-    __syncthreads();
-    if (tid == 0) {
-        double t = 0.0; int m = 0;
-        for (int k = 0; k < CH_RED_WAVES; ++k) { t += red[k]; m += redn[k]; }
-        A.loss[mesh * 2 + dir] = (float)t;
-        if (A.valid) A.valid[mesh * 2 + dir] = m;
-    }
+    ch_reduce_body(val, mq, Nq, A.loss + mesh * 2 + dir, A.valid ? A.valid + mesh * 2 + dir : nullptr);
 }
 
 // ----------------------------------------------------------------------------------------------------------- backward
@@ -198,69 +179,32 @@ __device__ __forceinline__ ChamferSide chamfer_side(const ChamferArgs& A, size_t
     return S;
 }
 
-// the bucket of query q of the other set, or -1: masked, without a target, or an index that names no row
-__device__ __forceinline__ int chamfer_bucket(const ChamferSide& S, int q) {
-    if (S.my && !S.my[q]) return -1;
-    const int t = S.idx_in[q];
-    return ch_index_ok(t, S.Nd) ? t : -1;
-}
-
 __global__ __launch_bounds__(CH_ROW_THREADS)
 void k_chamfer_count(const ChamferArgs A) {
     const int set = blockIdx.z;
     if (!(A.want >> set & 1)) return;
-    const ChamferSide S = chamfer_side(A, (size_t)A.b0 + blockIdx.y, set);
-    const int q = blockIdx.x * CH_ROW_THREADS + threadIdx.x;
-    if (q >= S.Nq) return;
-    const int t = chamfer_bucket(S, q);
-    if (t >= 0) atomicAdd(&S.cnt[t], 1);
+    ch_count_body(chamfer_side(A, (size_t)A.b0 + blockIdx.y, set), blockIdx.x * CH_ROW_THREADS + threadIdx.x);
 }
 
 __global__ __launch_bounds__(CH_RED_THREADS)
 void k_chamfer_scan(const ChamferArgs A) {
-    __shared__ int wave_total[CH_RED_WAVES];
     const int set = blockIdx.x;
     if (!(A.want >> set & 1)) return;
-    const ChamferSide S = chamfer_side(A, (size_t)A.b0 + blockIdx.y, set);
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    int carry = 0;
-    for (int base = 0; base < S.Nd; base += CH_RED_THREADS) {
-        const int i = base + tid;
-        const int c = i < S.Nd ? S.cnt[i] : 0;
-        const int incl = wave_incl_scan_dpp(c);
-        if (lane == 63) wave_total[w] = incl;
-        __syncthreads();
-        int before = 0, total = 0;
-        for (int k = 0; k < CH_RED_WAVES; ++k) { const int t = wave_total[k]; before += k < w ? t : 0; total += t; }
-        if (i < S.Nd) { S.off[i] = carry + before + incl - c; S.cnt[i] = 0; }       // (the counts become the fill's cursors)
-        carry += total;
-        __syncthreads();
-    }
-    if (tid == 0) S.off[S.Nd] = carry;
+    ch_scan_body(chamfer_side(A, (size_t)A.b0 + blockIdx.y, set));
 }
 
 __global__ __launch_bounds__(CH_ROW_THREADS)
 void k_chamfer_fill(const ChamferArgs A) {
     const int set = blockIdx.z;
     if (!(A.want >> set & 1)) return;
-    const ChamferSide S = chamfer_side(A, (size_t)A.b0 + blockIdx.y, set);
-    const int q = blockIdx.x * CH_ROW_THREADS + threadIdx.x;
-    if (q >= S.Nq) return;
-    const int t = chamfer_bucket(S, q);
-    if (t >= 0) S.list[S.off[t] + atomicAdd(&S.cnt[t], 1)] = q;
+    ch_fill_body(chamfer_side(A, (size_t)A.b0 + blockIdx.y, set), blockIdx.x * CH_ROW_THREADS + threadIdx.x);
 }
 
 __global__ __launch_bounds__(CH_ROW_THREADS)
 void k_chamfer_order(const ChamferArgs A) {
     const int set = blockIdx.z;
     if (!(A.want >> set & 1)) return;
-    const ChamferSide S = chamfer_side(A, (size_t)A.b0 + blockIdx.y, set);
-    const int q = blockIdx.x * CH_ROW_THREADS + threadIdx.x;
-    if (q >= S.Nq) return;
-    const int t = chamfer_bucket(S, q);
-    if (t < 0) return;
-    const int o = S.off[t], len = S.off[t + 1] - o;
-    S.sorted[o + ch_rank(S.list + o, len, q)] = q;
+    ch_order_body(chamfer_side(A, (size_t)A.b0 + blockIdx.y, set), blockIdx.x * CH_ROW_THREADS + threadIdx.x);
 }
 
 // what query q of the other set (target: the row at x) adds to that row: -c (y_q - x)

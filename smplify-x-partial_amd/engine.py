@@ -1182,6 +1182,187 @@ def chamfer_backward(a, b, fwd, grad, want=("a", "b"), mask_a=None, mask_b=None,
     return da, db
 
 
+# ---- differentiable point-to-triangle term (sfx_p2m_forward / _backward, csrc/p2m.hip) -----------------------------------------
+P2M_MAX_POINTS = 1 << 26                                                # SFX_P2M_MAX_POINTS
+_P2M_CACHE_SIZE = 8
+_p2m_scratch_cache = collections.OrderedDict()  # (device, B, Np, Nv) -> the scratch tensors of calls of that size
+_p2m_topology_cache = collections.OrderedDict()  # (topology, Nv) -> the checked faces and their device copies
+
+
+def p2m_forward_scratch_bytes(B, Np, Nv):
+    """SFX_P2M_FORWARD_SCRATCH_BYTES of include/sfx.h."""
+    return 4 * B * Np
+
+
+def p2m_backward_scratch_bytes(B, Np, Nv):
+    """SFX_P2M_BACKWARD_SCRATCH_BYTES of include/sfx.h."""
+    return 4 * B * (9 * Np + 2 * Nv + 1)
+
+
+def _p2m_scratch(which, nbytes, B, Np, Nv, dev):
+    """The scratch of sfx_p2m_forward ('fwd') or _backward ('bwd') for calls of one size on one device, kept like
+    _chamfer_scratch keeps its own."""
+    import torch
+    key = (dev, B, Np, Nv)
+    ent = _p2m_scratch_cache.get(key)
+    if ent is None:
+        ent = _p2m_scratch_cache[key] = {}
+        while len(_p2m_scratch_cache) > _P2M_CACHE_SIZE:
+            _p2m_scratch_cache.popitem(last=False)
+    else:
+        _p2m_scratch_cache.move_to_end(key)
+    if which not in ent:
+        ent[which] = torch.empty([max(1, nbytes // 4)], dtype=torch.int32, device=dev)
+    return ent[which]
+
+
+def _p2m_topology(faces, Nv):
+    """The cache entry of a topology against Nv vertices: shape, dtype and range are checked once per object (a tensor is
+    recognised by its storage and version, as in _render_topology; anything else by its contents), before where anything
+    lives.  The entry holds the int32 host copy and one device copy per device (_p2m_faces)."""
+    import hashlib
+    import torch
+    if torch.is_tensor(faces):
+        if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+            raise ValueError("faces: shape %s, expected (F, 3) with F >= 1" % (tuple(faces.shape),))
+        if faces.dtype not in (torch.int32, torch.int64):
+            raise ValueError("faces: torch.int32 or torch.int64 is needed, got %s" % faces.dtype)
+        key = ("tensor", faces.data_ptr(), faces._version, tuple(faces.shape), tuple(faces.stride()), faces.dtype, faces.device, Nv)
+    else:
+        host = np.ascontiguousarray(np.asarray(faces))
+        if host.ndim != 2 or host.shape[1] != 3 or host.shape[0] < 1 or host.dtype.kind not in "iu":
+            raise ValueError("faces: an integer array of shape (F, 3) with F >= 1 is needed, got %s %s" % (host.dtype, host.shape))
+        key = ("host", hashlib.sha1(host.tobytes()).hexdigest(), host.shape, host.dtype.str, Nv)
+    ent = _p2m_topology_cache.get(key)
+    if ent is None:
+        host = (faces.detach().cpu().numpy() if torch.is_tensor(faces) else host).astype(np.int64)
+        if host.shape[0] > P2M_MAX_POINTS:
+            raise ValueError("faces: %d faces, at most %d" % (host.shape[0], P2M_MAX_POINTS))
+        if host.min() < 0 or host.max() >= Nv:
+            raise ValueError("faces: vertex ids %d..%d outside the %d vertices" % (host.min(), host.max(), Nv))
+        ent = dict(keep=faces, F=int(host.shape[0]), host=np.ascontiguousarray(host.astype(np.int32)), dev={})
+        _p2m_topology_cache[key] = ent
+        while len(_p2m_topology_cache) > _P2M_CACHE_SIZE:
+            _p2m_topology_cache.popitem(last=False)
+    else:
+        _p2m_topology_cache.move_to_end(key)
+    return ent
+
+
+def _p2m_faces(ent, dev):
+    import torch
+    if dev not in ent["dev"]:
+        ent["dev"][dev] = torch.as_tensor(ent["host"], device=dev)
+    return ent["dev"][dev]
+
+
+def _p2m_args(points, vertices, faces, point_mask, point_weights, face_mask, rho):
+    """The checked inputs both point-to-triangle calls share: sizes, tensors as the library reads them, rho."""
+    import torch
+    B, Np = _points("points", points)
+    Nv = _points("vertices", vertices)[1]
+    rho = float(rho)
+    if not (np.isfinite(rho) and rho >= 0.0):
+        raise ValueError("rho: %r, a finite value >= 0 is needed" % (rho,))
+    if Np > P2M_MAX_POINTS or Nv > P2M_MAX_POINTS:
+        raise ValueError("points, vertices: %d and %d, at most %d each" % (Np, Nv, P2M_MAX_POINTS))
+    _expect_shape("vertices", vertices, (B, Nv, 3))
+    topo = _p2m_topology(faces, Nv)
+    F = topo["F"]
+    _expect_shape("point_mask", point_mask, (B, Np))
+    if face_mask is not None:
+        if not torch.is_tensor(face_mask):
+            raise TypeError("face_mask: a torch tensor is needed, got %s" % type(face_mask).__name__)
+        if tuple(face_mask.shape) not in ((F,), (B, F)):
+            raise ValueError("face_mask: shape %s, expected %s or %s" % (tuple(face_mask.shape), (F,), (B, F)))
+        if face_mask.dtype not in (torch.bool, torch.uint8):
+            raise ValueError("face_mask: torch.bool or torch.uint8 is needed, got %s" % face_mask.dtype)
+        if face_mask.dim() == 1:
+            face_mask = face_mask[None].expand(B, F).contiguous()
+    if point_weights is not None:
+        if not torch.is_tensor(point_weights):
+            raise TypeError("point_weights: a torch tensor is needed, got %s" % type(point_weights).__name__)
+        if tuple(point_weights.shape) != (B, Np):
+            raise ValueError("point_weights: shape %s, expected %s" % (tuple(point_weights.shape), (B, Np)))
+    points = A.tensor("points", points, (B, Np, 3))
+    dev = points.device
+    vertices = A.tensor("vertices", vertices, (B, Nv, 3), device=dev, holder="points")
+    point_mask = _point_mask("point_mask", point_mask, (B, Np), dev, "points")
+    face_mask = _point_mask("face_mask", face_mask, (B, F), dev, "points")
+    point_weights = A.tensor("point_weights", point_weights, (B, Np), device=dev, optional=True, holder="points")
+    return B, Np, Nv, F, dev, points, vertices, _p2m_faces(topo, dev), point_mask, point_weights, face_mask, rho
+
+
+def point_mesh_eval(points, vertices, faces, point_mask=None, point_weights=None, face_mask=None, rho=0.0, return_dist2=True,
+                    return_bary=True, stream=None):
+    """The point-to-triangle term from B point clouds to the surfaces of B meshes of one topology (sfx_p2m_forward; the
+    contract is in include/sfx.h): points [B, Np, 3], vertices [B, Nv, 3] float32 contiguous CUDA tensors; faces [F, 3] integers
+    (a CUDA / CPU tensor or an array: checked once per object for shape, dtype and range, its device copy cached); point_mask
+    [B, Np], face_mask [B, F] or [F] torch.bool / torch.uint8 or None (a masked point has no term, a masked face is no
+    candidate); point_weights [B, Np] float32 or None; rho = 0: squared distances, rho > 0: the GMoF rho^2 s / (s + rho^2).
+    Returns a dict of device tensors:
+      loss [B]            sum over the valid points of w rho(s) to the nearest point of the mesh's triangles
+      face [B, Np]        int32: the nearest face (the lowest index of a tie), -1 at a masked point or without a candidate
+      bary [B, Np, 3]     (u, v, w) of the closest point on it (with return_bary)
+      dist2 [B, Np]       its squared distance, float32 (with return_dist2)
+      valid [B]           int32: valid points
+    Face, squared distance and barycentrics are a float32 numpy restatement of the contract bit for bit; a mesh's bits depend
+    on its own data only.  Only enqueues on the current (or the given) stream; the scratch of a size is cached, so calls of one
+    size belong on one stream."""
+    import torch
+    B, Np, Nv, F, dev, points, vertices, faces, point_mask, point_weights, face_mask, rho = _p2m_args(
+        points, vertices, faces, point_mask, point_weights, face_mask, rho)
+    out = dict(loss=torch.empty([B], dtype=torch.float32, device=dev), face=torch.empty([B, Np], dtype=torch.int32, device=dev),
+               valid=torch.empty([B], dtype=torch.int32, device=dev))
+    if return_bary:
+        out["bary"] = torch.empty([B, Np, 3], dtype=torch.float32, device=dev)
+    if return_dist2:
+        out["dist2"] = torch.empty([B, Np], dtype=torch.float32, device=dev)
+    if B > 0:
+        nbytes = p2m_forward_scratch_bytes(B, Np, Nv)
+        scratch = _p2m_scratch("fwd", nbytes, B, Np, Nv, dev)
+        with torch.cuda.device(dev):
+            capi.check(capi.load().sfx_p2m_forward(
+                B, Np, Nv, F, A.ptr(points), A.ptr(vertices), A.ptr(faces), A.ptr(point_mask), A.ptr(face_mask),
+                A.ptr(point_weights), rho, A.ptr(out["face"]), A.ptr(out.get("bary")), A.ptr(out.get("dist2")),
+                A.ptr(out["loss"]), A.ptr(out["valid"]), A.ptr(scratch), nbytes, A.stream(stream, dev)))
+    return out
+
+
+def point_mesh_backward(points, vertices, faces, fwd, grad, want=("points", "vertices"), point_mask=None, point_weights=None,
+                        rho=0.0, stream=None):
+    """Gradient of the point-to-triangle term (sfx_p2m_backward): `fwd` is what point_mesh_eval returned for the same inputs
+    (its face is read), grad [B] the upstream of loss; point_mask, point_weights and rho as in that call.  want: which of
+    'points', 'vertices' to compute.  Returns (dp [B, Np, 3] or None, dv [B, Nv, 3] or None).  A point's row is c (p - q); a
+    vertex's row sums -(c bary_k)(p - q) over the corners that name it, in float64 in ascending corner entry through an inverted
+    index built on the device: no float atomics, the same bits in every run and in any batch.  Only enqueues on the current (or
+    the given) stream."""
+    import torch
+    want = tuple(want)
+    if not want or [w for w in want if w not in ("points", "vertices")]:
+        raise ValueError("want: some of ('points', 'vertices'), got %r" % (want,))
+    B, Np, Nv, F, dev, points, vertices, faces, point_mask, point_weights, _, rho = _p2m_args(
+        points, vertices, faces, point_mask, point_weights, None, rho)
+    if not isinstance(fwd, dict) or "face" not in fwd:
+        raise TypeError("fwd: the dict point_mesh_eval returned is needed (face)")
+    if not torch.is_tensor(grad):
+        raise TypeError("grad: a torch tensor is needed, got %s" % type(grad).__name__)
+    if tuple(grad.shape) != (B,):
+        raise ValueError("grad: shape %s, expected %s" % (tuple(grad.shape), (B,)))
+    face = A.tensor("fwd['face']", fwd["face"], (B, Np), device=dev, dtype=torch.int32, holder="points")
+    grad = A.tensor("grad", grad, (B,), device=dev, holder="points")
+    dp = torch.empty([B, Np, 3], dtype=torch.float32, device=dev) if "points" in want else None
+    dv = torch.empty([B, Nv, 3], dtype=torch.float32, device=dev) if "vertices" in want else None
+    if B > 0:
+        nbytes = p2m_backward_scratch_bytes(B, Np, Nv)
+        scratch = _p2m_scratch("bwd", nbytes, B, Np, Nv, dev)
+        with torch.cuda.device(dev):
+            capi.check(capi.load().sfx_p2m_backward(
+                B, Np, Nv, F, A.ptr(points), A.ptr(vertices), A.ptr(faces), A.ptr(point_mask), A.ptr(point_weights), rho,
+                A.ptr(face), A.ptr(grad), A.ptr(dp), A.ptr(dv), A.ptr(scratch), nbytes, A.stream(stream, dev)))
+    return dp, dv
+
+
 # ---- fitted meshes over their images (sfx_render_meshes, csrc/raster.hip) -----------------------------------------------------
 RENDER_MAX_LIGHTS = capi.RENDER_MAX_LIGHTS
 RENDER_BASE_RGB = (0.4, 0.4, 0.7)                                       # utils.py:499 vertex_colors
