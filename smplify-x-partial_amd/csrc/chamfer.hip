@@ -19,18 +19,16 @@
 //   k_chamfer_fill      every query takes the next free place of its bucket (integer atomic cursor: any order)
 //   k_chamfer_order     every query moves to its rank inside its bucket (ch_rank): the buckets are now ascending, whatever the
 //                       fill's order was
-//   k_chamfer_rows      one thread per output row: its gather term, then its list.  Up to CH_SERIAL_MAX entries the thread walks
-//                       them; a longer list is cut into 64 segments summed by the 64 lanes of the row's wave and added in segment
-//                       order (ch_seg_len).  Every sum is float64 in a fixed order and is rounded to float32 once.
-// No kernel uses a float atomic; a mesh's bits depend on its own points only.  The bodies of the reduce and of the four index
-// steps are in csrc/chamfer_index.h, which csrc/p2m.hip (the point-to-triangle term) uses too.
+//   k_chamfer_rows      one thread per output row: its gather term, then its list by ch_rows_body, which states the order of
+//                       the sum.  Every sum is float64 in a fixed order and is rounded to float32 once.
+// No kernel uses a float atomic; a mesh's bits depend on its own points only.  The bodies of the reduce, of the four index
+// steps and of the walk of a row's list are in csrc/chamfer_index.h, which csrc/p2m.hip (the point-to-triangle term) uses too;
+// so are what both units' entries refuse alike and their loop over chunks of meshes.
 #include "../../include/sfx.h"
 #include "sfx_internal.h"
 #include "wave_ops.h"
 #include "chamfer_math.h"
 #include "chamfer_index.h"
-
-#include <cmath>
 
 #define CH_NN_THREADS 256
 #define CH_NN_QPT 2
@@ -208,7 +206,8 @@ void k_chamfer_order(const ChamferArgs A) {
 }
 
 // what query q of the other set (target: the row at x) adds to that row: -c (y_q - x)
-__device__ __forceinline__ void chamfer_scatter_term(const ChamferSide& S, double r2, int q, float x0, float x1, float x2, double (&p)[3]) {
+__device__ __forceinline__ void chamfer_scatter_term(const ChamferSide& S, double r2, int q, const float (&x)[3], double (&p)[3]) {
+    const float x0 = x[0], x1 = x[1], x2 = x[2];
     const float y0 = S.Y[(size_t)q * 3], y1 = S.Y[(size_t)q * 3 + 1], y2 = S.Y[(size_t)q * 3 + 2];
     const float s = ch_dist2(y0, y1, y2, x0, x1, x2);
     const double c = ch_coef(S.g_in, S.wy ? S.wy[q] : 1.f, s, r2);
@@ -221,60 +220,32 @@ void k_chamfer_rows(const ChamferArgs A) {
     if (!(A.want >> set & 1)) return;
     const ChamferSide S = chamfer_side(A, (size_t)A.b0 + blockIdx.y, set);
     if ((int)(blockIdx.x * CH_ROW_THREADS) >= S.Nd) return;             // (the whole workgroup)
-    const int r = blockIdx.x * CH_ROW_THREADS + threadIdx.x, lane = threadIdx.x & 63;
+    const int r = blockIdx.x * CH_ROW_THREADS + threadIdx.x;
     const bool live = r < S.Nd;
-    float x0 = 0.f, x1 = 0.f, x2 = 0.f;
+    float x[3] = {0.f, 0.f, 0.f};
     double row[3] = {0.0, 0.0, 0.0};
-    int o = 0, len = 0;
     if (live) {
-        x0 = S.X[(size_t)r * 3]; x1 = S.X[(size_t)r * 3 + 1]; x2 = S.X[(size_t)r * 3 + 2];
+        x[0] = S.X[(size_t)r * 3]; x[1] = S.X[(size_t)r * 3 + 1]; x[2] = S.X[(size_t)r * 3 + 2];
         const int t = (!S.mx || S.mx[r]) ? S.idx_own[r] : -1;
         if (ch_index_ok(t, S.Nq)) {                                       // the gather term: c (x - y_t)
+            const float x0 = x[0], x1 = x[1], x2 = x[2];
             const float y0 = S.Y[(size_t)t * 3], y1 = S.Y[(size_t)t * 3 + 1], y2 = S.Y[(size_t)t * 3 + 2];
             const float s = ch_dist2(x0, x1, x2, y0, y1, y2);
             const double c = ch_coef(S.g_own, S.wx ? S.wx[r] : 1.f, s, A.r2);
             row[0] = c * ((double)x0 - (double)y0); row[1] = c * ((double)x1 - (double)y1); row[2] = c * ((double)x2 - (double)y2);
         }
-        o = S.off[r]; len = S.off[r + 1] - o;
-        if (len > 0 && len <= CH_SERIAL_MAX) {                            // one segment, walked by this thread
-            double p[3] = {0.0, 0.0, 0.0};
-            for (int k = 0; k < len; ++k) chamfer_scatter_term(S, A.r2, S.sorted[o + k], x0, x1, x2, p);
-            row[0] += p[0]; row[1] += p[1]; row[2] += p[2];
-        }
     }
-    // long lists, one after the other: the wave's lanes take a segment each, the segment sums are added in segment order
-    unsigned long long todo = __ballot(live && len > CH_SERIAL_MAX);
-    while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        const int lo = __builtin_amdgcn_readlane(o, src), ll = __builtin_amdgcn_readlane(len, src);
-        const float t0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x0), src));
-        const float t1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x1), src));
-        const float t2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x2), src));
-        const int seg = ch_seg_len(ll), n_seg = (ll + seg - 1) / seg;     // (n_seg <= 64: a lane each)
-        double p[3] = {0.0, 0.0, 0.0};
-        const int k0 = min(ll, lane * seg), k1 = min(ll, k0 + seg);
-        for (int k = k0; k < k1; ++k) chamfer_scatter_term(S, A.r2, S.sorted[lo + k], t0, t1, t2, p);
-        for (int l = 0; l < n_seg; ++l) {                                 // (l is wave-uniform)
-            const double v0 = readlane_f64(p[0], l), v1 = readlane_f64(p[1], l), v2 = readlane_f64(p[2], l);
-            if (lane == src) { row[0] += v0; row[1] += v1; row[2] += v2; }
-        }
-    }
+    ch_rows_body(S.off, S.sorted, r, live, x, row, [&](const float (&t)[3], int q, double (&p)[3]) { chamfer_scatter_term(S, A.r2, q, t, p); });
     if (live && S.out) { S.out[(size_t)r * 3] = (float)row[0]; S.out[(size_t)r * 3 + 1] = (float)row[1]; S.out[(size_t)r * 3 + 2] = (float)row[2]; }
 }
 
 // ---------------------------------------------------------------------------------------------------------- the entries
-// what both entries refuse; 0 = fine
+// what both entries refuse, in the order B, sizes, rho, scratch; 0 = fine
 static int chamfer_refuse(const char* entry, int32_t B, int32_t Na, int32_t Nb, float rho, const void* scratch,
                           int64_t scratch_bytes, size_t need) {
-    if (B < 0) { sfx_set_error("%s: B = %d", entry, B); return -1; }
-    if (Na < 1 || Nb < 1 || Na > SFX_CHAMFER_MAX_POINTS || Nb > SFX_CHAMFER_MAX_POINTS) {
+    if (B >= 0 && (Na < 1 || Nb < 1 || Na > SFX_CHAMFER_MAX_POINTS || Nb > SFX_CHAMFER_MAX_POINTS)) {
         sfx_set_error("%s: Na = %d, Nb = %d points, supported 1..%d", entry, Na, Nb, SFX_CHAMFER_MAX_POINTS); return -1; }
-    if (!std::isfinite(rho) || rho < 0.f) { sfx_set_error("%s: rho = %g, a finite value >= 0 is needed", entry, (double)rho); return -1; }
-    if (!scratch || scratch_bytes < 0 || (size_t)scratch_bytes < need) {
-        sfx_set_error("%s: scratch of %lld bytes, %zu are needed for B = %d, Na = %d, Nb = %d", entry,
-                      scratch ? (long long)scratch_bytes : 0LL, need, B, Na, Nb); return -1; }
-    return 0;
+    return ch_refuse(entry, B, rho, scratch, scratch_bytes, need, "Na", Na, "Nb", Nb);
 }
 
 extern "C" int sfx_chamfer_forward(int32_t B, int32_t Na, int32_t Nb, const float* a_dev, const float* b_dev,
@@ -293,15 +264,13 @@ extern "C" int sfx_chamfer_forward(int32_t B, int32_t Na, int32_t Nb, const floa
     A.val = (float*)scratch_dev; A.loss = loss_dev; A.valid = valid_dev;
     hipStream_t s = (hipStream_t)stream;
     const int per = CH_NN_THREADS * CH_NN_QPT, tiles = (std::max(Na, Nb) + per - 1) / per;
-    for (int b0 = 0; b0 < B; b0 += CH_GRID_Y) {              // (gridDim.y holds 65 535 meshes)
-        A.b0 = b0;
-        const int nb = std::min(B - b0, CH_GRID_Y);
+    return ch_mesh_chunks(A, B, [&](int nb) {
         hipLaunchKernelGGL(k_chamfer_nearest, dim3(tiles, nb, 2), dim3(CH_NN_THREADS), 0, s, A);
         SFX_CHECK(hipGetLastError());
         hipLaunchKernelGGL(k_chamfer_reduce, dim3(2, nb), dim3(CH_RED_THREADS), 0, s, A);
         SFX_CHECK(hipGetLastError());
-    }
-    return 0;
+        return 0;
+    });
 }
 
 extern "C" int sfx_chamfer_backward(int32_t B, int32_t Na, int32_t Nb, const float* a_dev, const float* b_dev,
@@ -324,9 +293,7 @@ extern "C" int sfx_chamfer_backward(int32_t B, int32_t Na, int32_t Nb, const flo
     hipStream_t s = (hipStream_t)stream;
     SFX_CHECK(hipMemsetAsync(A.cnt, 0, sizeof(int) * Bz * n, s));
     const int tiles = (std::max(Na, Nb) + CH_ROW_THREADS - 1) / CH_ROW_THREADS;
-    for (int b0 = 0; b0 < B; b0 += CH_GRID_Y) {
-        A.b0 = b0;
-        const int nb = std::min(B - b0, CH_GRID_Y);
+    return ch_mesh_chunks(A, B, [&](int nb) {
         hipLaunchKernelGGL(k_chamfer_count, dim3(tiles, nb, 2), dim3(CH_ROW_THREADS), 0, s, A);
         SFX_CHECK(hipGetLastError());
         hipLaunchKernelGGL(k_chamfer_scan, dim3(2, nb), dim3(CH_RED_THREADS), 0, s, A);
@@ -337,6 +304,6 @@ extern "C" int sfx_chamfer_backward(int32_t B, int32_t Na, int32_t Nb, const flo
         SFX_CHECK(hipGetLastError());
         hipLaunchKernelGGL(k_chamfer_rows, dim3(tiles, nb, 2), dim3(CH_ROW_THREADS), 0, s, A);
         SFX_CHECK(hipGetLastError());
-    }
-    return 0;
+        return 0;
+    });
 }

@@ -19,7 +19,7 @@
 //   k_p2m_corners   corner[e] = the vertex of corner k of point i's face, -1 where the point has no term
 //   k_p2m_count / _scan / _fill / _order     the four integer steps
 //   k_p2m_point_rows    dp
-//   k_p2m_vertex_rows   dv: the row's list in ascending e, cut into segments by ch_seg_len, float64, rounded once
+//   k_p2m_vertex_rows   dv: the row's list in ascending e by ch_rows_body of csrc/chamfer_index.h, float64, rounded once
 // s, q and the barycentrics are formed again from the points with the header: the same bits as the forward's.
 #include "../../include/sfx.h"
 #include "sfx_internal.h"
@@ -27,9 +27,6 @@
 #include "chamfer_math.h"
 #include "chamfer_index.h"
 #include "p2m_math.h"
-
-#include <algorithm>
-#include <cmath>
 
 #define P2M_THREADS 256
 #define P2M_QPT 2
@@ -237,48 +234,21 @@ __global__ __launch_bounds__(CH_ROW_THREADS)
 void k_p2m_vertex_rows(const P2mArgs A) {
     const size_t mesh = (size_t)A.b0 + blockIdx.y;
     const P2mSide S = p2m_side(A, mesh);
-    const int r = blockIdx.x * CH_ROW_THREADS + threadIdx.x, lane = threadIdx.x & 63;
+    const int r = blockIdx.x * CH_ROW_THREADS + threadIdx.x;
     const bool live = r < S.Nd;
+    const float none[3] = {0.f, 0.f, 0.f};                              // (a corner's term reads nothing of its vertex)
     double row[3] = {0.0, 0.0, 0.0};
-    int o = 0, len = 0;
-    if (live) {
-        o = S.off[r]; len = S.off[r + 1] - o;
-        if (len > 0 && len <= CH_SERIAL_MAX) {                            // one segment, walked by this thread
-            double p[3] = {0.0, 0.0, 0.0};
-            for (int k = 0; k < len; ++k) p2m_scatter_term(A, S, S.sorted[o + k], p);
-            row[0] += p[0]; row[1] += p[1]; row[2] += p[2];
-        }
-    }
-    // long lists, one after the other: the wave's lanes take a segment each, the segment sums are added in segment order
-    unsigned long long todo = __ballot(live && len > CH_SERIAL_MAX);
-    while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        const int lo = __builtin_amdgcn_readlane(o, src), ll = __builtin_amdgcn_readlane(len, src);
-        const int seg = ch_seg_len(ll), n_seg = (ll + seg - 1) / seg;     // (n_seg <= 64: a lane each)
-        double p[3] = {0.0, 0.0, 0.0};
-        const int k0 = min(ll, lane * seg), k1 = min(ll, k0 + seg);
-        for (int k = k0; k < k1; ++k) p2m_scatter_term(A, S, S.sorted[lo + k], p);
-        for (int l = 0; l < n_seg; ++l) {                                 // (l is wave-uniform)
-            const double v0 = readlane_f64(p[0], l), v1 = readlane_f64(p[1], l), v2 = readlane_f64(p[2], l);
-            if (lane == src) { row[0] += v0; row[1] += v1; row[2] += v2; }
-        }
-    }
+    ch_rows_body(S.off, S.sorted, r, live, none, row, [&](const float (&)[3], int e, double (&acc)[3]) { p2m_scatter_term(A, S, e, acc); });
     if (live) { float* out = A.dv + (mesh * A.Nv + r) * 3; out[0] = (float)row[0]; out[1] = (float)row[1]; out[2] = (float)row[2]; }
 }
 
 // ---------------------------------------------------------------------------------------------------------- the entries
-// what both entries refuse; 0 = fine
+// what both entries refuse, in the order B, sizes, rho, scratch; 0 = fine
 static int p2m_refuse(const char* entry, int32_t B, int32_t Np, int32_t Nv, int32_t F, float rho, const void* scratch,
                       int64_t scratch_bytes, size_t need) {
-    if (B < 0) { sfx_set_error("%s: B = %d", entry, B); return -1; }
-    if (Np < 1 || Np > SFX_P2M_MAX_POINTS || Nv < 1 || Nv > SFX_P2M_MAX_POINTS || F < 1 || F > SFX_P2M_MAX_POINTS) {
+    if (B >= 0 && (Np < 1 || Np > SFX_P2M_MAX_POINTS || Nv < 1 || Nv > SFX_P2M_MAX_POINTS || F < 1 || F > SFX_P2M_MAX_POINTS)) {
         sfx_set_error("%s: Np = %d points, Nv = %d vertices, F = %d faces, supported 1..%d each", entry, Np, Nv, F, SFX_P2M_MAX_POINTS); return -1; }
-    if (!std::isfinite(rho) || rho < 0.f) { sfx_set_error("%s: rho = %g, a finite value >= 0 is needed", entry, (double)rho); return -1; }
-    if (!scratch || scratch_bytes < 0 || (size_t)scratch_bytes < need) {
-        sfx_set_error("%s: scratch of %lld bytes, %zu are needed for B = %d, Np = %d, Nv = %d", entry,
-                      scratch ? (long long)scratch_bytes : 0LL, need, B, Np, Nv); return -1; }
-    return 0;
+    return ch_refuse(entry, B, rho, scratch, scratch_bytes, need, "Np", Np, "Nv", Nv);
 }
 
 extern "C" int sfx_p2m_forward(int32_t B, int32_t Np, int32_t Nv, int32_t F, const float* p_dev, const float* v_dev,
@@ -296,15 +266,13 @@ extern "C" int sfx_p2m_forward(int32_t B, int32_t Np, int32_t Nv, int32_t F, con
     A.val = (float*)scratch_dev; A.loss = loss_dev; A.valid = valid_dev;
     hipStream_t s = (hipStream_t)stream;
     const int per = P2M_THREADS * P2M_QPT, tiles = (Np + per - 1) / per;
-    for (int b0 = 0; b0 < B; b0 += CH_GRID_Y) {              // (gridDim.y holds 65 535 meshes)
-        A.b0 = b0;
-        const int nb = std::min(B - b0, CH_GRID_Y);
+    return ch_mesh_chunks(A, B, [&](int nb) {
         hipLaunchKernelGGL(k_p2m_nearest, dim3(tiles, nb), dim3(P2M_THREADS), 0, s, A);
         SFX_CHECK(hipGetLastError());
         hipLaunchKernelGGL(k_p2m_reduce, dim3(nb), dim3(CH_RED_THREADS), 0, s, A);
         SFX_CHECK(hipGetLastError());
-    }
-    return 0;
+        return 0;
+    });
 }
 
 extern "C" int sfx_p2m_backward(int32_t B, int32_t Np, int32_t Nv, int32_t F, const float* p_dev, const float* v_dev,
@@ -327,14 +295,12 @@ extern "C" int sfx_p2m_backward(int32_t B, int32_t Np, int32_t Nv, int32_t F, co
     if (dv_dev) SFX_CHECK(hipMemsetAsync(A.cnt, 0, sizeof(int) * Bz * nv, s));
     const int point_tiles = (Np + CH_ROW_THREADS - 1) / CH_ROW_THREADS, entry_tiles = (int)((n3 + CH_ROW_THREADS - 1) / CH_ROW_THREADS);
     const int vertex_tiles = (Nv + CH_ROW_THREADS - 1) / CH_ROW_THREADS;
-    for (int b0 = 0; b0 < B; b0 += CH_GRID_Y) {
-        A.b0 = b0;
-        const int nb = std::min(B - b0, CH_GRID_Y);
+    return ch_mesh_chunks(A, B, [&](int nb) {
         if (dp_dev) {
             hipLaunchKernelGGL(k_p2m_point_rows, dim3(point_tiles, nb), dim3(CH_ROW_THREADS), 0, s, A);
             SFX_CHECK(hipGetLastError());
         }
-        if (!dv_dev) continue;
+        if (!dv_dev) return 0;
         hipLaunchKernelGGL(k_p2m_corners, dim3(entry_tiles, nb), dim3(CH_ROW_THREADS), 0, s, A);
         SFX_CHECK(hipGetLastError());
         hipLaunchKernelGGL(k_p2m_count, dim3(entry_tiles, nb), dim3(CH_ROW_THREADS), 0, s, A);
@@ -347,6 +313,6 @@ extern "C" int sfx_p2m_backward(int32_t B, int32_t Np, int32_t Nv, int32_t F, co
         SFX_CHECK(hipGetLastError());
         hipLaunchKernelGGL(k_p2m_vertex_rows, dim3(vertex_tiles, nb), dim3(CH_ROW_THREADS), 0, s, A);
         SFX_CHECK(hipGetLastError());
-    }
-    return 0;
+        return 0;
+    });
 }

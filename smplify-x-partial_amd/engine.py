@@ -961,18 +961,55 @@ def _points(name, t):
     return int(t.shape[0]), int(t.shape[1])
 
 
-def _expect_shape(name, t, shape):
-    """The shape (and, for a mask, the dtype) of a further argument, checked before where ANY argument lives: A.tensor
-    checks one tensor at a time, what it is before where it is."""
+def _expect(name, t, *shapes, mask=False):
+    """What a further argument is, refused before where ANY argument lives: a tensor of one of `shapes` and, for a mask, of
+    torch.bool / torch.uint8; None passes.  A.tensor remains the single check of what is handed to the library, but it checks
+    one tensor at a time, what it is before where it is, and every "what" of a call is to be refused before any "where"."""
     import torch
     if t is None:
         return
     if not torch.is_tensor(t):
         raise TypeError("%s: a torch tensor is needed, got %s" % (name, type(t).__name__))
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError("%s: shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
-    if len(shape) == 2 and t.dtype not in (torch.bool, torch.uint8):
+    if tuple(t.shape) not in shapes:
+        raise ValueError("%s: shape %s, expected %s" % (name, tuple(t.shape), " or ".join(str(tuple(n)) for n in shapes)))
+    if mask and t.dtype not in (torch.bool, torch.uint8):
         raise ValueError("%s: torch.bool or torch.uint8 is needed, got %s" % (name, t.dtype))
+
+
+def check_rho(rho):
+    """rho of a robustified term as a float; refuses what the library would."""
+    rho = float(rho)
+    if not (np.isfinite(rho) and rho >= 0.0):
+        raise ValueError("rho: %r, a finite value >= 0 is needed" % (rho,))
+    return rho
+
+
+_CACHE_SIZE = 8
+
+
+def _cached(cache, key, make, size=_CACHE_SIZE):
+    """cache[key] of an OrderedDict, made by make() on a miss (an insert beyond `size` drops the oldest entries, and with them
+    whatever they held on a device); a hit marks the entry recent."""
+    if key in cache:
+        cache.move_to_end(key)
+        return cache[key]
+    ent = cache[key] = make()
+    while len(cache) > size:
+        cache.popitem(last=False)
+    return ent
+
+
+_scratch_cache = collections.OrderedDict()      # (term, device, sizes) -> the scratch tensors of that term's calls of that size
+
+
+def _term_scratch(term, which, nbytes, dev, *sizes):
+    """The scratch of a term's forward ('fwd') or backward ('bwd') for calls of one size on one device: made once and kept
+    (the last few sizes), so calls of one size belong on one stream."""
+    import torch
+    ent = _cached(_scratch_cache, (term, dev) + sizes, dict)
+    if which not in ent:
+        ent[which] = torch.empty([max(1, nbytes // 4)], dtype=torch.int32, device=dev)
+    return ent[which]
 
 
 def _point_mask(name, mask, shape, dev, holder):
@@ -1000,8 +1037,8 @@ def align_errors(est, gt, mode="procrustes", mask=None, anchors=(2, 3), return_t
             raise ValueError("anchors: %d given, supported 1..%d" % (anc.size, ALIGN_MAX_ANCHORS))
         if anc.min() < 0 or anc.max() >= N:
             raise ValueError("anchors: %s outside the %d points" % (anc.tolist(), N))
-    _expect_shape("gt", gt, (B, N, 3))
-    _expect_shape("mask", mask, (B, N))
+    _expect("gt", gt, (B, N, 3))
+    _expect("mask", mask, (B, N), mask=True)
     est = A.tensor("est", est, (B, N, 3))
     dev = est.device
     gt = A.tensor("gt", gt, (B, N, 3), device=dev, holder="est")
@@ -1032,9 +1069,9 @@ def nearest_distances(a, b, thresholds=(), mask_a=None, mask_b=None, return_dist
     th = capi.f64(list(thresholds)).reshape(-1)
     if th.size > NEAREST_MAX_THRESH:
         raise ValueError("thresholds: %d given, at most %d" % (th.size, NEAREST_MAX_THRESH))
-    _expect_shape("b", b, (B, Nb, 3))
-    _expect_shape("mask_a", mask_a, (B, Na))
-    _expect_shape("mask_b", mask_b, (B, Nb))
+    _expect("b", b, (B, Nb, 3))
+    _expect("mask_a", mask_a, (B, Na), mask=True)
+    _expect("mask_b", mask_b, (B, Nb), mask=True)
     a = A.tensor("a", a, (B, Na, 3))
     dev = a.device
     b = A.tensor("b", b, (B, Nb, 3), device=dev, holder="a")
@@ -1057,8 +1094,6 @@ def nearest_distances(a, b, thresholds=(), mask_a=None, mask_b=None, return_dist
 
 # ---- differentiable nearest-point term between point sets (sfx_chamfer_forward / _backward, csrc/chamfer.hip) ---------------
 CHAMFER_MAX_POINTS = 1 << 26                                            # SFX_CHAMFER_MAX_POINTS
-_CHAMFER_CACHE_SIZE = 8
-_chamfer_cache = collections.OrderedDict()      # (device, B, Na, Nb) -> the scratch tensors of calls of that size
 
 
 def chamfer_forward_scratch_bytes(B, Na, Nb):
@@ -1071,42 +1106,18 @@ def chamfer_backward_scratch_bytes(B, Na, Nb):
     return 4 * B * (4 * (Na + Nb) + 2)
 
 
-def _chamfer_scratch(which, nbytes, B, Na, Nb, dev):
-    """The scratch of sfx_chamfer_forward ('fwd') or _backward ('bwd') for calls of one size on one device: made once and kept
-    (the last few sizes), so calls of one size belong on one stream."""
-    import torch
-    key = (dev, B, Na, Nb)
-    ent = _chamfer_cache.get(key)
-    if ent is None:
-        ent = _chamfer_cache[key] = {}
-        while len(_chamfer_cache) > _CHAMFER_CACHE_SIZE:
-            _chamfer_cache.popitem(last=False)
-    else:
-        _chamfer_cache.move_to_end(key)
-    if which not in ent:
-        ent[which] = torch.empty([max(1, nbytes // 4)], dtype=torch.int32, device=dev)
-    return ent[which]
-
-
 def _chamfer_args(a, b, mask_a, mask_b, weight_a, weight_b, rho):
     """The checked inputs both chamfer calls share: sizes, tensors as the library reads them, rho."""
-    import torch
     B, Na = _points("a", a)
     Nb = _points("b", b)[1]
-    rho = float(rho)
-    if not (np.isfinite(rho) and rho >= 0.0):
-        raise ValueError("rho: %r, a finite value >= 0 is needed" % (rho,))
+    rho = check_rho(rho)
     if Na > CHAMFER_MAX_POINTS or Nb > CHAMFER_MAX_POINTS:
         raise ValueError("a, b: %d and %d points, at most %d each" % (Na, Nb, CHAMFER_MAX_POINTS))
-    _expect_shape("b", b, (B, Nb, 3))
-    _expect_shape("mask_a", mask_a, (B, Na))
-    _expect_shape("mask_b", mask_b, (B, Nb))
-    for name, w, n in (("weight_a", weight_a, Na), ("weight_b", weight_b, Nb)):
-        if w is not None:
-            if not torch.is_tensor(w):
-                raise TypeError("%s: a torch tensor is needed, got %s" % (name, type(w).__name__))
-            if tuple(w.shape) != (B, n):
-                raise ValueError("%s: shape %s, expected %s" % (name, tuple(w.shape), (B, n)))
+    _expect("b", b, (B, Nb, 3))
+    _expect("mask_a", mask_a, (B, Na), mask=True)
+    _expect("mask_b", mask_b, (B, Nb), mask=True)
+    _expect("weight_a", weight_a, (B, Na))
+    _expect("weight_b", weight_b, (B, Nb))
     a = A.tensor("a", a, (B, Na, 3))
     dev = a.device
     b = A.tensor("b", b, (B, Nb, 3), device=dev, holder="a")
@@ -1140,7 +1151,7 @@ def chamfer_eval(a, b, mask_a=None, mask_b=None, weight_a=None, weight_b=None, r
         out["dist2_ba"] = torch.empty([B, Nb], dtype=torch.float32, device=dev)
     if B > 0:
         nbytes = chamfer_forward_scratch_bytes(B, Na, Nb)
-        scratch = _chamfer_scratch("fwd", nbytes, B, Na, Nb, dev)
+        scratch = _term_scratch("chamfer", "fwd", nbytes, dev, B, Na, Nb)
         with torch.cuda.device(dev):
             capi.check(capi.load().sfx_chamfer_forward(
                 B, Na, Nb, A.ptr(a), A.ptr(b), A.ptr(mask_a), A.ptr(mask_b), A.ptr(weight_a), A.ptr(weight_b), rho,
@@ -1163,10 +1174,7 @@ def chamfer_backward(a, b, fwd, grad, want=("a", "b"), mask_a=None, mask_b=None,
     B, Na, Nb, dev, a, b, mask_a, mask_b, weight_a, weight_b, rho = _chamfer_args(a, b, mask_a, mask_b, weight_a, weight_b, rho)
     if not isinstance(fwd, dict) or "idx_ab" not in fwd or "idx_ba" not in fwd:
         raise TypeError("fwd: the dict chamfer_eval returned is needed (idx_ab, idx_ba)")
-    if not torch.is_tensor(grad):
-        raise TypeError("grad: a torch tensor is needed, got %s" % type(grad).__name__)
-    if tuple(grad.shape) != (B, 2):
-        raise ValueError("grad: shape %s, expected %s" % (tuple(grad.shape), (B, 2)))
+    _expect("grad", grad, (B, 2))
     idx_ab = A.tensor("fwd['idx_ab']", fwd["idx_ab"], (B, Na), device=dev, dtype=torch.int32, holder="a")
     idx_ba = A.tensor("fwd['idx_ba']", fwd["idx_ba"], (B, Nb), device=dev, dtype=torch.int32, holder="a")
     grad = A.tensor("grad", grad, (B, 2), device=dev, holder="a")
@@ -1174,7 +1182,7 @@ def chamfer_backward(a, b, fwd, grad, want=("a", "b"), mask_a=None, mask_b=None,
     db = torch.empty([B, Nb, 3], dtype=torch.float32, device=dev) if "b" in want else None
     if B > 0:
         nbytes = chamfer_backward_scratch_bytes(B, Na, Nb)
-        scratch = _chamfer_scratch("bwd", nbytes, B, Na, Nb, dev)
+        scratch = _term_scratch("chamfer", "bwd", nbytes, dev, B, Na, Nb)
         with torch.cuda.device(dev):
             capi.check(capi.load().sfx_chamfer_backward(
                 B, Na, Nb, A.ptr(a), A.ptr(b), A.ptr(mask_a), A.ptr(mask_b), A.ptr(weight_a), A.ptr(weight_b), rho,
@@ -1182,11 +1190,56 @@ def chamfer_backward(a, b, fwd, grad, want=("a", "b"), mask_a=None, mask_b=None,
     return da, db
 
 
+# ---- a mesh topology as the device calls read it (point_mesh_*, render_meshes) --------------------------------------------------
+_topology_cache = collections.OrderedDict()     # (faces object, V) -> the checked faces and what each device holds of them
+
+
+def _checked_faces(faces, V):
+    """`faces` as an int64 host array [F, 3] after the one check of its shape, dtype and vertex ids against V vertices."""
+    f = np.asarray(faces)
+    if f.ndim != 2 or f.shape[1] != 3 or f.shape[0] < 1 or f.dtype.kind not in "iu":
+        raise ValueError("faces: an integer array of shape (F, 3) with F >= 1 is needed, got %s %s" % (f.dtype, f.shape))
+    f = f.astype(np.int64)
+    if V < 1 or f.min() < 0 or f.max() >= V:
+        raise ValueError("faces: vertex ids %d..%d outside the %d vertices" % (f.min(), f.max(), V))
+    return f
+
+
+def _topology(faces, V):
+    """The cache entry of a topology against V vertices: checked once per object, whatever lives where.  A tensor is recognised
+    by its storage and version (the entry keeps it alive, so the address cannot be handed out again), anything else by its
+    contents.  The entry holds the int32 host copy, F and, per device, what _topology_on keeps there."""
+    import hashlib
+    import torch
+    if torch.is_tensor(faces):
+        if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+            raise ValueError("faces: shape %s, expected (F, 3) with F >= 1" % (tuple(faces.shape),))
+        if faces.dtype not in (torch.int32, torch.int64):
+            raise ValueError("faces: torch.int32 or torch.int64 is needed, got %s" % faces.dtype)
+        key = ("tensor", faces.data_ptr(), faces._version, tuple(faces.shape), tuple(faces.stride()), faces.dtype, faces.device, V)
+        host = faces.detach().cpu().numpy
+    else:
+        arr = np.ascontiguousarray(np.asarray(faces))
+        key = ("host", hashlib.sha1(arr.tobytes()).hexdigest(), arr.shape, arr.dtype.str, V)
+        host = lambda: arr
+
+    def make():
+        f = _checked_faces(host(), V)
+        return dict(keep=faces, F=int(f.shape[0]), host=np.ascontiguousarray(f.astype(np.int32)), dev={})
+    return _cached(_topology_cache, key, make)
+
+
+def _topology_on(ent, dev):
+    """What a topology entry holds on one device: `faces`, the int32 device copy, and whatever its callers keep beside it (it
+    goes when the entry is evicted)."""
+    import torch
+    if dev not in ent["dev"]:
+        ent["dev"][dev] = dict(faces=torch.as_tensor(ent["host"], device=dev))
+    return ent["dev"][dev]
+
+
 # ---- differentiable point-to-triangle term (sfx_p2m_forward / _backward, csrc/p2m.hip) -----------------------------------------
 P2M_MAX_POINTS = 1 << 26                                                # SFX_P2M_MAX_POINTS
-_P2M_CACHE_SIZE = 8
-_p2m_scratch_cache = collections.OrderedDict()  # (device, B, Np, Nv) -> the scratch tensors of calls of that size
-_p2m_topology_cache = collections.OrderedDict()  # (topology, Nv) -> the checked faces and their device copies
 
 
 def p2m_forward_scratch_bytes(B, Np, Nv):
@@ -1199,98 +1252,30 @@ def p2m_backward_scratch_bytes(B, Np, Nv):
     return 4 * B * (9 * Np + 2 * Nv + 1)
 
 
-def _p2m_scratch(which, nbytes, B, Np, Nv, dev):
-    """The scratch of sfx_p2m_forward ('fwd') or _backward ('bwd') for calls of one size on one device, kept like
-    _chamfer_scratch keeps its own."""
-    import torch
-    key = (dev, B, Np, Nv)
-    ent = _p2m_scratch_cache.get(key)
-    if ent is None:
-        ent = _p2m_scratch_cache[key] = {}
-        while len(_p2m_scratch_cache) > _P2M_CACHE_SIZE:
-            _p2m_scratch_cache.popitem(last=False)
-    else:
-        _p2m_scratch_cache.move_to_end(key)
-    if which not in ent:
-        ent[which] = torch.empty([max(1, nbytes // 4)], dtype=torch.int32, device=dev)
-    return ent[which]
-
-
-def _p2m_topology(faces, Nv):
-    """The cache entry of a topology against Nv vertices: shape, dtype and range are checked once per object (a tensor is
-    recognised by its storage and version, as in _render_topology; anything else by its contents), before where anything
-    lives.  The entry holds the int32 host copy and one device copy per device (_p2m_faces)."""
-    import hashlib
-    import torch
-    if torch.is_tensor(faces):
-        if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
-            raise ValueError("faces: shape %s, expected (F, 3) with F >= 1" % (tuple(faces.shape),))
-        if faces.dtype not in (torch.int32, torch.int64):
-            raise ValueError("faces: torch.int32 or torch.int64 is needed, got %s" % faces.dtype)
-        key = ("tensor", faces.data_ptr(), faces._version, tuple(faces.shape), tuple(faces.stride()), faces.dtype, faces.device, Nv)
-    else:
-        host = np.ascontiguousarray(np.asarray(faces))
-        if host.ndim != 2 or host.shape[1] != 3 or host.shape[0] < 1 or host.dtype.kind not in "iu":
-            raise ValueError("faces: an integer array of shape (F, 3) with F >= 1 is needed, got %s %s" % (host.dtype, host.shape))
-        key = ("host", hashlib.sha1(host.tobytes()).hexdigest(), host.shape, host.dtype.str, Nv)
-    ent = _p2m_topology_cache.get(key)
-    if ent is None:
-        host = (faces.detach().cpu().numpy() if torch.is_tensor(faces) else host).astype(np.int64)
-        if host.shape[0] > P2M_MAX_POINTS:
-            raise ValueError("faces: %d faces, at most %d" % (host.shape[0], P2M_MAX_POINTS))
-        if host.min() < 0 or host.max() >= Nv:
-            raise ValueError("faces: vertex ids %d..%d outside the %d vertices" % (host.min(), host.max(), Nv))
-        ent = dict(keep=faces, F=int(host.shape[0]), host=np.ascontiguousarray(host.astype(np.int32)), dev={})
-        _p2m_topology_cache[key] = ent
-        while len(_p2m_topology_cache) > _P2M_CACHE_SIZE:
-            _p2m_topology_cache.popitem(last=False)
-    else:
-        _p2m_topology_cache.move_to_end(key)
-    return ent
-
-
-def _p2m_faces(ent, dev):
-    import torch
-    if dev not in ent["dev"]:
-        ent["dev"][dev] = torch.as_tensor(ent["host"], device=dev)
-    return ent["dev"][dev]
-
-
 def _p2m_args(points, vertices, faces, point_mask, point_weights, face_mask, rho):
     """The checked inputs both point-to-triangle calls share: sizes, tensors as the library reads them, rho."""
-    import torch
     B, Np = _points("points", points)
     Nv = _points("vertices", vertices)[1]
-    rho = float(rho)
-    if not (np.isfinite(rho) and rho >= 0.0):
-        raise ValueError("rho: %r, a finite value >= 0 is needed" % (rho,))
+    rho = check_rho(rho)
     if Np > P2M_MAX_POINTS or Nv > P2M_MAX_POINTS:
         raise ValueError("points, vertices: %d and %d, at most %d each" % (Np, Nv, P2M_MAX_POINTS))
-    _expect_shape("vertices", vertices, (B, Nv, 3))
-    topo = _p2m_topology(faces, Nv)
+    _expect("vertices", vertices, (B, Nv, 3))
+    topo = _topology(faces, Nv)
     F = topo["F"]
-    _expect_shape("point_mask", point_mask, (B, Np))
-    if face_mask is not None:
-        if not torch.is_tensor(face_mask):
-            raise TypeError("face_mask: a torch tensor is needed, got %s" % type(face_mask).__name__)
-        if tuple(face_mask.shape) not in ((F,), (B, F)):
-            raise ValueError("face_mask: shape %s, expected %s or %s" % (tuple(face_mask.shape), (F,), (B, F)))
-        if face_mask.dtype not in (torch.bool, torch.uint8):
-            raise ValueError("face_mask: torch.bool or torch.uint8 is needed, got %s" % face_mask.dtype)
-        if face_mask.dim() == 1:
-            face_mask = face_mask[None].expand(B, F).contiguous()
-    if point_weights is not None:
-        if not torch.is_tensor(point_weights):
-            raise TypeError("point_weights: a torch tensor is needed, got %s" % type(point_weights).__name__)
-        if tuple(point_weights.shape) != (B, Np):
-            raise ValueError("point_weights: shape %s, expected %s" % (tuple(point_weights.shape), (B, Np)))
+    if F > P2M_MAX_POINTS:
+        raise ValueError("faces: %d faces, at most %d" % (F, P2M_MAX_POINTS))
+    _expect("point_mask", point_mask, (B, Np), mask=True)
+    _expect("face_mask", face_mask, (F,), (B, F), mask=True)
+    if face_mask is not None and face_mask.dim() == 1:
+        face_mask = face_mask[None].expand(B, F).contiguous()
+    _expect("point_weights", point_weights, (B, Np))
     points = A.tensor("points", points, (B, Np, 3))
     dev = points.device
     vertices = A.tensor("vertices", vertices, (B, Nv, 3), device=dev, holder="points")
     point_mask = _point_mask("point_mask", point_mask, (B, Np), dev, "points")
     face_mask = _point_mask("face_mask", face_mask, (B, F), dev, "points")
     point_weights = A.tensor("point_weights", point_weights, (B, Np), device=dev, optional=True, holder="points")
-    return B, Np, Nv, F, dev, points, vertices, _p2m_faces(topo, dev), point_mask, point_weights, face_mask, rho
+    return B, Np, Nv, F, dev, points, vertices, _topology_on(topo, dev)["faces"], point_mask, point_weights, face_mask, rho
 
 
 def point_mesh_eval(points, vertices, faces, point_mask=None, point_weights=None, face_mask=None, rho=0.0, return_dist2=True,
@@ -1320,7 +1305,7 @@ def point_mesh_eval(points, vertices, faces, point_mask=None, point_weights=None
         out["dist2"] = torch.empty([B, Np], dtype=torch.float32, device=dev)
     if B > 0:
         nbytes = p2m_forward_scratch_bytes(B, Np, Nv)
-        scratch = _p2m_scratch("fwd", nbytes, B, Np, Nv, dev)
+        scratch = _term_scratch("p2m", "fwd", nbytes, dev, B, Np, Nv)
         with torch.cuda.device(dev):
             capi.check(capi.load().sfx_p2m_forward(
                 B, Np, Nv, F, A.ptr(points), A.ptr(vertices), A.ptr(faces), A.ptr(point_mask), A.ptr(face_mask),
@@ -1345,17 +1330,14 @@ def point_mesh_backward(points, vertices, faces, fwd, grad, want=("points", "ver
         points, vertices, faces, point_mask, point_weights, None, rho)
     if not isinstance(fwd, dict) or "face" not in fwd:
         raise TypeError("fwd: the dict point_mesh_eval returned is needed (face)")
-    if not torch.is_tensor(grad):
-        raise TypeError("grad: a torch tensor is needed, got %s" % type(grad).__name__)
-    if tuple(grad.shape) != (B,):
-        raise ValueError("grad: shape %s, expected %s" % (tuple(grad.shape), (B,)))
+    _expect("grad", grad, (B,))
     face = A.tensor("fwd['face']", fwd["face"], (B, Np), device=dev, dtype=torch.int32, holder="points")
     grad = A.tensor("grad", grad, (B,), device=dev, holder="points")
     dp = torch.empty([B, Np, 3], dtype=torch.float32, device=dev) if "points" in want else None
     dv = torch.empty([B, Nv, 3], dtype=torch.float32, device=dev) if "vertices" in want else None
     if B > 0:
         nbytes = p2m_backward_scratch_bytes(B, Np, Nv)
-        scratch = _p2m_scratch("bwd", nbytes, B, Np, Nv, dev)
+        scratch = _term_scratch("p2m", "bwd", nbytes, dev, B, Np, Nv)
         with torch.cuda.device(dev):
             capi.check(capi.load().sfx_p2m_backward(
                 B, Np, Nv, F, A.ptr(points), A.ptr(vertices), A.ptr(faces), A.ptr(point_mask), A.ptr(point_weights), rho,
@@ -1374,21 +1356,14 @@ RENDER_LIGHTS = tuple(((0.5 * np.cos(phi), -0.5 * np.sin(phi), -np.cos(np.pi / 6
                       for phi in (0.0, 2.0 * np.pi / 3.0, 4.0 * np.pi / 3.0)) + (((0.0, 0.0, -1.0), 1.0),)
 RENDER_MAX_PIXELS = 1 << 26     # pixels of one launch: the visibility buffer takes 8 bytes each (512 MB)
 RENDER_WANT = ("rgba", "depth", "tri", "screen", "dropped")
-_RENDER_CACHE_SIZE = 8
-_render_cache = collections.OrderedDict()       # (topology, device) -> the topology's device arrays and the scratch of its calls
 
 
 def vertex_face_csr(faces, V):
     """The faces of every vertex of a triangle mesh, on the host: (offsets int32 [V + 1], face ids int32 [offsets[V]]) with the
     faces of vertex v at offsets[v] .. offsets[v + 1] - 1 in ascending face id, each face once (also one that names the vertex
     twice).  Deterministic: the order in which sfx_render_meshes sums a vertex's face normals."""
-    f = np.asarray(faces)
-    if f.ndim != 2 or f.shape[1] != 3 or f.shape[0] < 1 or f.dtype.kind not in "iu":
-        raise ValueError("faces: an integer array of shape (F, 3) with F >= 1 is needed, got %s %s" % (f.dtype, f.shape))
-    f = f.astype(np.int64)
     V = int(V)
-    if V < 1 or f.min() < 0 or f.max() >= V:
-        raise ValueError("faces: vertex ids %d..%d outside the %d vertices" % (f.min(), f.max(), V))
+    f = _checked_faces(faces, V)
     F = f.shape[0]
     pairs = np.unique(f.reshape(-1) * F + np.repeat(np.arange(F, dtype=np.int64), 3))      # (vertex, face), sorted, each once
     offsets = np.zeros(V + 1, np.int64)
@@ -1397,36 +1372,17 @@ def vertex_face_csr(faces, V):
 
 
 def _render_topology(faces, V, dev):
-    """The cache entry of a topology on a device: faces and CSR as device tensors, plus the scratch tensors of its calls.  A
-    tensor is recognised by its storage and version (the entry keeps it alive, so the address cannot be handed out again),
-    anything else by its contents."""
-    import hashlib
+    """What render_meshes keeps of a topology on a device, beside the faces of _topology_on: the vertex -> face lists as device
+    tensors and the scratch tensors of its calls."""
     import torch
-    if torch.is_tensor(faces):
-        if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
-            raise ValueError("faces: shape %s, expected (F, 3) with F >= 1" % (tuple(faces.shape),))
-        if faces.dtype not in (torch.int32, torch.int64):
-            raise ValueError("faces: torch.int32 or torch.int64 is needed, got %s" % faces.dtype)
-        key = ("tensor", faces.data_ptr(), faces._version, tuple(faces.shape), tuple(faces.stride()), faces.dtype, V, dev)
-    else:
-        host = np.ascontiguousarray(np.asarray(faces))
-        key = ("host", hashlib.sha1(host.tobytes()).hexdigest(), host.shape, host.dtype.str, V, dev)
-    ent = _render_cache.get(key)
-    if ent is None:
-        host = faces.detach().cpu().numpy() if torch.is_tensor(faces) else host
-        off, vf = vertex_face_csr(host, V)
-        F = int(host.shape[0])
-        vf_pad = np.zeros(3 * F, np.int32)                             # (the C ABI's [3F])
+    ent = _topology(faces, V)
+    part = _topology_on(ent, dev)
+    if "off" not in part:
+        off, vf = vertex_face_csr(ent["host"], V)
+        vf_pad = np.zeros(3 * ent["F"], np.int32)                      # (the C ABI's [3F])
         vf_pad[:vf.size] = vf
-        ent = dict(keep=faces, F=F, scratch={},
-                   faces=torch.as_tensor(capi.i32(host.astype(np.int64)), device=dev),
-                   off=torch.as_tensor(off, device=dev), vf=torch.as_tensor(vf_pad, device=dev))
-        _render_cache[key] = ent
-        while len(_render_cache) > _RENDER_CACHE_SIZE:
-            _render_cache.popitem(last=False)
-    else:
-        _render_cache.move_to_end(key)
-    return ent
+        part.update(F=ent["F"], scratch={}, off=torch.as_tensor(off, device=dev), vf=torch.as_tensor(vf_pad, device=dev))
+    return part
 
 
 def _render_scratch(ent, n, V, HW, dev):

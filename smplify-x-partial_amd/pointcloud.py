@@ -21,6 +21,40 @@ from . import engine
 REDUCTIONS = ("mean", "sum")
 
 
+def _first_derivatives_only():
+    """Called by a backward: autograd records the backward pass only under create_graph=True."""
+    if torch.is_grad_enabled():
+        raise RuntimeError("backward(create_graph=True): the differentiable loss has first derivatives only -- its gradient "
+                           "is computed by the device kernel, there is no graph of it to differentiate")
+
+
+class _PointSetLoss(nn.Module):
+    """What the point-set terms share: rho and the reduction, the inputs as the device reads them, the mean over the valid."""
+
+    def __init__(self, rho=0.0, reduction="mean"):
+        super().__init__()
+        rho = engine.check_rho(rho)
+        if reduction not in REDUCTIONS:
+            raise ValueError("reduction: one of %s, got %r" % (REDUCTIONS, reduction))
+        self.rho, self.reduction = rho, reduction
+
+    @staticmethod
+    def _float32(vertices, points, *weights):
+        """vertices and points as float32 (differentiable casts), then the weights as float32 constants (None stays None)."""
+        for name, t in (("vertices", vertices), ("points", points)):
+            if not torch.is_tensor(t):
+                raise TypeError("%s: a torch tensor is needed, got %s" % (name, type(t).__name__))
+            if not t.is_floating_point():
+                raise ValueError("%s: a floating-point tensor is needed, got %s" % (name, t.dtype))
+        return [vertices.to(torch.float32).contiguous(), points.to(torch.float32).contiguous()] + [
+            w.detach().to(torch.float32).contiguous() if torch.is_tensor(w) else w for w in weights]
+
+    def _reduced(self, loss, valid, dtype):
+        if self.reduction == "mean":
+            loss = loss / valid.clamp(min=1).to(loss.dtype)
+        return loss.to(dtype)
+
+
 class _Chamfer(torch.autograd.Function):
     """loss [B, 2] of engine.chamfer_eval; backward: engine.chamfer_backward at the indices the forward found, for the inputs
     that need a gradient.  First derivatives only: backward(create_graph=True) is refused."""
@@ -35,9 +69,7 @@ class _Chamfer(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dloss, _dvalid):
-        if torch.is_grad_enabled():       # autograd records the backward pass only under create_graph=True
-            raise RuntimeError("backward(create_graph=True): the differentiable loss has first derivatives only -- its gradient "
-                               "is computed by the device kernel, there is no graph of it to differentiate")
+        _first_derivatives_only()
         a, b, idx_ab, idx_ba = ctx.saved_tensors
         mask_a, mask_b, weight_a, weight_b, rho = ctx.consts
         want = tuple(n for n, need in zip(("a", "b"), ctx.needs_input_grad[:2]) if need)
@@ -48,7 +80,7 @@ class _Chamfer(torch.autograd.Function):
         return da, db, None, None, None, None, None
 
 
-class ChamferLoss(nn.Module):
+class ChamferLoss(_PointSetLoss):
     """forward(vertices [B, Nv, 3], points [B, Np, 3], vertex_mask=None, point_mask=None, vertex_weights=None,
     point_weights=None) -> [B, 2]: column 0 is mesh -> points (every valid vertex to its nearest valid point), column 1 is
     points -> mesh.  Per point the term is w rho(s) of the squared distance s: rho = 0 gives s itself, rho > 0 the GMoF
@@ -59,29 +91,10 @@ class ChamferLoss(nn.Module):
     whatever the inputs are: float64 tensors are converted for the call, and the loss and the gradients come back in the
     dtype of `vertices`.  Tensors must be on the GPU: there is no CPU fallback."""
 
-    def __init__(self, rho=0.0, reduction="mean"):
-        super().__init__()
-        rho = float(rho)
-        if not (rho >= 0.0 and rho != float("inf")):
-            raise ValueError("rho: %r, a finite value >= 0 is needed" % (rho,))
-        if reduction not in REDUCTIONS:
-            raise ValueError("reduction: one of %s, got %r" % (REDUCTIONS, reduction))
-        self.rho, self.reduction = rho, reduction
-
     def forward(self, vertices, points, vertex_mask=None, point_mask=None, vertex_weights=None, point_weights=None):
-        for name, t in (("vertices", vertices), ("points", points)):
-            if not torch.is_tensor(t):
-                raise TypeError("%s: a torch tensor is needed, got %s" % (name, type(t).__name__))
-            if not t.is_floating_point():
-                raise ValueError("%s: a floating-point tensor is needed, got %s" % (name, t.dtype))
-        dtype = vertices.dtype
-        a, b = vertices.to(torch.float32).contiguous(), points.to(torch.float32).contiguous()      # (differentiable casts)
-        wa = vertex_weights.detach().to(torch.float32).contiguous() if torch.is_tensor(vertex_weights) else vertex_weights
-        wb = point_weights.detach().to(torch.float32).contiguous() if torch.is_tensor(point_weights) else point_weights
+        a, b, wa, wb = self._float32(vertices, points, vertex_weights, point_weights)
         loss, valid = _Chamfer.apply(a, b, vertex_mask, point_mask, wa, wb, self.rho)
-        if self.reduction == "mean":
-            loss = loss / valid.clamp(min=1).to(loss.dtype)
-        return loss.to(dtype)
+        return self._reduced(loss, valid, vertices.dtype)
 
 
 class _PointToMesh(torch.autograd.Function):
@@ -99,9 +112,7 @@ class _PointToMesh(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dloss, _dvalid):
-        if torch.is_grad_enabled():       # autograd records the backward pass only under create_graph=True
-            raise RuntimeError("backward(create_graph=True): the differentiable loss has first derivatives only -- its gradient "
-                               "is computed by the device kernel, there is no graph of it to differentiate")
+        _first_derivatives_only()
         vertices, points, face = ctx.saved_tensors
         faces, point_mask, point_weights, rho = ctx.consts
         want = tuple(n for n, need in zip(("vertices", "points"), ctx.needs_input_grad[:2]) if need)
@@ -112,7 +123,7 @@ class _PointToMesh(torch.autograd.Function):
         return dv, dp, None, None, None, None, None
 
 
-class PointToMeshLoss(nn.Module):
+class PointToMeshLoss(_PointSetLoss):
     """PointToMeshLoss(faces, rho=0.0, reduction='mean'); forward(vertices [B, Nv, 3], points [B, Np, 3], point_mask=None,
     point_weights=None, face_mask=None) -> [B]: every valid cloud point against the nearest point of the mesh's triangles
     (`faces` [F, 3] integers, one topology for the batch).  Per point the term is w rho(s) of the squared distance s to the
@@ -125,24 +136,10 @@ class PointToMeshLoss(nn.Module):
     dtype of `vertices`.  Tensors must be on the GPU: there is no CPU fallback."""
 
     def __init__(self, faces, rho=0.0, reduction="mean"):
-        super().__init__()
-        rho = float(rho)
-        if not (rho >= 0.0 and rho != float("inf")):
-            raise ValueError("rho: %r, a finite value >= 0 is needed" % (rho,))
-        if reduction not in REDUCTIONS:
-            raise ValueError("reduction: one of %s, got %r" % (REDUCTIONS, reduction))
-        self.faces, self.rho, self.reduction = faces, rho, reduction
+        super().__init__(rho, reduction)
+        self.faces = faces
 
     def forward(self, vertices, points, point_mask=None, point_weights=None, face_mask=None):
-        for name, t in (("vertices", vertices), ("points", points)):
-            if not torch.is_tensor(t):
-                raise TypeError("%s: a torch tensor is needed, got %s" % (name, type(t).__name__))
-            if not t.is_floating_point():
-                raise ValueError("%s: a floating-point tensor is needed, got %s" % (name, t.dtype))
-        dtype = vertices.dtype
-        v, p = vertices.to(torch.float32).contiguous(), points.to(torch.float32).contiguous()      # (differentiable casts)
-        w = point_weights.detach().to(torch.float32).contiguous() if torch.is_tensor(point_weights) else point_weights
+        v, p, w = self._float32(vertices, points, point_weights)
         loss, valid = _PointToMesh.apply(v, p, self.faces, point_mask, w, face_mask, self.rho)
-        if self.reduction == "mean":
-            loss = loss / valid.clamp(min=1).to(loss.dtype)
-        return loss.to(dtype)
+        return self._reduced(loss, valid, vertices.dtype)

@@ -40,6 +40,28 @@ def lattice_clouds(Na=600, Nb=1500):
     return rng.randint(-3, 4, size=(1, Na, 3)).astype(np.float32), rng.randint(-3, 4, size=(1, Nb, 3)).astype(np.float32)
 
 
+# Rows of a 70-row destination set (one full wave and six rows of the next) and the entries each collects, per mesh: in the first
+# wave two lists past SERIAL_MAX (33: 33 segments of 1; 130: segments of 3, the last one short) beside one of exactly SERIAL_MAX,
+# shorter ones and empty rows; in the second wave one long list among rows that are empty or collect a single entry.  The two
+# meshes put their long lists on different lanes (mesh 1: the first and the last lane of the first wave, the last row of all).
+LONG_LIST_ROWS = ({5: 33, 20: 130, 41: 32, 66: 33, 64: 1, 69: 1, 7: 1, 30: 3, 50: 20, 12: 31},
+                  {0: 130, 63: 33, 17: 32, 69: 33, 65: 1, 1: 1, 40: 4, 33: 25, 8: 26})
+LONG_LIST_NROWS = 70
+
+
+@functools.lru_cache(maxsize=None)
+def long_list_clouds():
+    """(a [2, 70, 3], b [2, 285, 3], counts [2, 70]): a on a 10 cm grid with 5 mm of jitter, b 5 mm about the rows of
+    LONG_LIST_ROWS in a shuffled order, so b's nearest points in a are those rows, counts[m, r] queries each."""
+    rng = np.random.RandomState(21)
+    r = np.arange(LONG_LIST_NROWS)
+    a = (np.stack([0.1 * (r % 10), 0.1 * (r // 10), 0.0 * r], 1) + 0.005 * rng.normal(size=(2, LONG_LIST_NROWS, 3))).astype(np.float32)
+    counts = np.array([[rows.get(int(k), 0) for k in r] for rows in LONG_LIST_ROWS])
+    pick = np.stack([rng.permutation(np.repeat(r, c)) for c in counts])
+    b = (np.take_along_axis(a, pick[..., None].repeat(3, -1), 1) + 0.005 * rng.normal(size=pick.shape + (3,))).astype(np.float32)
+    return a, b, counts
+
+
 def masks_and_weights(B, Na, Nb, seed=3):
     rng = np.random.RandomState(seed + Na + Nb)
     ma, mb = rng.rand(B, Na) > 0.3, rng.rand(B, Nb) > 0.3

@@ -228,6 +228,32 @@ def soup_case(B, Np, F, seed=0):
     return p, v, faces
 
 
+@functools.lru_cache(maxsize=None)
+def long_list_case():
+    """(p [2, 130, 3], v [2, 70, 3], faces [F, 3], face [2, 130], counts [2, 70]): the vertex rows of chamfer_common
+    .LONG_LIST_ROWS as corner entries.  Every point of a mesh is given a face that names the mesh's 130-entry vertex; the two
+    other corners of the 130 faces take the other rows with their counts, and rows 22 .. 27 of the first wave take what is left
+    (17 or 18 each: short lists).  `face` is handed to the backward as the forward's result would be: the backward forms each
+    point's term against the face it is given."""
+    rng = np.random.RandomState(23)
+    Nv, Np = CC.LONG_LIST_NROWS, 130
+    tri, counts = [], np.zeros((2, Nv), int)
+    for m, rows in enumerate(CC.LONG_LIST_ROWS):
+        hub = [r for r, c in rows.items() if c == Np][0]
+        rest = {r: c for r, c in rows.items() if r != hub}
+        left = 2 * Np - sum(rest.values())
+        rest.update({22 + k: left // 6 + (k < left % 6) for k in range(6)})
+        slots = np.repeat(sorted(rest), [rest[r] for r in sorted(rest)])    # (no row holds 130 of them: a pair is two vertices)
+        tri.append(np.stack([np.roll((hub, slots[i], slots[i + Np]), i % 3) for i in range(Np)]))
+        counts[m] = np.bincount(tri[m].reshape(-1), minlength=Nv)
+    faces, face = np.unique(np.concatenate(tri), axis=0, return_inverse=True)
+    face = face.reshape(2, Np).astype(np.int32)
+    v = (0.1 * rng.normal(size=(2, Nv, 3))).astype(np.float32)
+    centre = np.stack([v[m][faces[face[m]]].mean(1) for m in range(2)])
+    p = (centre + 0.02 * rng.normal(size=(2, Np, 3))).astype(np.float32)
+    return p, v, faces.astype(np.int32), face, counts
+
+
 def masks_and_weights(B, Np, F, seed=3):
     rng = np.random.RandomState(seed + Np + F)
     mp, mf = rng.rand(B, Np) > 0.3, rng.rand(B, F) > 0.3

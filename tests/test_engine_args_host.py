@@ -267,3 +267,25 @@ def test_ign_part_pairs_parser():
     for nothing in ([], None, ()):
         e = _args.ign_pairs(nothing)
         assert e.dtype == np.int32 and e.shape == (0, 2)
+
+
+# ---------------------------------------------------------------- 6. the bounded cache of the device calls' entries
+def test_bounded_cache_evicts_the_oldest_and_a_hit_makes_an_entry_recent():
+    import collections
+    from smplifyx_amd import engine
+    cache, made = collections.OrderedDict(), []
+
+    def get(key):
+        return engine._cached(cache, key, lambda: made.append(key) or [key], size=3)
+    ents = {k: get(k) for k in "abcd"}
+    assert list(cache) == ["b", "c", "d"] and "a" not in cache               # four keys, size 3: the first is gone
+    assert get("b") is ents["b"] and list(cache) == ["c", "d", "b"]          # a hit marks the entry recent ...
+    get("e")
+    assert list(cache) == ["d", "b", "e"]                                    # ... so the next insert evicts another
+    assert get("d") is ents["d"] and get("b") is ents["b"]
+    assert made == ["a", "b", "c", "d", "e"]                                 # made once per resident key
+    assert get("a") is not ents["a"] and made[-1] == "a"                     # an evicted key is made again
+    with pytest.raises(KeyError):                                            # a make() that raises leaves no entry
+        engine._cached(cache, "z", lambda: {}["z"], size=3)
+    assert "z" not in cache and len(cache) == 3
+    assert engine._cached.__defaults__ == (8,)                               # the size the device calls run with

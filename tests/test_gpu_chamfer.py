@@ -150,7 +150,8 @@ def test_loss_and_gradients_against_float64(gpu, Na, Nb, robust, with_masks_and_
 @pytest.mark.parametrize("rho", [0.0, 0.02])
 def test_gradient_rows_in_the_devices_own_order(gpu, rho):
     """Every row of da and db, bit for bit: the gather term, then the row's list in ascending query index (chamfer_common
-    .rows_exact restates csrc/chamfer_math.h), with masks and weights."""
+    .rows_exact restates csrc/chamfer_math.h), with masks and weights.  Then the two meshes of chamfer_common.long_list_clouds: a
+    wave that holds two long lists beside short lists and empty rows, and a partly filled wave with one more (LONG_LIST_ROWS)."""
     a, b = CC.body_clouds(1, 513, 1025)
     ma, mb, wa, wb = CC.masks_and_weights(1, 513, 1025)
     g = np.float32([[0.75, 1.25]])
@@ -161,6 +162,15 @@ def test_gradient_rows_in_the_devices_own_order(gpu, rho):
     only_a = device_grad(a, b, out, g, ma, mb, wa, wb, rho, want=("a",))
     only_b = device_grad(a, b, out, g, ma, mb, wa, wb, rho, want=("b",))
     assert only_a[1] is None and only_b[0] is None and same_bits(only_a[0], da) and same_bits(only_b[1], db)
+    a, b, counts = CC.long_list_clouds()
+    wa, wb = CC.masks_and_weights(2, a.shape[1], b.shape[1])[2:]
+    g = np.float32([[0.75, 1.25], [1.5, 0.5]])
+    out = device_eval(a, b, None, None, wa, wb, rho)
+    da, db = device_grad(a, b, out, g, None, None, wa, wb, rho)
+    for m in range(2):
+        assert np.bincount(out["idx_ba"][m], minlength=a.shape[1]).tolist() == counts[m].tolist()
+        assert same_bits(da[m], CC.rows_exact(a[m], b[m], out["idx_ab"][m], out["idx_ba"][m], wa[m], wb[m], g[m, 0], g[m, 1], rho))
+        assert same_bits(db[m], CC.rows_exact(b[m], a[m], out["idx_ba"][m], out["idx_ab"][m], wb[m], wa[m], g[m, 1], g[m, 0], rho))
 
 
 # ---- 3. masks and weights -------------------------------------------------------------------------------------------------------

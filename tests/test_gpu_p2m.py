@@ -148,7 +148,8 @@ def test_loss_and_gradients_against_float64(gpu, Np, F, robust, with_masks_and_w
 @pytest.mark.parametrize("rho", [0.0, 0.01])
 def test_gradient_rows_in_the_devices_own_order(gpu, rho):
     """Every row of dp and dv, bit for bit (p2m_common.rows_exact restates csrc/p2m_math.h over csrc/chamfer_math.h), with a
-    point mask, a face mask and weights."""
+    point mask, a face mask and weights.  Then the two meshes of p2m_common.long_list_case: a wave of vertex rows that holds two
+    long lists beside short lists and empty rows, and a partly filled wave with one more (chamfer_common.LONG_LIST_ROWS)."""
     Np, F = 513, 257
     p, v, faces = PC.grid_case(1, Np, F)
     mp, mf, w = PC.masks_and_weights(1, Np, F)
@@ -161,6 +162,14 @@ def test_gradient_rows_in_the_devices_own_order(gpu, rho):
     only_p = device_grad(p, v, faces, out, g, mp, w, rho, want=("points",))
     only_v = device_grad(p, v, faces, out, g, mp, w, rho, want=("vertices",))
     assert only_p[1] is None and only_v[0] is None and same_bits(only_p[0], dp) and same_bits(only_v[1], dv)
+    p, v, faces, face, counts = PC.long_list_case()
+    w = PC.masks_and_weights(2, p.shape[1], len(faces))[2]
+    g = np.float32([0.75, 1.5])
+    dp, dv = device_grad(p, v, faces, dict(face=face), g, None, w, rho)
+    for m in range(2):
+        assert all(counts[m][r] == c for r, c in CC.LONG_LIST_ROWS[m].items())
+        rp, rv = PC.rows_exact(p[m], v[m], faces, face[m], None, w[m], g[m], rho)
+        assert same_bits(dp[m], rp) and same_bits(dv[m], rv)
 
 
 def test_a_vertex_that_collects_more_than_2048_entries(gpu):

@@ -127,11 +127,11 @@ def test_point_mesh_eval_refuses_before_any_launch():
         with pytest.raises(ValueError, match="rho"):
             engine.point_mesh_eval(p, v, FACES, rho=rho)
     # a faces object is checked once: the second call finds its entry
-    n = len(engine._p2m_topology_cache)
+    n = len(engine._topology_cache)
     for _ in range(2):
         with pytest.raises(ValueError, match="no CPU fallback"):
             engine.point_mesh_eval(p, v, FACES)
-    assert len(engine._p2m_topology_cache) == n
+    assert len(engine._topology_cache) == n
 
 
 def test_point_mesh_backward_refuses_before_any_launch():
