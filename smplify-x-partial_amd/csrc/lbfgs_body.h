@@ -9,8 +9,10 @@
 // The specification is oracle/lbfgs_machine.py (same transitions, same rounding rule).
 //
 // This file: the tick (lbfgs_tick_wave0), its entry for a workgroup (lbfgs_tick_body) and the workgroup-wide write-back
-// (tick_write_back).  The dual-typed scalars every branch is decided on, the cubic step and the scalar state are
-// lbfgs_scalar.h; the history and the blocked two-loop recursion are lbfgs_two_loop.h.  Compile with -ffp-contract=off (see there).
+// (tick_write_back).  The tick is the phase / action skeleton, the vector work (Lane3 in registers, rows in LDS) and the fit's
+// stage sequencing; every transition decided on scalars alone -- the line search's bracket and zoom phases, the LBFGS.step
+// prologue and end-of-iteration tests, run_fitting's bookkeeping -- is lbfgs_scalar.h, with the dual-typed scalars, the cubic
+// step and the scalar state; the history and the blocked two-loop recursion are lbfgs_two_loop.h.  Compile with -ffp-contract=off (see there).
 #pragma once
 #include "lbfgs_scalar.h"
 #include "lbfgs_two_loop.h"
@@ -137,15 +139,6 @@ __device__ __forceinline__ void lbfgs_tick_wave0(const DevModel& M, const BatchD
         LB_SYNC();
         for (int e = 0; e < NE3; ++e) { const int i = 3 * lane + e; if (i < N) Xt[idx3[e]] = xt.v[e]; }
     };
-#define armijo_fail(f_new, t) sc_gt((f_new), sc_add(s.ls_f0, sc_mul(sc_mul(P(1e-4), (t)), s.ls_gtd0)))
-#define curv_ok(gtd_new) sc_le(sc_abs(gtd_new), sc_mul(P(-0.9), s.ls_gtd0))
-    // bracket set-up: gradient slot 0 = G0 (a Lane3 value), slot 1 = the incoming gradient
-#define start_zoom(b0, b1, f0, f1, G0, gd0, gd1, done) do {                                              \
-        s.br0 = (b0); s.br1 = (b1); s.bf0 = (f0); s.bf1 = (f1); s.bgtd0 = (gd0); s.bgtd1 = (gd1);        \
-        st3(VEC(VEC_BG0), (G0), lane, N); st3(VEC(VEC_BG1), g_in, lane, N);                               \
-        s.ls_done = (done) ? 1 : 0; s.insuf = 0;                                                         \
-        if (sc_le(s.bf0, s.bf1)) { s.low = 0; s.high = 1; } else { s.low = 1; s.high = 0; } } while (0)
-
     // optimiser trace (sfx_batch_trace): one record per finished line search / LBFGS.step / stage
 #define TRACE(ty, a_, b_, c_) do { if (D.trace && D.trace_n && lane == 0) { const int n_ = D.trace_n[b];                         \
         if (n_ < D.trace_cap) D.trace[(size_t)b * D.trace_cap + n_] = make_float4((float)(ty), (float)(a_), (float)(b_), (float)(c_)); \
@@ -162,57 +155,26 @@ __device__ __forceinline__ void lbfgs_tick_wave0(const DevModel& M, const BatchD
         s.loss = f_in;
         act = A_ENTRY;
     } else if (s.phase == PH_BRACKET) {
-        s.ls_evals += 1;
-        const Sc t = s.t;
         const Lane3 d = ld3(VEC(VEC_D), lane, N);
-        const Sc gtd_new = T(dot3(g_in, d));
-        if (s.ls_iter == max_ls) {
-            start_zoom(P(0.0), t, s.ls_f0, f_in, ld3(VEC(VEC_LSG0), lane, N), s.ls_gtd0, gtd_new, false);
-            act = A_ZOOM_NEXT;
-        } else if (armijo_fail(f_in, t) || (s.ls_iter > 1 && sc_ge(f_in, s.f_prev))) {
-            start_zoom(s.t_prev, t, s.f_prev, f_in, ld3(VEC(VEC_GPREV), lane, N), s.gtd_prev, gtd_new, false);
-            act = A_ZOOM_NEXT;
-        } else if (curv_ok(gtd_new)) {
-            // single-point bracket: the point itself is accepted
-            start_zoom(t, t, f_in, f_in, g_in, gtd_new, gtd_new, true);
-            s.low = 0; s.high = 1;
-            act = A_ZOOM_NEXT;
-        } else if (sc_ge(gtd_new, P(0.0))) {
-            start_zoom(s.t_prev, t, s.f_prev, f_in, ld3(VEC(VEC_GPREV), lane, N), s.gtd_prev, gtd_new, false);
-            act = A_ZOOM_NEXT;
-        } else {
-            const Sc lo = sc_add(t, sc_mul(P(0.01), sc_sub(t, s.t_prev)));
-            const Sc hi = sc_mul(t, P(10.0));
-            const Sc t_next = cubic_interpolate(s.t_prev, s.f_prev, s.gtd_prev, t, f_in, gtd_new, true, lo, hi);
-            s.t_prev = t; s.f_prev = f_in; s.gtd_prev = gtd_new;
+        const int g0 = ls_bracket_eval(s, f_in, T(dot3(g_in, d)), max_ls);
+        if (g0 == LS_EXTEND) {
             st3(VEC(VEC_GPREV), g_in, lane, N);
-            s.t = t_next;
-            s.ls_iter += 1;
-            write_trial(t_next);
+            write_trial(s.t);
             act = A_NONE;
+        } else {       // a bracket: gradient slot 0 = the one named, slot 1 = the incoming gradient
+            const Lane3 G0 = g0 == LS_G0_GIN ? g_in : ld3(VEC(g0 == LS_G0_LSG0 ? VEC_LSG0 : VEC_GPREV), lane, N);
+            st3(VEC(VEC_BG0), G0, lane, N); st3(VEC(VEC_BG1), g_in, lane, N);
+            act = A_ZOOM_NEXT;
         }
     } else {   // PH_ZOOM
-        s.ls_evals += 1; s.ls_iter += 1;
-        const Sc t = s.t;
         const Lane3 d = ld3(VEC(VEC_D), lane, N);
-        const Sc gtd_new = T(dot3(g_in, d));
-        const int lo = s.low, hi = s.high;
-        if (armijo_fail(f_in, t) || sc_ge(f_in, (lo ? s.bf1 : s.bf0))) {
-            { const Sc v_ = t; if (hi) s.br1 = v_; else s.br0 = v_; } { const Sc v_ = f_in; if (hi) s.bf1 = v_; else s.bf0 = v_; } { const Sc v_ = gtd_new; if (hi) s.bgtd1 = v_; else s.bgtd0 = v_; }
-            st3(VEC(hi ? VEC_BG1 : VEC_BG0), g_in, lane, N);
-            if (sc_le(s.bf0, s.bf1)) { s.low = 0; s.high = 1; } else { s.low = 1; s.high = 0; }
-        } else {
-            if (curv_ok(gtd_new)) s.ls_done = 1;
-            else if (sc_ge(sc_mul(gtd_new, sc_sub((hi ? s.br1 : s.br0), (lo ? s.br1 : s.br0))), P(0.0))) {
-                { const Sc v_ = (lo ? s.br1 : s.br0); if (hi) s.br1 = v_; else s.br0 = v_; } { const Sc v_ = (lo ? s.bf1 : s.bf0); if (hi) s.bf1 = v_; else s.bf0 = v_; } { const Sc v_ = (lo ? s.bgtd1 : s.bgtd0); if (hi) s.bgtd1 = v_; else s.bgtd0 = v_; }
-                const Lane3 tmp = ld3(VEC(lo ? VEC_BG1 : VEC_BG0), lane, N);
-                st3(VEC(hi ? VEC_BG1 : VEC_BG0), tmp, lane, N);
-            }
-            { const Sc v_ = t; if (lo) s.br1 = v_; else s.br0 = v_; } { const Sc v_ = f_in; if (lo) s.bf1 = v_; else s.bf0 = v_; } { const Sc v_ = gtd_new; if (lo) s.bgtd1 = v_; else s.bgtd0 = v_; }
-            st3(VEC(lo ? VEC_BG1 : VEC_BG0), g_in, lane, N);
+        const ZoomMove m = ls_zoom_eval(s, f_in, T(dot3(g_in, d)), tol_change);
+        if (m.copy_first) {
+            const Lane3 tmp = ld3(VEC(m.end ? VEC_BG1 : VEC_BG0), lane, N);
+            st3(VEC(m.end ? VEC_BG0 : VEC_BG1), tmp, lane, N);
         }
-        if (sc_lt(sc_mul(sc_abs(sc_sub(s.br1, s.br0)), s.d_norm), P(tol_change))) act = A_FINISH_LS;
-        else act = A_ZOOM_NEXT;
+        st3(VEC(m.end ? VEC_BG1 : VEC_BG0), g_in, lane, N);
+        act = m.collapsed ? A_FINISH_LS : A_ZOOM_NEXT;
     }
 
     TMARK(2);
@@ -221,18 +183,12 @@ __device__ __forceinline__ void lbfgs_tick_wave0(const DevModel& M, const BatchD
     while (act != A_NONE && guard++ < 4096) {
         switch (act) {
         case A_ENTRY: {          // LBFGS.step prologue (lbfgs_ls.py:279-290); (loss, G) hold f, g at x
-            s.cache_valid = 1;
-            s.func_evals += 1;
-            s.orig_loss = s.loss;
-            s.cur_evals = 1; s.n_iter = 0;
             const Lane3 g = ld3(VEC(VEC_G), lane, N);
-            if (sc_le(T(absmax3(g, lane, N)), P(tol_grad))) act = A_END_STEP;
-            else act = A_ITER_HEAD;
+            act = step_entry(s, absmax3(g, lane, N), tol_grad);
             break;
         }
         case A_ITER_HEAD: {      // direction + first trial point (lbfgs_ls.py:304-397)
-            if (!(s.n_iter < max_iter)) { act = A_END_STEP; break; }
-            s.n_iter += 1; s.n_iter_total += 1;
+            if (!step_iter_begin(s, max_iter)) { act = A_END_STEP; break; }
             const Lane3 g = ld3(VEC(VEC_G), lane, N);
             Lane3 d;
             if (s.n_iter_total == 1) {
@@ -269,74 +225,45 @@ __device__ __forceinline__ void lbfgs_tick_wave0(const DevModel& M, const BatchD
             }
             st3(VEC(VEC_D), d, lane, N);
             st3(VEC(VEC_PREVG), g, lane, N);
-            s.prev_loss = s.loss;
-            Sc t;
+            float asum = 0.f;
             if (s.n_iter_total == 1) {
-                float asum = 0.f;
                 for (int e = 0; e < NE3; ++e) asum = asum + fabsf(g.v[e]);
                 asum = wsum(asum);
-                t = sc_mul(sc_pmin(P(1.0), sc_div(P(1.0), T(asum))), P((double)C.lr));
-            } else t = P((double)C.lr);
-            s.t = t;
+            }
+            step_first_length(s, asum, C.lr);
             const Sc gtd = T(dot3(g, d));
-            if (sc_gt(gtd, P(-tol_change))) { act = A_END_STEP; break; }
+            if (!step_descends(gtd, tol_change)) { act = A_END_STEP; break; }
             // strong-Wolfe set-up (lbfgs_ls.py:39-52)
             const Lane3 xi = gather_x();
             st3(VEC(VEC_XINIT), xi, lane, N);
             st3(VEC(VEC_LSG0), g, lane, N);
             st3(VEC(VEC_GPREV), g, lane, N);
-            s.ls_f0 = s.loss; s.ls_gtd0 = gtd;
-            s.d_norm = T(absmax3(d, lane, N));
-            s.ls_evals = 0; s.ls_iter = 0;
-            s.t_prev = P(0.0); s.f_prev = s.loss; s.gtd_prev = gtd;
-            s.phase = PH_BRACKET;
+            ls_setup(s, gtd, absmax3(d, lane, N));
             LB_SYNC();
-            write_trial(t);
+            write_trial(s.t);
             act = A_NONE;
             break;
         }
         case A_ZOOM_NEXT: {      // next zoom trial (lbfgs_ls.py:108-131)
-            if (s.ls_done || !(s.ls_iter < max_iter)) { act = A_FINISH_LS; break; }
-            Sc t = cubic_interpolate(s.br0, s.bf0, s.bgtd0, s.br1, s.bf1, s.bgtd1, false, P(0), P(0));
-            const Sc bmax = sc_gt(s.br1, s.br0) ? s.br1 : s.br0;
-            const Sc bmin = sc_lt(s.br1, s.br0) ? s.br1 : s.br0;
-            const Sc eps = sc_mul(P(0.1), sc_sub(bmax, bmin));
-            if (sc_lt(sc_pmin(sc_sub(bmax, t), sc_sub(t, bmin)), eps)) {
-                if (s.insuf || sc_ge(t, bmax) || sc_le(t, bmin)) {
-                    if (sc_lt(sc_abs(sc_sub(t, bmax)), sc_abs(sc_sub(t, bmin)))) t = sc_sub(bmax, eps);
-                    else t = sc_add(bmin, eps);
-                    s.insuf = 0;
-                } else s.insuf = 1;
-            } else s.insuf = 0;
-            s.t = t;
-            s.phase = PH_ZOOM;
-            write_trial(t);
+            if (!ls_zoom_trial(s, max_iter)) { act = A_FINISH_LS; break; }
+            write_trial(s.t);
             act = A_NONE;
             break;
         }
         case A_FINISH_LS: {      // accept the lowest bracket end (lbfgs_ls.py:163-167,398-434)
-            const int lo = s.low;
-            const Sc t = (lo ? s.br1 : s.br0);
-            s.loss = (lo ? s.bf1 : s.bf0); s.t = t;
-            const Lane3 g = ld3(VEC(lo ? VEC_BG1 : VEC_BG0), lane, N);
+            const Sc t = ls_accept(s);
+            const Lane3 g = ld3(VEC(s.low ? VEC_BG1 : VEC_BG0), lane, N);
             st3(VEC(VEC_G), g, lane, N);
             const Lane3 xi = ld3(VEC(VEC_XINIT), lane, N), d = ld3(VEC(VEC_D), lane, N);
             const Lane3 xn = axpy3(xi, (float)t.v, d);
             for (int e = 0; e < NE3; ++e) { const int i = 3 * lane + e; if (i < N) X[idx3[e]] = xn.v[e]; }
-            s.cache_valid = 1;
-            const bool opt_cond = sc_le(T(absmax3(g, lane, N)), P(tol_grad));
-            s.cur_evals += s.ls_evals; s.func_evals += s.ls_evals;
+            const float g_inf = absmax3(g, lane, N);
             TRACE(0, t.v, s.loss.v, s.ls_evals);
-            if (s.n_iter == max_iter) { act = A_END_STEP; break; }
-            if (s.cur_evals >= max_eval) { act = A_END_STEP; break; }
-            if (opt_cond) { act = A_END_STEP; break; }
             Lane3 stp;
             const float tf = (float)t.v;
             for (int e = 0; e < NE3; ++e) stp.v[e] = d.v[e] * tf;
-            if (sc_le(T(absmax3(stp, lane, N)), P(tol_change))) { act = A_END_STEP; break; }
-            if (sc_lt(sc_abs(sc_sub(s.loss, s.prev_loss)), P(tol_change))) { act = A_END_STEP; break; }
-            LB_SYNC();
-            act = A_ITER_HEAD;
+            act = step_iter_end(s, g_inf, absmax3(stp, lane, N), max_iter, max_eval, tol_grad, tol_change);
+            if (act == A_ITER_HEAD) LB_SYNC();
             break;
         }
         case A_END_STEP: {       // run_fitting bookkeeping (fitting.py:175-217)
@@ -352,14 +279,8 @@ __device__ __forceinline__ void lbfgs_tick_wave0(const DevModel& M, const BatchD
                 act = A_NONE;
                 break;
             }
-            bool stop = false;
-            if (isnan(loss) || isinf(loss)) stop = true;
-            if (!stop && s.outer > 0 && s.has_prev_outer && C.ftol > 0.0) {
-                const double pv = s.prev_loss_outer;
-                const double den = fmax(fmax(fabs(pv), fabs(loss)), 1.0);
-                if ((pv - loss) / den <= C.ftol) stop = true;
-            }
-            if (!stop) {
+            bool stop = fit_stops_on_loss(s, loss, C.ftol);
+            if (!stop) {         // the gtol test (fitting.py:191) on the last gradient the closure returned
                 const Lane3 gl = glast_cached ? ld3(VEC(VEC_G), lane, N) : g_in;
                 bool all_small = true;
                 for (int gi = 0; gi < vl.ngroups; ++gi) {
@@ -374,21 +295,9 @@ __device__ __forceinline__ void lbfgs_tick_wave0(const DevModel& M, const BatchD
                 }
                 if (all_small) stop = true;
             }
-            if (!stop) {
-                s.prev_loss_outer = loss; s.has_prev_outer = 1;
-                s.outer += 1;
-                if (s.outer >= C.maxiters) stop = true;
-            }
-            if (stop) { act = A_FINISH_STAGE; break; }
-            s.phase = PH_ENTRY;
-            if (C.reuse && s.cache_valid) {
-                glast_cached = 1;
-                s.ref_evals += 1;
-                act = A_ENTRY;          // (loss, G) already hold f, g at the unchanged x
-            } else {
-                for (int i = lane; i < SFX_NPAR_MAX; i += 64) Xt[i] = X[i];
-                act = A_NONE;
-            }
+            act = fit_next_step(s, stop, loss, C.maxiters, C.reuse);
+            if (act == A_ENTRY) glast_cached = 1;          // (loss, G) already hold f, g at the unchanged x
+            else if (act == A_NONE) { for (int i = lane; i < SFX_NPAR_MAX; i += 64) Xt[i] = X[i]; }
             break;
         }
         case A_FINISH_STAGE: {

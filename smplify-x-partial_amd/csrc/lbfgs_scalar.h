@@ -1,5 +1,7 @@
-// lbfgs_scalar.h -- the scalar layer of the on-device optimiser (lbfgs_body.h): the dual-typed arithmetic, the cubic step
-// of the line search, the side view's flipped orientation and the per-frame scalar state.
+// lbfgs_scalar.h -- the scalar layer of the on-device optimisers (lbfgs_body.h, lbfgs_wide.h): the dual-typed arithmetic, the
+// cubic step of the line search, the side view's flipped orientation, the per-frame scalar state, and every transition of the
+// state machine that is decided on scalars alone (the strong-Wolfe bracket and zoom phases, the LBFGS.step prologue and
+// end-of-iteration tests, run_fitting's bookkeeping) -- the two ticks call these and keep the vector work between them.
 //
 // The reference mixes Python floats (double) and 0-d float32 tensors; PyTorch computes in
 // float32 whenever a tensor takes part.  `Sc` carries that distinction so that every
@@ -118,6 +120,165 @@ __host__ __device__ __forceinline__ OptScal fresh_state() {
     s.br0 = s.br1 = s.bf0 = s.bf1 = s.bgtd0 = s.bgtd1 = P(0.0);
     s.prev_loss_outer = 0.0;
     return s;
+}
+
+// ---- The transitions of the state machine that read and write scalars only, stated once for both ticks (lbfgs_body.h: a frame's
+// vectors in LDS, one wavefront; lbfgs_wide.h: rows in memory behind a vector layer).  A tick computes the reductions a
+// transition wants, calls it, and does the vector work the returned value names.  Specification: oracle/lbfgs_machine.py;
+// tests/lbfgs_scalar_check.cpp runs the line-search transitions against it on seeded states.
+
+// c ? a : b on values (a ternary on members of the state would select between their addresses and keep the state in memory)
+__host__ __device__ __forceinline__ Sc sc_pick(int c, const Sc a, const Sc b) { Sc r; r.v = c ? a.v : b.v; r.t = c ? a.t : b.t; return r; }
+
+// the strong-Wolfe conditions at step t (lbfgs_ls.py:58, :73 and :134, :147)
+__host__ __device__ __forceinline__ bool ls_armijo_fail(const OptScal& s, Sc f_new, Sc t) { return sc_gt(f_new, sc_add(s.ls_f0, sc_mul(sc_mul(P(1e-4), t), s.ls_gtd0))); }
+__host__ __device__ __forceinline__ bool ls_curv_ok(const OptScal& s, Sc gtd_new) { return sc_le(sc_abs(gtd_new), sc_mul(P(-0.9), s.ls_gtd0)); }
+__host__ __device__ __forceinline__ void ls_order_ends(OptScal& s) { const int swap = sc_le(s.bf0, s.bf1) ? 0 : 1; s.low = swap; s.high = 1 - swap; }
+__host__ __device__ __forceinline__ void ls_set_bracket(OptScal& s, Sc b0, Sc b1, Sc f0, Sc f1, Sc gd0, Sc gd1, int done) {
+    s.br0 = b0; s.br1 = b1; s.bf0 = f0; s.bf1 = f1; s.bgtd0 = gd0; s.bgtd1 = gd1;
+    s.ls_done = done; s.insuf = 0;
+    ls_order_ends(s);
+}
+__host__ __device__ __forceinline__ void ls_set_end(OptScal& s, int end, Sc b, Sc f, Sc gd) {
+    if (end) { s.br1 = b; s.bf1 = f; s.bgtd1 = gd; } else { s.br0 = b; s.bf0 = f; s.bgtd0 = gd; }
+}
+
+// Bracket phase, one evaluation (f_in, gtd_new = g_in . d) at s.t (lbfgs_ls.py:54-100).  LS_EXTEND: the search goes on at the new
+// s.t and the incoming gradient becomes the previous one.  Otherwise a bracket is set up -- scalars, order of the ends, ls_done,
+// insuf -- whose gradient slot 1 is the incoming gradient and whose slot 0 is the one named; the zoom trial comes next.
+enum { LS_EXTEND = 0, LS_G0_LSG0, LS_G0_GPREV, LS_G0_GIN };
+__host__ __device__ __forceinline__ int ls_bracket_eval(OptScal& s, Sc f_in, Sc gtd_new, int max_ls) {
+    s.ls_evals += 1;
+    const Sc t = s.t;
+    // loop budget exhausted: no tests on the last point, bracket = [0, t]
+    if (s.ls_iter == max_ls) { ls_set_bracket(s, P(0.0), t, s.ls_f0, f_in, s.ls_gtd0, gtd_new, 0); return LS_G0_LSG0; }
+    if (ls_armijo_fail(s, f_in, t) || (s.ls_iter > 1 && sc_ge(f_in, s.f_prev))) {
+        ls_set_bracket(s, s.t_prev, t, s.f_prev, f_in, s.gtd_prev, gtd_new, 0); return LS_G0_GPREV; }
+    // single-point bracket: the point itself is accepted
+    if (ls_curv_ok(s, gtd_new)) { ls_set_bracket(s, t, t, f_in, f_in, gtd_new, gtd_new, 1); s.low = 0; s.high = 1; return LS_G0_GIN; }
+    if (sc_ge(gtd_new, P(0.0))) { ls_set_bracket(s, s.t_prev, t, s.f_prev, f_in, s.gtd_prev, gtd_new, 0); return LS_G0_GPREV; }
+    const Sc lo = sc_add(t, sc_mul(P(0.01), sc_sub(t, s.t_prev)));
+    const Sc hi = sc_mul(t, P(10.0));
+    const Sc t_next = cubic_interpolate(s.t_prev, s.f_prev, s.gtd_prev, t, f_in, gtd_new, true, lo, hi);
+    s.t_prev = t; s.f_prev = f_in; s.gtd_prev = gtd_new;
+    s.t = t_next; s.ls_iter += 1;
+    return LS_EXTEND;
+}
+
+// Zoom phase, one evaluation at s.t (lbfgs_ls.py:132-161): the bracket's scalars and the order of its ends.  For the gradients:
+// `end` receives the incoming one, after the other end has taken a copy of end's old gradient where copy_first is set.
+// collapsed: the bracket is narrower than tol_change, the lower end is accepted; otherwise the zoom trial comes next.
+struct ZoomMove { int end, copy_first, collapsed; };
+__host__ __device__ __forceinline__ ZoomMove ls_zoom_eval(OptScal& s, Sc f_in, Sc gtd_new, double tol_change) {
+    s.ls_evals += 1; s.ls_iter += 1;
+    const Sc t = s.t;
+    const int lo = s.low, hi = s.high;
+    ZoomMove m; m.copy_first = 0;
+    if (ls_armijo_fail(s, f_in, t) || sc_ge(f_in, sc_pick(lo, s.bf1, s.bf0))) {
+        ls_set_end(s, hi, t, f_in, gtd_new); m.end = hi;
+        ls_order_ends(s);
+    } else {
+        if (ls_curv_ok(s, gtd_new)) s.ls_done = 1;
+        else if (sc_ge(sc_mul(gtd_new, sc_sub(sc_pick(hi, s.br1, s.br0), sc_pick(lo, s.br1, s.br0))), P(0.0))) {
+            ls_set_end(s, hi, sc_pick(lo, s.br1, s.br0), sc_pick(lo, s.bf1, s.bf0), sc_pick(lo, s.bgtd1, s.bgtd0));
+            m.copy_first = 1;
+        }
+        ls_set_end(s, lo, t, f_in, gtd_new); m.end = lo;
+    }
+    m.collapsed = sc_lt(sc_mul(sc_abs(sc_sub(s.br1, s.br0)), s.d_norm), P(tol_change)) ? 1 : 0;
+    return m;
+}
+
+// The next zoom trial (lbfgs_ls.py:108-131).  false: the search is over (done, or out of iterations) and the lower end is
+// accepted; true: s.t is the point to evaluate.
+__host__ __device__ __forceinline__ bool ls_zoom_trial(OptScal& s, int max_iter) {
+    if (s.ls_done || !(s.ls_iter < max_iter)) return false;
+    Sc t = cubic_interpolate(s.br0, s.bf0, s.bgtd0, s.br1, s.bf1, s.bgtd1, false, P(0), P(0));
+    const Sc bmax = sc_pick(sc_gt(s.br1, s.br0), s.br1, s.br0);      // Python max(list), min(list)
+    const Sc bmin = sc_pick(sc_lt(s.br1, s.br0), s.br1, s.br0);
+    const Sc eps = sc_mul(P(0.1), sc_sub(bmax, bmin));
+    if (sc_lt(sc_pmin(sc_sub(bmax, t), sc_sub(t, bmin)), eps)) {
+        if (s.insuf || sc_ge(t, bmax) || sc_le(t, bmin)) {
+            if (sc_lt(sc_abs(sc_sub(t, bmax)), sc_abs(sc_sub(t, bmin)))) t = sc_sub(bmax, eps);
+            else t = sc_add(bmin, eps);
+            s.insuf = 0;
+        } else s.insuf = 1;
+    } else s.insuf = 0;
+    s.t = t; s.phase = PH_ZOOM;
+    return true;
+}
+
+// LBFGS.step prologue (lbfgs_ls.py:279-290); s.loss holds f at x, g_inf = |g|inf there.  Returns the next action.
+__host__ __device__ __forceinline__ int step_entry(OptScal& s, float g_inf, double tol_grad) {
+    s.cache_valid = 1; s.func_evals += 1;
+    s.orig_loss = s.loss; s.cur_evals = 1; s.n_iter = 0;
+    return sc_le(T(g_inf), P(tol_grad)) ? A_END_STEP : A_ITER_HEAD;
+}
+// One more iteration of LBFGS.step (lbfgs_ls.py:304-306)?  true: counted; n_iter_total == 1 marks the optimiser's first.
+__host__ __device__ __forceinline__ bool step_iter_begin(OptScal& s, int max_iter) {
+    if (!(s.n_iter < max_iter)) return false;
+    s.n_iter += 1; s.n_iter_total += 1;
+    return true;
+}
+// The first step length of an iteration (lbfgs_ls.py:375-381); g_asum = |g|_1, read in the optimiser's first iteration only.
+__host__ __device__ __forceinline__ void step_first_length(OptScal& s, float g_asum, float lr) {
+    s.prev_loss = s.loss;
+    s.t = s.n_iter_total == 1 ? sc_mul(sc_pmin(P(1.0), sc_div(P(1.0), T(g_asum))), P((double)lr)) : P((double)lr);
+}
+// Directional derivative gtd = g . d: is d a descent direction worth a line search (lbfgs_ls.py:384-386)?
+__host__ __device__ __forceinline__ bool step_descends(Sc gtd, double tol_change) { return !sc_gt(gtd, P(-tol_change)); }
+// strong-Wolfe set-up (lbfgs_ls.py:39-52); d_inf = |d|inf
+__host__ __device__ __forceinline__ void ls_setup(OptScal& s, Sc gtd, float d_inf) {
+    s.ls_f0 = s.loss; s.ls_gtd0 = gtd; s.d_norm = T(d_inf);
+    s.ls_evals = 0; s.ls_iter = 0;
+    s.t_prev = P(0.0); s.f_prev = s.loss; s.gtd_prev = gtd; s.phase = PH_BRACKET;
+}
+
+// The line search is over: its lower end is the new point (lbfgs_ls.py:163-167, :398-404).  s.low still names the gradient;
+// returns the accepted step length.  (The one place that selects between members, not values: the end is read once and
+// nothing else of the bracket with it, and on values the fused tick kernels spill 4 to 20 bytes more per lane.)
+__host__ __device__ __forceinline__ Sc ls_accept(OptScal& s) {
+    const int lo = s.low;
+    const Sc t = lo ? s.br1 : s.br0;
+    s.loss = lo ? s.bf1 : s.bf0; s.t = t;
+    s.cache_valid = 1;
+    s.cur_evals += s.ls_evals; s.func_evals += s.ls_evals;
+    return t;
+}
+// The ordered end-of-iteration tests (lbfgs_ls.py:409-434); g_inf = |g|inf at the new point, step_inf = |t d|inf.
+__host__ __device__ __forceinline__ int step_iter_end(const OptScal& s, float g_inf, float step_inf, int max_iter, int max_eval,
+                                                      double tol_grad, double tol_change) {
+    const bool opt_cond = sc_le(T(g_inf), P(tol_grad));
+    if (s.n_iter == max_iter) return A_END_STEP;
+    if (s.cur_evals >= max_eval) return A_END_STEP;
+    if (opt_cond) return A_END_STEP;
+    if (sc_le(T(step_inf), P(tol_change))) return A_END_STEP;
+    if (sc_lt(sc_abs(sc_sub(s.loss, s.prev_loss)), P(tol_change))) return A_END_STEP;
+    return A_ITER_HEAD;
+}
+
+// run_fitting's bookkeeping after one LBFGS.step that returned `loss` (fitting.py:175-217), in two halves around the gtol
+// test, whose per-group reduction is the caller's.  First half: the non-finite stop and the ftol test.
+__host__ __device__ __forceinline__ bool fit_stops_on_loss(const OptScal& s, double loss, double ftol) {
+    if (isnan(loss) || isinf(loss)) return true;
+    if (s.outer > 0 && s.has_prev_outer && ftol > 0.0) {
+        const double pv = s.prev_loss_outer;
+        const double den = fmax(fmax(fabs(pv), fabs(loss)), 1.0);
+        if ((pv - loss) / den <= ftol) return true;
+    }
+    return false;
+}
+// Second half: the outer counter and maxiters, then the re-entry.  A_FINISH_STAGE: run_fitting returns; A_ENTRY: the next
+// LBFGS.step starts from the (loss, gradient) it already holds at the unchanged point (reuse); A_NONE: from an evaluation there.
+__host__ __device__ __forceinline__ int fit_next_step(OptScal& s, bool stop, double loss, int maxiters, int reuse) {
+    if (!stop) {
+        s.prev_loss_outer = loss; s.has_prev_outer = 1; s.outer += 1;
+        if (s.outer >= maxiters) stop = true;
+    }
+    if (stop) return A_FINISH_STAGE;
+    s.phase = PH_ENTRY;
+    if (reuse && s.cache_valid) { s.ref_evals += 1; return A_ENTRY; }
+    return A_NONE;
 }
 
 #pragma clang fp contract(fast)

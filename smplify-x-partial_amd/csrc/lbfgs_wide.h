@@ -6,7 +6,9 @@
 //   _strong_Wolfe / _cubic_interpolate  smplifyx/optimizers/lbfgs_ls.py:11-167
 // with the transitions and the rounding rule of oracle/lbfgs_machine.py and the mode / resume semantics of
 // lbfgs_tick_wave0<..., FIT = false> (lbfgs_body.h): one call of wide_tick consumes one evaluation and leaves the next point to
-// evaluate in the row W_XT.  Every scalar decision goes through lbfgs_scalar.h (Sc, cubic_interpolate, OptScal, fresh_state).
+// evaluate in the row W_XT.  Every transition decided on scalars alone is lbfgs_scalar.h's, shared with lbfgs_tick_wave0 (the
+// line search's bracket and zoom phases, the LBFGS.step prologue and end-of-iteration tests, run_fitting's bookkeeping); this
+// file is the phase / action skeleton, the vector work between those calls, and the history with its plain recursion.
 //
 // The vector layer V (a template parameter) owns how a row of N floats is stored and who works on it: opt_wide.hip gives one
 // workgroup of 1024 threads over rows in device memory, tests/lbfgs_wide_check.cpp a serial loop on the CPU.  The machine asks
@@ -63,9 +65,6 @@ struct WideState {
 
 // The history ring has hist_cap + 1 slots: the candidate pair of an iteration is formed in the free slot and stays there when
 // it is accepted (y.s > 1e-10), so no pair is copied and the oldest one is still whole when the candidate is refused.
-// c ? a : b on values (a ternary on members of the state would select between their addresses and keep the state in memory)
-__host__ __device__ __forceinline__ Sc sc_pick(int c, const Sc a, const Sc b) { Sc r; r.v = c ? a.v : b.v; r.t = c ? a.t : b.t; return r; }
-
 __host__ __device__ __forceinline__ int wide_ring_slots(int hist_cap) { return hist_cap + 1; }
 
 // init = 1: a fresh optimiser (lbfgs_ls.py:293-300) at the point the caller left in row W_X; init = 2: resume after a
@@ -97,15 +96,7 @@ __host__ __device__ __forceinline__ int wide_tick(V& v, const WideCfg& C, WideSt
     int glast_cached = 0;
     s.evals += 1; s.ref_evals += 1;
 
-#define W_ARMIJO_FAIL(f_new, t) sc_gt((f_new), sc_add(s.ls_f0, sc_mul(sc_mul(P(1e-4), (t)), s.ls_gtd0)))
-#define W_CURV_OK(gtd_new) sc_le(sc_abs(gtd_new), sc_mul(P(-0.9), s.ls_gtd0))
-    // bracket set-up: gradient slot 0 = row G0, slot 1 = the incoming gradient
-#define W_START_ZOOM(b0, b1, f0, f1, G0, gd0, gd1, done) do {                                            \
-        s.br0 = (b0); s.br1 = (b1); s.bf0 = (f0); s.bf1 = (f1); s.bgtd0 = (gd0); s.bgtd1 = (gd1);        \
-        v.copy(BG0, (G0)); v.copy(BG1, GIN);                                                              \
-        s.ls_done = (done) ? 1 : 0; s.insuf = 0;                                                         \
-        if (sc_le(s.bf0, s.bf1)) { s.low = 0; s.high = 1; } else { s.low = 1; s.high = 0; } } while (0)
-#define W_TRIAL(t) v.axpy(XT, XINIT, (float)(t).v, D)
+#define W_TRIAL() v.axpy(XT, XINIT, (float)s.t.v, D)
 
     int act = A_NONE;
     // ---------------------------------------------------------------- consume the evaluation
@@ -114,54 +105,20 @@ __host__ __device__ __forceinline__ int wide_tick(V& v, const WideCfg& C, WideSt
         s.loss = f_in;
         act = A_ENTRY;
     } else if (s.phase == PH_BRACKET) {
-        s.ls_evals += 1;
-        const Sc t = s.t;
-        const Sc gtd_new = T(v.dot(GIN, D));
-        if (s.ls_iter == max_ls) {
-            W_START_ZOOM(P(0.0), t, s.ls_f0, f_in, LSG0, s.ls_gtd0, gtd_new, false);
-            act = A_ZOOM_NEXT;
-        } else if (W_ARMIJO_FAIL(f_in, t) || (s.ls_iter > 1 && sc_ge(f_in, s.f_prev))) {
-            W_START_ZOOM(s.t_prev, t, s.f_prev, f_in, GPREV, s.gtd_prev, gtd_new, false);
-            act = A_ZOOM_NEXT;
-        } else if (W_CURV_OK(gtd_new)) {
-            // single-point bracket: the point itself is accepted
-            W_START_ZOOM(t, t, f_in, f_in, GIN, gtd_new, gtd_new, true);
-            s.low = 0; s.high = 1;
-            act = A_ZOOM_NEXT;
-        } else if (sc_ge(gtd_new, P(0.0))) {
-            W_START_ZOOM(s.t_prev, t, s.f_prev, f_in, GPREV, s.gtd_prev, gtd_new, false);
-            act = A_ZOOM_NEXT;
-        } else {
-            const Sc lo = sc_add(t, sc_mul(P(0.01), sc_sub(t, s.t_prev)));
-            const Sc hi = sc_mul(t, P(10.0));
-            const Sc t_next = cubic_interpolate(s.t_prev, s.f_prev, s.gtd_prev, t, f_in, gtd_new, true, lo, hi);
-            s.t_prev = t; s.f_prev = f_in; s.gtd_prev = gtd_new;
+        const int g0 = ls_bracket_eval(s, f_in, T(v.dot(GIN, D)), max_ls);
+        if (g0 == LS_EXTEND) {
             v.copy(GPREV, GIN);
-            s.t = t_next;
-            s.ls_iter += 1;
-            W_TRIAL(t_next);
+            W_TRIAL();
             act = A_NONE;
+        } else {       // a bracket: gradient slot 0 = the row named, slot 1 = the incoming gradient
+            v.copy(BG0, g0 == LS_G0_GIN ? GIN : g0 == LS_G0_LSG0 ? LSG0 : GPREV); v.copy(BG1, GIN);
+            act = A_ZOOM_NEXT;
         }
     } else {   // PH_ZOOM
-        s.ls_evals += 1; s.ls_iter += 1;
-        const Sc t = s.t;
-        const Sc gtd_new = T(v.dot(GIN, D));
-        const int lo = s.low, hi = s.high;
-        if (W_ARMIJO_FAIL(f_in, t) || sc_ge(f_in, sc_pick(lo, s.bf1, s.bf0))) {
-            if (hi) { s.br1 = t; s.bf1 = f_in; s.bgtd1 = gtd_new; } else { s.br0 = t; s.bf0 = f_in; s.bgtd0 = gtd_new; }
-            v.copy(hi ? BG1 : BG0, GIN);
-            if (sc_le(s.bf0, s.bf1)) { s.low = 0; s.high = 1; } else { s.low = 1; s.high = 0; }
-        } else {
-            if (W_CURV_OK(gtd_new)) s.ls_done = 1;
-            else if (sc_ge(sc_mul(gtd_new, sc_sub(sc_pick(hi, s.br1, s.br0), sc_pick(lo, s.br1, s.br0))), P(0.0))) {
-                if (hi) { s.br1 = s.br0; s.bf1 = s.bf0; s.bgtd1 = s.bgtd0; } else { s.br0 = s.br1; s.bf0 = s.bf1; s.bgtd0 = s.bgtd1; }
-                v.copy(hi ? BG1 : BG0, lo ? BG1 : BG0);
-            }
-            if (lo) { s.br1 = t; s.bf1 = f_in; s.bgtd1 = gtd_new; } else { s.br0 = t; s.bf0 = f_in; s.bgtd0 = gtd_new; }
-            v.copy(lo ? BG1 : BG0, GIN);
-        }
-        if (sc_lt(sc_mul(sc_abs(sc_sub(s.br1, s.br0)), s.d_norm), P(tol_change))) act = A_FINISH_LS;
-        else act = A_ZOOM_NEXT;
+        const ZoomMove m = ls_zoom_eval(s, f_in, T(v.dot(GIN, D)), tol_change);
+        if (m.copy_first) v.copy(m.end ? BG0 : BG1, m.end ? BG1 : BG0);
+        v.copy(m.end ? BG1 : BG0, GIN);
+        act = m.collapsed ? A_FINISH_LS : A_ZOOM_NEXT;
     }
 
     // ---------------------------------------------------------------- run until an evaluation is needed
@@ -169,17 +126,11 @@ __host__ __device__ __forceinline__ int wide_tick(V& v, const WideCfg& C, WideSt
     while (act != A_NONE && guard++ < 4096) {
         switch (act) {
         case A_ENTRY: {          // LBFGS.step prologue (lbfgs_ls.py:279-290); (loss, G) hold f, g at x
-            s.cache_valid = 1;
-            s.func_evals += 1;
-            s.orig_loss = s.loss;
-            s.cur_evals = 1; s.n_iter = 0;
-            if (sc_le(T(v.amax(G)), P(tol_grad))) act = A_END_STEP;
-            else act = A_ITER_HEAD;
+            act = step_entry(s, v.amax(G), tol_grad);
             break;
         }
         case A_ITER_HEAD: {      // direction + first trial point (lbfgs_ls.py:304-397)
-            if (!(s.n_iter < max_iter)) { act = A_END_STEP; break; }
-            s.n_iter += 1; s.n_iter_total += 1;
+            if (!step_iter_begin(s, max_iter)) { act = A_END_STEP; break; }
             if (s.n_iter_total == 1) {
                 v.neg(D, G);
                 s.hist_n = 0; s.hist_head = 0; s.H_diag = P(1.0);
@@ -221,61 +172,31 @@ __host__ __device__ __forceinline__ int wide_tick(V& v, const WideCfg& C, WideSt
                 v.r_store(D, q);
             }
             v.copy(PREVG, G);
-            s.prev_loss = s.loss;
-            Sc t;
-            if (s.n_iter_total == 1) t = sc_mul(sc_pmin(P(1.0), sc_div(P(1.0), T(v.asum(G)))), P((double)C.lr));
-            else t = P((double)C.lr);
-            s.t = t;
+            step_first_length(s, s.n_iter_total == 1 ? v.asum(G) : 0.f, C.lr);
             const Sc gtd = T(v.dot(G, D));
-            if (sc_gt(gtd, P(-tol_change))) { act = A_END_STEP; break; }
+            if (!step_descends(gtd, tol_change)) { act = A_END_STEP; break; }
             // strong-Wolfe set-up (lbfgs_ls.py:39-52)
             v.copy(XINIT, X);
             v.copy(LSG0, G);
             v.copy(GPREV, G);
-            s.ls_f0 = s.loss; s.ls_gtd0 = gtd;
-            s.d_norm = T(v.amax(D));
-            s.ls_evals = 0; s.ls_iter = 0;
-            s.t_prev = P(0.0); s.f_prev = s.loss; s.gtd_prev = gtd;
-            s.phase = PH_BRACKET;
-            W_TRIAL(t);
+            ls_setup(s, gtd, v.amax(D));
+            W_TRIAL();
             act = A_NONE;
             break;
         }
         case A_ZOOM_NEXT: {      // next zoom trial (lbfgs_ls.py:108-131)
-            if (s.ls_done || !(s.ls_iter < max_iter)) { act = A_FINISH_LS; break; }
-            Sc t = cubic_interpolate(s.br0, s.bf0, s.bgtd0, s.br1, s.bf1, s.bgtd1, false, P(0), P(0));
-            const Sc bmax = sc_pick(sc_gt(s.br1, s.br0), s.br1, s.br0);
-            const Sc bmin = sc_pick(sc_lt(s.br1, s.br0), s.br1, s.br0);
-            const Sc eps = sc_mul(P(0.1), sc_sub(bmax, bmin));
-            if (sc_lt(sc_pmin(sc_sub(bmax, t), sc_sub(t, bmin)), eps)) {
-                if (s.insuf || sc_ge(t, bmax) || sc_le(t, bmin)) {
-                    if (sc_lt(sc_abs(sc_sub(t, bmax)), sc_abs(sc_sub(t, bmin)))) t = sc_sub(bmax, eps);
-                    else t = sc_add(bmin, eps);
-                    s.insuf = 0;
-                } else s.insuf = 1;
-            } else s.insuf = 0;
-            s.t = t;
-            s.phase = PH_ZOOM;
-            W_TRIAL(t);
+            if (!ls_zoom_trial(s, max_iter)) { act = A_FINISH_LS; break; }
+            W_TRIAL();
             act = A_NONE;
             break;
         }
         case A_FINISH_LS: {      // accept the lowest bracket end (lbfgs_ls.py:163-167,398-434)
-            const int lo = s.low;
-            const Sc t = sc_pick(lo, s.br1, s.br0);
-            s.loss = sc_pick(lo, s.bf1, s.bf0); s.t = t;
-            v.copy(G, lo ? BG1 : BG0);
+            v.copy(G, s.low ? BG1 : BG0);
+            const Sc t = ls_accept(s);
             v.axpy(X, XINIT, (float)t.v, D);
-            s.cache_valid = 1;
-            const bool opt_cond = sc_le(T(v.amax(G)), P(tol_grad));
-            s.cur_evals += s.ls_evals; s.func_evals += s.ls_evals;
             v.trace(0, t.v, s.loss.v, s.ls_evals);
-            if (s.n_iter == max_iter) { act = A_END_STEP; break; }
-            if (s.cur_evals >= max_eval) { act = A_END_STEP; break; }
-            if (opt_cond) { act = A_END_STEP; break; }
-            if (sc_le(T(v.amax_scaled(D, (float)t.v)), P(tol_change))) { act = A_END_STEP; break; }
-            if (sc_lt(sc_abs(sc_sub(s.loss, s.prev_loss)), P(tol_change))) { act = A_END_STEP; break; }
-            act = A_ITER_HEAD;
+            const float g_inf = v.amax(G);
+            act = step_iter_end(s, g_inf, v.amax_scaled(D, (float)t.v), max_iter, max_eval, tol_grad, tol_change);
             break;
         }
         case A_END_STEP: {       // run_fitting bookkeeping (fitting.py:175-217)
@@ -289,14 +210,8 @@ __host__ __device__ __forceinline__ int wide_tick(V& v, const WideCfg& C, WideSt
                 act = A_NONE;
                 break;
             }
-            bool stop = false;
-            if (isnan(loss) || isinf(loss)) stop = true;
-            if (!stop && s.outer > 0 && s.has_prev_outer && C.ftol > 0.0) {
-                const double pv = s.prev_loss_outer;
-                const double den = fmax(fmax(fabs(pv), fabs(loss)), 1.0);
-                if ((pv - loss) / den <= C.ftol) stop = true;
-            }
-            if (!stop) {
+            bool stop = fit_stops_on_loss(s, loss, C.ftol);
+            if (!stop) {         // the gtol test (fitting.py:191) on the last gradient the closure returned
                 typename V::Row gl = glast_cached ? G : GIN;
                 bool all_small = true;     // (one group that is not small decides: the others need no look)
                 for (int gi = 0; gi < C.ngroups && all_small; ++gi) {
@@ -305,21 +220,9 @@ __host__ __device__ __forceinline__ int wide_tick(V& v, const WideCfg& C, WideSt
                 }
                 if (all_small) stop = true;
             }
-            if (!stop) {
-                s.prev_loss_outer = loss; s.has_prev_outer = 1;
-                s.outer += 1;
-                if (s.outer >= C.maxiters) stop = true;
-            }
-            if (stop) { act = A_FINISH_STAGE; break; }
-            s.phase = PH_ENTRY;
-            if (C.reuse && s.cache_valid) {
-                glast_cached = 1;
-                s.ref_evals += 1;
-                act = A_ENTRY;          // (loss, G) already hold f, g at the unchanged x
-            } else {
-                v.copy(XT, X);
-                act = A_NONE;
-            }
+            act = fit_next_step(s, stop, loss, C.maxiters, C.reuse);
+            if (act == A_ENTRY) glast_cached = 1;          // (loss, G) already hold f, g at the unchanged x
+            else if (act == A_NONE) v.copy(XT, X);
             break;
         }
         case A_FINISH_STAGE: {
@@ -336,9 +239,6 @@ __host__ __device__ __forceinline__ int wide_tick(V& v, const WideCfg& C, WideSt
     }
     if (v.leader()) { st.s = s; st.status = status; st.evals = evals_total; st.result = result; }
     return status;
-#undef W_ARMIJO_FAIL
-#undef W_CURV_OK
-#undef W_START_ZOOM
 #undef W_TRIAL
 }
 

@@ -6,10 +6,12 @@
 //   _strong_Wolfe / _cubic_interpolate  smplifyx/optimizers/lbfgs_ls.py:11-167
 // The state machine is lbfgs_tick_wave0 itself without the fit's stage sequencing (FIT = false), over a BatchDev that holds one
 // "stage" (0), an identity variable list and none of the model's buffers: one wavefront per problem consumes one evaluation
-// per launch and leaves the next point to evaluate in the caller's buffer.
+// per launch and leaves the next point to evaluate in the caller's buffer.  (The tick's scalar transitions: lbfgs_scalar.h.)
+// The host half of the C ABI that sfx_opt_wide_* shares -- argument checks, defaults, the trace's owner -- is opt_host.h.
 // Specification: oracle/lbfgs_machine.py (x_trial, feed(f, g), done, records).
 #include "../../include/sfx.h"
 #include "lbfgs_body.h"
+#include "opt_host.h"
 
 #include <memory>
 
@@ -55,7 +57,8 @@ void k_opt_tick(BatchDev D, const VarList* __restrict__ vls, int init, int step_
 }
 
 struct sfx_opt {
-    DevAlloc mem, trace_mem;
+    DevAlloc mem;
+    OptTrace trace;             // (D.trace / D.trace_n / D.trace_cap are its view)
     BatchDev D{};
     VarList* vl_dev = nullptr;
     int* evals = nullptr;
@@ -68,42 +71,21 @@ struct sfx_opt {
 extern "C" int sfx_opt_create(const sfx_opt_cfg* c, sfx_opt** out) {
     if (!c || !out) { sfx_set_error("null argument"); return -1; }
     *out = nullptr;
-    if (c->N < 1 || c->N > SFX_NVAR_MAX) { sfx_set_error("sfx_opt_create: N = %d, supported 1..%d", c->N, SFX_NVAR_MAX); return -1; }
-    if (c->B < 1) { sfx_set_error("sfx_opt_create: B = %d, at least 1 problem is needed", c->B); return -1; }
-    if (c->n_groups < 0 || c->n_groups > SFX_MAX_GROUPS) {
-        sfx_set_error("sfx_opt_create: %d parameter groups, at most %d", c->n_groups, SFX_MAX_GROUPS); return -1; }
-    if (c->n_groups > 0) {
-        long sum = 0;
-        for (int i = 0; i < c->n_groups; ++i) {
-            if (c->group_len[i] < 1) { sfx_set_error("sfx_opt_create: group %d has length %d", i, c->group_len[i]); return -1; }
-            sum += c->group_len[i];
-        }
-        if (sum != c->N) { sfx_set_error("sfx_opt_create: group lengths sum to %ld, N = %d", sum, c->N); return -1; }
-    }
-    if (c->history_size < 0 || c->history_size > SFX_HIST_MAX) {
-        sfx_set_error("sfx_opt_create: history_size %d, supported 1..%d (0 = %d)", c->history_size, SFX_HIST_MAX, SFX_HIST); return -1; }
-    if (c->maxiters < 1) { sfx_set_error("sfx_opt_create: maxiters = %d", c->maxiters); return -1; }
-    if (c->max_iter < 0 || c->max_eval < 0) { sfx_set_error("sfx_opt_create: negative max_iter / max_eval"); return -1; }
-    int dev_count = 0;
-    if (hipGetDeviceCount(&dev_count) != hipSuccess || dev_count == 0) {
-        (void)hipGetLastError();
-        sfx_set_error("sfx_opt_create: no HIP device (there is no CPU fallback)"); return -3;
-    }
+    if (const int rc = opt_check_cfg("sfx_opt_create", c, SFX_NVAR_MAX, SFX_MAX_GROUPS)) return rc;
     // every argument is accepted: from here on only the device can refuse, and ~sfx_opt releases whatever was acquired by then
     std::unique_ptr<sfx_opt> h(new sfx_opt());
     const int B = c->B, N = c->N;
     h->N = N;
     BatchDev& D = h->D;
     BatchCfgDev& C = D.cfg;
+    const OptDefaults d = opt_defaults(c);
     C.B = B; C.n_stages = 1;
     C.maxiters = c->maxiters; C.ftol = c->ftol; C.gtol = c->gtol; C.lr = c->lr;
-    C.lbfgs_max_iter = c->max_iter > 0 ? c->max_iter : c->maxiters;
-    C.max_eval = c->max_eval > 0 ? c->max_eval : C.lbfgs_max_iter * 5 / 4;
-    C.tol_grad = c->tolerance_grad >= 0 ? c->tolerance_grad : 1e-5;
-    C.tol_change = c->tolerance_change >= 0 ? c->tolerance_change : 1e-9;
-    C.hist_cap = c->history_size > 0 ? c->history_size : SFX_HIST;
+    C.lbfgs_max_iter = d.max_iter; C.max_eval = d.max_eval;
+    C.tol_grad = d.tol_grad; C.tol_change = d.tol_change;
+    C.hist_cap = d.hist_cap;
     C.hist_ring = std::max(C.hist_cap, SFX_HIST);
-    C.reuse = c->reuse_entry_eval ? 1 : 0;
+    C.reuse = d.reuse;
     C.side_thsh = 0.f;
     VarList vl{};                  // identity: optimiser index i = slot i of the problem's row
     vl.n = N;
@@ -140,17 +122,14 @@ extern "C" int sfx_opt_create(const sfx_opt_cfg* c, sfx_opt** out) {
 extern "C" void sfx_opt_destroy(sfx_opt* h) { delete h; }
 
 extern "C" int sfx_opt_begin(sfx_opt* h, int32_t mode, int32_t resume, const float* x0_dev, float* x_trial_dev, void* stream) {
-    if (!h || !x0_dev || !x_trial_dev) { sfx_set_error("sfx_opt_begin: null argument"); return -1; }
-    if (mode != 0 && mode != 1) { sfx_set_error("sfx_opt_begin: mode %d (0 = run_fitting, 1 = one LBFGS.step)", mode); return -1; }
-    if (resume && (mode != 1 || h->mode != 1)) {
-        sfx_set_error("sfx_opt_begin: resume continues a mode-1 run (one LBFGS.step) with another; there is none"); return -1; }
+    if (const int rc = opt_check_begin("sfx_opt_begin", !h || !x0_dev || !x_trial_dev, mode, resume, h ? h->mode : -1)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const BatchDev& D = h->D;
     if (!resume) {
         // the rows of an earlier run left in the ring are skipped with a factor 0: exact only while they are finite, which an
         // evaluation supplied from outside does not promise
         SFX_CHECK(hipMemsetAsync(D.hist, 0, (size_t)D.cfg.B * 2 * (D.cfg.hist_ring + 8) * SFX_NVAR_MAX * sizeof(float), s));
-        if (D.trace_n) SFX_CHECK(hipMemsetAsync(D.trace_n, 0, (size_t)D.cfg.B * sizeof(int), s));
+        if (const int rc = h->trace.empty(D.cfg.B, s)) return rc;
     }
     h->mode = mode;
     hipLaunchKernelGGL(k_opt_tick, dim3(D.cfg.B), dim3(64), 0, s, D, h->vl_dev, resume ? 2 : 1, mode, h->N, x0_dev,
@@ -160,8 +139,7 @@ extern "C" int sfx_opt_begin(sfx_opt* h, int32_t mode, int32_t resume, const flo
 }
 
 extern "C" int sfx_opt_tell(sfx_opt* h, const float* loss_dev, const float* grad_dev, float* x_trial_dev, void* stream) {
-    if (!h || !loss_dev || !grad_dev || !x_trial_dev) { sfx_set_error("sfx_opt_tell: null argument"); return -1; }
-    if (h->mode < 0) { sfx_set_error("sfx_opt_tell before sfx_opt_begin"); return -1; }
+    if (const int rc = opt_check_tell("sfx_opt_tell", "sfx_opt_begin", !h || !loss_dev || !grad_dev || !x_trial_dev, h ? h->mode : -1)) return rc;
     const BatchDev& D = h->D;
     hipLaunchKernelGGL(k_opt_tick, dim3(D.cfg.B), dim3(64), 0, (hipStream_t)stream, D, h->vl_dev, 0, h->mode, h->N,
                        (const float*)nullptr, loss_dev, grad_dev, x_trial_dev, h->evals);
@@ -202,25 +180,11 @@ extern "C" int sfx_opt_get(sfx_opt* h, float* x_dev, float* grad_dev, float* res
 
 extern "C" int sfx_opt_trace(sfx_opt* h, int32_t capacity) {
     if (!h || capacity < 0) { sfx_set_error("sfx_opt_trace: bad argument"); return -1; }
-    BatchDev& D = h->D;
-    SFX_CHECK(hipDeviceSynchronize());
-    h->trace_mem.clear(); D.trace = nullptr; D.trace_n = nullptr; D.trace_cap = 0;
-    if (capacity == 0) return 0;
-    // both buffers or neither: the kernel tests D.trace alone, so a half-attached trace must never be left behind
-    DevAlloc fresh;
-    float4* tr = fresh.alloc<float4>((size_t)D.cfg.B * capacity);
-    int* tn = fresh.zeros<int>(D.cfg.B);
-    if (fresh.failed) { sfx_set_error("sfx_opt_trace: %s", hipGetErrorString(hipGetLastError())); return -2; }
-    std::swap(h->trace_mem.ptrs, fresh.ptrs);
-    D.trace = tr; D.trace_n = tn; D.trace_cap = capacity;
-    return 0;
+    const int rc = h->trace.attach("sfx_opt_trace", h->D.cfg.B, capacity);
+    h->trace.view(h->D.trace, h->D.trace_n, h->D.trace_cap);
+    return rc;
 }
 
 extern "C" int sfx_opt_get_trace(sfx_opt* h, float* records, int32_t* counts) {
-    if (!h || !h->D.trace) { sfx_set_error("no trace buffer attached (sfx_opt_trace)"); return -1; }
-    const BatchDev& D = h->D;
-    SFX_CHECK(hipDeviceSynchronize());
-    if (records) SFX_CHECK(hipMemcpy(records, D.trace, (size_t)D.cfg.B * D.trace_cap * sizeof(float4), hipMemcpyDeviceToHost));
-    if (counts) SFX_CHECK(hipMemcpy(counts, D.trace_n, (size_t)D.cfg.B * sizeof(int), hipMemcpyDeviceToHost));
-    return 0;
+    return OptTrace::read(h ? &h->trace : nullptr, "sfx_opt_trace", h ? h->D.cfg.B : 0, records, counts);
 }

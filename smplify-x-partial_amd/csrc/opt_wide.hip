@@ -5,8 +5,9 @@
 //   FittingMonitor.run_fitting          smplifyx/fitting.py:147-217            (mode 0)
 //   LBFGS.step                          smplifyx/optimizers/lbfgs_ls.py:256-445 (mode 1)
 //   _strong_Wolfe / _cubic_interpolate  smplifyx/optimizers/lbfgs_ls.py:11-167
-// The state machine is lbfgs_wide.h (specification: oracle/lbfgs_machine.py); this file is its vector layer for ONE WORKGROUP of
-// 1024 threads per problem, the kernel that consumes one evaluation per launch, and the C ABI.
+// The state machine is lbfgs_wide.h over the scalar transitions of lbfgs_scalar.h, which the fit loop's tick shares (specification:
+// oracle/lbfgs_machine.py); this file is its vector layer for ONE WORKGROUP of 1024 threads per problem, the kernel that consumes
+// one evaluation per launch, and the C ABI, whose host half shared with sfx_opt_* is opt_host.h.
 //
 // Layout.  A row is N floats padded with zeros to a multiple of 4; thread t owns its 16-byte chunks t, t + 1024, ... (at most 8
 // at N = 32768), in every row alike: element-wise work needs no barrier, a thread only ever reads what it wrote itself.  The
@@ -23,6 +24,7 @@
 #include "../../include/sfx.h"
 #include "sfx_internal.h"
 #include "lbfgs_wide.h"
+#include "opt_host.h"
 
 #include <memory>
 #include <vector>
@@ -347,7 +349,8 @@ void k_opt_wide_gather(const WideDev D, int which, float* __restrict__ out) {
 }
 
 struct sfx_opt_wide {
-    DevAlloc mem, trace_mem;
+    DevAlloc mem;
+    OptTrace trace;             // (D.trace / D.trace_n / D.trace_cap are its view)
     WideDev D{};
     int mode = -1;              // of the last sfx_opt_wide_begin (-1: none yet)
     int* status_host = nullptr; // pinned: the readback of sfx_opt_wide_active
@@ -357,27 +360,7 @@ struct sfx_opt_wide {
 extern "C" int sfx_opt_wide_create(const sfx_opt_wide_cfg* c, sfx_opt_wide** out) {
     if (!c || !out) { sfx_set_error("null argument"); return -1; }
     *out = nullptr;
-    if (c->N < 1 || c->N > SFX_WIDE_NMAX) { sfx_set_error("sfx_opt_wide_create: N = %d, supported 1..%d", c->N, SFX_WIDE_NMAX); return -1; }
-    if (c->B < 1) { sfx_set_error("sfx_opt_wide_create: B = %d, at least 1 problem is needed", c->B); return -1; }
-    if (c->n_groups < 0 || c->n_groups > SFX_WIDE_MAX_GROUPS || (c->n_groups > 0 && !c->group_len)) {
-        sfx_set_error("sfx_opt_wide_create: %d parameter groups, at most %d", c->n_groups, SFX_WIDE_MAX_GROUPS); return -1; }
-    if (c->n_groups > 0) {
-        long sum = 0;
-        for (int i = 0; i < c->n_groups; ++i) {
-            if (c->group_len[i] < 1) { sfx_set_error("sfx_opt_wide_create: group %d has length %d", i, c->group_len[i]); return -1; }
-            sum += c->group_len[i];
-        }
-        if (sum != c->N) { sfx_set_error("sfx_opt_wide_create: group lengths sum to %ld, N = %d", sum, c->N); return -1; }
-    }
-    if (c->history_size < 0 || c->history_size > SFX_HIST_MAX) {
-        sfx_set_error("sfx_opt_wide_create: history_size %d, supported 1..%d (0 = %d)", c->history_size, SFX_HIST_MAX, SFX_HIST); return -1; }
-    if (c->maxiters < 1) { sfx_set_error("sfx_opt_wide_create: maxiters = %d", c->maxiters); return -1; }
-    if (c->max_iter < 0 || c->max_eval < 0) { sfx_set_error("sfx_opt_wide_create: negative max_iter / max_eval"); return -1; }
-    int dev_count = 0;
-    if (hipGetDeviceCount(&dev_count) != hipSuccess || dev_count == 0) {
-        (void)hipGetLastError();
-        sfx_set_error("sfx_opt_wide_create: no HIP device (there is no CPU fallback)"); return -3;
-    }
+    if (const int rc = opt_check_cfg("sfx_opt_wide_create", c, SFX_WIDE_NMAX, SFX_WIDE_MAX_GROUPS)) return rc;
     // every argument is accepted: from here on only the device can refuse, and ~sfx_opt_wide releases whatever was acquired by then
     std::unique_ptr<sfx_opt_wide> h(new sfx_opt_wide());
     WideDev& D = h->D;
@@ -386,12 +369,11 @@ extern "C" int sfx_opt_wide_create(const sfx_opt_wide_cfg* c, sfx_opt_wide** out
     D.B = B; D.Np = (N + 3) & ~3;
     C.N = N;
     C.maxiters = c->maxiters; C.ftol = c->ftol; C.gtol = c->gtol; C.lr = c->lr;
-    C.max_iter = c->max_iter > 0 ? c->max_iter : c->maxiters;
-    C.max_eval = c->max_eval > 0 ? c->max_eval : C.max_iter * 5 / 4;
-    C.tol_grad = c->tolerance_grad >= 0 ? c->tolerance_grad : 1e-5;
-    C.tol_change = c->tolerance_change >= 0 ? c->tolerance_change : 1e-9;
-    C.hist_cap = c->history_size > 0 ? c->history_size : SFX_HIST;
-    C.reuse = c->reuse_entry_eval ? 1 : 0;
+    const OptDefaults d = opt_defaults(c);
+    C.max_iter = d.max_iter; C.max_eval = d.max_eval;
+    C.tol_grad = d.tol_grad; C.tol_change = d.tol_change;
+    C.hist_cap = d.hist_cap;
+    C.reuse = d.reuse;
     C.ngroups = c->n_groups > 0 ? c->n_groups : 1;
     std::vector<int> g_off(C.ngroups), g_len(C.ngroups);
     for (int i = 0, o = 0; i < C.ngroups; ++i) { g_len[i] = c->n_groups > 0 ? c->group_len[i] : N; g_off[i] = o; o += g_len[i]; }
@@ -418,14 +400,11 @@ extern "C" int sfx_opt_wide_create(const sfx_opt_wide_cfg* c, sfx_opt_wide** out
 extern "C" void sfx_opt_wide_destroy(sfx_opt_wide* h) { delete h; }
 
 extern "C" int sfx_opt_wide_begin(sfx_opt_wide* h, int32_t mode, int32_t resume, const float* x0_dev, float* x_trial_dev, void* stream) {
-    if (!h || !x0_dev || !x_trial_dev) { sfx_set_error("sfx_opt_wide_begin: null argument"); return -1; }
-    if (mode != 0 && mode != 1) { sfx_set_error("sfx_opt_wide_begin: mode %d (0 = run_fitting, 1 = one LBFGS.step)", mode); return -1; }
-    if (resume && (mode != 1 || h->mode != 1)) {
-        sfx_set_error("sfx_opt_wide_begin: resume continues a mode-1 run (one LBFGS.step) with another; there is none"); return -1; }
+    if (const int rc = opt_check_begin("sfx_opt_wide_begin", !h || !x0_dev || !x_trial_dev, mode, resume, h ? h->mode : -1)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const WideDev& D = h->D;
     // (the ring needs no clearing: a recursion reads the hist_n rows written since the fresh start, and no others)
-    if (!resume && D.trace_n) SFX_CHECK(hipMemsetAsync(D.trace_n, 0, (size_t)D.B * sizeof(int), s));
+    if (!resume) { if (const int rc = h->trace.empty(D.B, s)) return rc; }
     h->mode = mode;
     hipLaunchKernelGGL(k_opt_wide_tick, dim3(D.B), dim3(WIDE_THREADS), 0, s, D, resume ? 2 : 1, mode, x0_dev,
                        (const float*)nullptr, (const float*)nullptr, x_trial_dev);
@@ -434,8 +413,7 @@ extern "C" int sfx_opt_wide_begin(sfx_opt_wide* h, int32_t mode, int32_t resume,
 }
 
 extern "C" int sfx_opt_wide_tell(sfx_opt_wide* h, const float* loss_dev, const float* grad_dev, float* x_trial_dev, void* stream) {
-    if (!h || !loss_dev || !grad_dev || !x_trial_dev) { sfx_set_error("sfx_opt_wide_tell: null argument"); return -1; }
-    if (h->mode < 0) { sfx_set_error("sfx_opt_wide_tell before sfx_opt_wide_begin"); return -1; }
+    if (const int rc = opt_check_tell("sfx_opt_wide_tell", "sfx_opt_wide_begin", !h || !loss_dev || !grad_dev || !x_trial_dev, h ? h->mode : -1)) return rc;
     const WideDev& D = h->D;
     hipLaunchKernelGGL(k_opt_wide_tick, dim3(D.B), dim3(WIDE_THREADS), 0, (hipStream_t)stream, D, 0, h->mode,
                        (const float*)nullptr, loss_dev, grad_dev, x_trial_dev);
@@ -475,25 +453,11 @@ extern "C" int sfx_opt_wide_get(sfx_opt_wide* h, float* x_dev, float* grad_dev, 
 
 extern "C" int sfx_opt_wide_trace(sfx_opt_wide* h, int32_t capacity) {
     if (!h || capacity < 0) { sfx_set_error("sfx_opt_wide_trace: bad argument"); return -1; }
-    WideDev& D = h->D;
-    SFX_CHECK(hipDeviceSynchronize());
-    h->trace_mem.clear(); D.trace = nullptr; D.trace_n = nullptr; D.trace_cap = 0;
-    if (capacity == 0) return 0;
-    // both buffers or neither: the kernel tests D.trace alone, so a half-attached trace must never be left behind
-    DevAlloc fresh;
-    float4* tr = fresh.alloc<float4>((size_t)D.B * capacity);
-    int* tn = fresh.zeros<int>(D.B);
-    if (fresh.failed) { sfx_set_error("sfx_opt_wide_trace: %s", hipGetErrorString(hipGetLastError())); return -2; }
-    std::swap(h->trace_mem.ptrs, fresh.ptrs);
-    D.trace = tr; D.trace_n = tn; D.trace_cap = capacity;
-    return 0;
+    const int rc = h->trace.attach("sfx_opt_wide_trace", h->D.B, capacity);
+    h->trace.view(h->D.trace, h->D.trace_n, h->D.trace_cap);
+    return rc;
 }
 
 extern "C" int sfx_opt_wide_get_trace(sfx_opt_wide* h, float* records, int32_t* counts) {
-    if (!h || !h->D.trace) { sfx_set_error("no trace buffer attached (sfx_opt_wide_trace)"); return -1; }
-    const WideDev& D = h->D;
-    SFX_CHECK(hipDeviceSynchronize());
-    if (records) SFX_CHECK(hipMemcpy(records, D.trace, (size_t)D.B * D.trace_cap * sizeof(float4), hipMemcpyDeviceToHost));
-    if (counts) SFX_CHECK(hipMemcpy(counts, D.trace_n, (size_t)D.B * sizeof(int), hipMemcpyDeviceToHost));
-    return 0;
+    return OptTrace::read(h ? &h->trace : nullptr, "sfx_opt_wide_trace", h ? h->D.B : 0, records, counts);
 }

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import helpers as H
+import opt_drive_common as O
 import opt_ext_common as X
 import opt_wide_common as W
 from oracle.lbfgs_machine import StageMachine
@@ -27,53 +28,14 @@ def gpu():
     return torch.device("cuda:0")
 
 
+CLS, LABEL = "WideOptimizer", "opt-wide"      # the handle under test: its class in smplifyx_amd.engine, the label of its check_bound lines
+
+
 def _opt(B, N, **hyper):
-    from smplifyx_amd import engine
-    return engine.WideOptimizer(B, N, **hyper)
+    return O.opt(CLS, B, N, **hyper)
 
 
-def _bits(a):
-    return np.ascontiguousarray(np.asarray(a, np.float32)).view(np.uint32)
-
-
-def _drive(opt, x0, evaluate, mode="fit", resume=False, extra=0, limit=400):
-    """Run `opt` from x0 [B][N] (numpy) on evaluate(x_trial, k) -> (f [B], g [B][N]) CUDA tensors until no problem is active (+
-    `extra` more evaluations).  Returns per evaluation the trial points, losses and gradients as numpy arrays, and the number of
-    evaluations after which active() first read 0."""
-    dev = opt.device
-    xt = opt.begin(torch.tensor(x0, device=dev), mode=mode, resume=resume)
-    xs, fs, gs, n_done = [], [], [], None
-    k = 0
-    while True:
-        if n_done is None and opt.active() == 0:
-            n_done = k
-        if n_done is not None and k >= n_done + extra:
-            break
-        f, g = evaluate(xt, k)
-        xs.append(xt.cpu().numpy().copy()); fs.append(f.cpu().numpy().copy()); gs.append(g.cpu().numpy().copy())
-        opt.tell(f.contiguous(), g.contiguous())
-        k += 1
-        assert k < limit, "the device optimiser does not finish"
-    return np.stack(xs), np.stack(fs), np.stack(gs), n_done
-
-
-def _family(b0=0):
-    return lambda xt, k: X.family_eval(xt, b0)
-
-
-def _check_replay(label, what, hyper, x0, xs, fs, gs, res, trace, bound):
-    """One problem's recorded run against the machine fed the same evaluations: the same number of evaluations (res['evals']),
-    the same records, the same result, trial points within the bound."""
-    n = int(res["evals"])
-    m = StageMachine(x0, dtype=np.float32, **hyper)
-    err, lock = X.replay(m, xs[:n], fs[:n], gs[:n])
-    assert lock, (label, what, "the machine wants %s evaluations, the device consumed %d" % ("fewer" if m.done else "more", n))
-    assert res["status"] == 1
-    assert X.same_result(res["result"], m.result), (label, what, res["result"], m.result)
-    if trace is not None:
-        assert X.same_records(trace, m.records), (label, what, trace[:, 0], [r[0] for r in m.records])
-    H.check_bound(label, what, err, bound)
-    return err
+_bits, _drive, _family, _check_replay = O.bits, O.drive, O.family, O.check_replay
 
 
 def _variant_bound(x0, hyper, xs, fs, gs):
@@ -115,22 +77,8 @@ def test_golden_trajectories(gpu, N):
 
 
 # ---------------------------------------------------------------- 2. replay on the family
-_RUNS = {}
-
-
 def _family_run(N, hname):
-    """The batch of NB problems of a configuration, run once per session: (x0, xs, fs, gs, result, trace, n_done)."""
-    key = (N, hname)
-    if key not in _RUNS:
-        opt = _opt(X.NB, N, **X.HYPER[hname])
-        opt.trace(256)
-        x0 = np.stack([X.family_x0(N, b) for b in range(X.NB)])
-        xs, fs, gs, n_done = _drive(opt, x0, _family())
-        r = opt.result()
-        r = dict(r, x=r["x"].cpu().numpy(), grad=r["grad"].cpu().numpy())
-        _RUNS[key] = (x0, xs, fs, gs, r, opt.get_trace(), n_done)
-        opt.close()
-    return _RUNS[key]
+    return O.family_run(CLS, N, hname)
 
 
 @pytest.mark.parametrize("N,hname", W.WIDE_CONFIGS)
@@ -186,67 +134,15 @@ def test_batch_independence_bit_for_bit(gpu):
 
 # ---------------------------------------------------------------- 4. step mode
 def test_step_mode_equals_fit_mode(gpu):
-    """K = 4 rounds of ONE LBFGS.step (the first fresh, the others resumed) = one run_fitting with maxiters = 4 and both of its
-    own tests off, bit for bit: trial points, entry losses, final point."""
-    N, K = 4097, 4
-    lb = dict(max_iter=20, max_eval=25)
-    x0 = np.stack([X.family_x0(N, b) for b in range(X.NB)])
-    fit = _opt(X.NB, N, maxiters=K, ftol=0.0, gtol=0.0, **lb)
-    fit.trace(256)
-    fxs, _, _, _ = _drive(fit, x0, _family())
-    rf = fit.result()
-    entry_fit = [t[t[:, 0] == 1][:, 1].astype(np.float32) for t in fit.get_trace()]
-    step = _opt(X.NB, N, **lb)
-    x, done, sxs, entry = x0, np.zeros(X.NB, np.int64), [[] for _ in range(X.NB)], []
-    for k in range(K):
-        rxs, _, _, _ = _drive(step, x, _family(), mode="step", resume=k > 0)
-        rs = step.result()
-        assert (rs["status"] == 1).all()
-        for b in range(X.NB):
-            sxs[b].append(rxs[:int(rs["evals"][b] - done[b]), b])
-        done = rs["evals"].astype(np.int64)
-        entry.append(rs["result"].copy())
-        x = rs["x"].cpu().numpy()
-    entry = np.stack(entry, 1)
-    for b in range(X.NB):
-        assert len(entry_fit[b]) == K and np.array_equal(_bits(entry_fit[b]), _bits(entry[b])), ("entry losses", b)
-        assert done[b] == rf["evals"][b]
-        assert np.array_equal(_bits(np.concatenate(sxs[b])), _bits(fxs[:done[b], b])), ("trial points", b)
-    assert np.array_equal(_bits(x), _bits(rf["x"].cpu().numpy())), "final point"
-    fit.close(); step.close()
+    """opt_drive_common.step_mode_equals_fit_mode at N = 4097."""
+    O.step_mode_equals_fit_mode(CLS, 4097)
 
 
 # ---------------------------------------------------------------- 5. a non-finite evaluation
 def test_a_nan_loss_ends_one_problem_only(gpu):
-    """opt_ext_common.NAN_CONFIG through the wide handle: the poisoned problem goes on and ends as the machine fed the same
-    evaluations does, and the other four never notice: bit for bit their clean run."""
-    (N, hname), bad = X.NAN_CONFIG, X.NAN_PROBLEM
+    """opt_drive_common.nan_loss_ends_one_problem_only: opt_ext_common.NAN_CONFIG through the wide handle."""
     assert X.NAN_CONFIG in W.WIDE_CONFIGS
-    hyper = X.HYPER[hname]
-    x0, xs, fs, gs, r, _, _ = _family_run(N, hname)
-
-    def evaluate(xt, k):
-        f, g = X.family_eval(xt)
-        if k == X.NAN_AT:
-            f = f.clone(); f[bad] = float("nan")
-        return f, g
-    opt = _opt(X.NB, N, **hyper)
-    opt.trace(256)
-    nxs, nfs, ngs, _ = _drive(opt, x0, evaluate)
-    rn = opt.result()
-    tr = opt.get_trace()
-    for b in range(X.NB):
-        n = int(rn["evals"][b])
-        if b == bad:
-            assert n > X.NAN_AT + 1 and np.isnan(nfs[X.NAN_AT, b])
-            res = dict(evals=n, status=rn["status"][b], result=rn["result"][b])
-            _check_replay("opt-wide family", "N=%d %s NaN loss trial points" % (N, hname), hyper, x0[b], nxs[:, b], nfs[:, b], ngs[:, b],
-                          res, tr[b], X.bound(N, hname))
-            continue
-        assert n == r["evals"][b]
-        assert np.array_equal(_bits(nxs[:n, b]), _bits(xs[:n, b])) and np.array_equal(_bits(rn["result"][b]), _bits(r["result"][b]))
-        assert np.array_equal(_bits(rn["x"].cpu().numpy()[b]), _bits(r["x"][b]))
-    opt.close()
+    O.nan_loss_ends_one_problem_only(CLS, LABEL + " family")
 
 
 # ---------------------------------------------------------------- 6. the Python surface
